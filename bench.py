@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the PF hot path (one "step" = one PF frame: propagate + weight + resample) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the stream, warms up, times the K
+steps, writes the last step's outputs if --dump-outputs is given, and prints the JSON line.  Everything measured
+beside the headline (the kernel pass behind `roofline`, `cpu_baseline`, `worst_case`, `multi_stream`,
+`scaling_reference`, `single_stream`, `parity_mode`) runs only with --full; without it those keys are null.
 
 N = 1 runs BASELINE.json configs[1] (C2: 5 LEDs, 100k particles, 50 blobs/frame, fp32 state).  For N > 1
 the driver launches one process per GPU with torch.distributed.run and every rank runs configs[4] (C5): an
@@ -13,7 +18,13 @@ Inputs are resident in HBM before the timed region (pfmpe_stage_blob_bank); each
 which is blocking (its last act is the stream synchronize that brings the winner to the host), so the
 timed region is bracketed by barrier + device sync on both sides.
 
-Extra objects on the JSON line:
+--dump-outputs DIR writes what a caller of the timed path holds after its last timed step, as DIR/<name>.npy
+(float64): the step's record (`record`, `winner_pose`, `most_likely_pose`, `pairs`) and the engine's state
+(`particles`: pfmpe_get_particles(1), `weights`: pfmpe_get_weights; above DUMP_MAX_ROWS particles a fixed seeded
+sample of rows, whose indices are `sample_index`).  Inputs depend on the arguments alone, so two builds of the
+library run with the same arguments can be compared file by file.  Ranks above 0 write to DIR/rank<r>/.
+
+Extra objects on the JSON line (--full):
   roofline     — dominant kernel's algorithmic bytes per launch / its HIP-event-timed average duration
   cpu_baseline — the oracle (single-thread restatement of the reference loop, O(N^2) resample) timed on
                  this host on a bounded sample of the same workload (rank 0, N = 1 only)
@@ -40,6 +51,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything measured beside the headline figure: the kernel pass (roofline), the CPU "
+                         "baselines, the worst-case frames, the multi-stream sweep, the C3/C4/C5 and parity-mode points")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--config", default="", choices=["", "C1", "C2", "C3", "C4", "C5"],
                     help="default: C2 (BASELINE.json configs[1]) at --gpus 1, C5 (configs[4]: one 1M-particle "
                          "stream per GPU) at --gpus > 1")
@@ -99,6 +115,79 @@ def info_or(pf, eng, key, default=-1):
         return eng.info(key)
     except pf.PFError:
         return default
+
+
+PARALLEL_MIN_FRAMES = 4000  # below this one process builds the stream as fast as a pool starts
+
+
+def _stream_span(job):
+    """Frames lo .. hi-1 of synthetic.make_stream(cfg, n >= hi, t0): the body of its loop, frame by frame (every
+    frame depends on its index alone; tests/test_bench_dist.py holds the two equal)."""
+    from pf_monocular_pose_estimator_amd import synthetic as syn
+    cfg, lo, hi, t0 = job
+    markers = syn.markers_for(cfg.M)
+    dt = cfg.dt
+    cols = [[] for _ in range(6)]  # time, truth, current_pose, predicted_pose, prediction, blobs
+    for f in range(lo, hi):
+        t = t0 + (f + 1) * dt
+        T, Tc, Tp = syn.truth_pose(t), syn.truth_pose(t - dt), syn.truth_pose(t - 2 * dt)
+        Pm = syn.se3_exp(syn.se3_log(syn.rigid_inv(Tp) @ Tc) / dt * dt)
+        for c, v in zip(cols, (t, T, syn.to12(Tc), syn.to12(Tc @ Pm), syn.to12(Pm),
+                               syn.blobs_for_frame(cfg, T, f, markers))):
+            c.append(v)
+    # a span travels back as a few stacked arrays (blobs too when every frame has as many), not as hi - lo objects
+    if len({b.shape for b in cols[5]}) == 1:
+        cols[5] = np.stack(cols[5])
+    return lo, [np.stack(c) for c in cols[:5]] + [cols[5]]
+
+
+def make_stream(cfg, n_frames: int, procs: int = 0, t0: float = 0.5):
+    """synthetic.make_stream(cfg, n_frames), the same frames bit for bit; a long stream (a run of many timed steps)
+    is built by `procs` worker processes (default: the CPUs this process may use, 16 at most), since the generator
+    costs ~0.4 ms per frame and is no part of what is measured."""
+    from pf_monocular_pose_estimator_amd import synthetic as syn
+    if procs <= 0:
+        procs = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+    if n_frames < PARALLEL_MIN_FRAMES or procs < 2:
+        return syn.make_stream(cfg, n_frames, t0)
+    import multiprocessing as mp
+    span = -(-n_frames // (4 * procs))
+    jobs = [(cfg, lo, min(n_frames, lo + span), t0) for lo in range(0, n_frames, span)]
+    pool = mp.get_context("spawn").Pool(procs)  # spawn: the workers share nothing with a process that opens a GPU
+    try:
+        parts = pool.map(_stream_span, jobs)
+        pool.close()
+    except BaseException:
+        pool.terminate()
+        raise
+    finally:
+        pool.join()
+    st = syn.Stream(cfg, syn.markers_for(cfg.M), syn.K_README.copy())
+    for lo, (tm, truth, cur, pred, prd, blobs) in parts:
+        st.frames.extend(syn.Frame(lo + i, float(tm[i]), truth[i], cur[i], pred[i], prd[i], blobs[i], cfg.dt)
+                         for i in range(len(tm)))
+    return st
+
+
+DUMP_MAX_ROWS = 400_000  # particles + weights + sample_index: 14 doubles a row, 44.8 MB at the cap (limit: 64 MB)
+RECORD_FIELDS = ("iters", "kept_iter", "most_likely_idx", "accepted", "resampled", "winner_idx", "n_corr", "flag_fail",
+                 "highest_prob", "prob_sum")
+
+
+def dump_outputs(dirpath: str, eng, out):
+    """--dump-outputs: the last timed step's record and the engine state it left, one float64 .npy per array."""
+    os.makedirs(dirpath, exist_ok=True)
+    rec = out.as_dict()
+    arrays = {"record": np.array([rec[k] for k in RECORD_FIELDS], dtype=np.float64),  # in RECORD_FIELDS order
+              "winner_pose": rec["winner_pose"], "most_likely_pose": rec["most_likely_pose"], "pairs": rec["pairs"]}
+    particles, weights = eng.get_particles(1), eng.get_weights()
+    if particles.shape[0] > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(64).choice(particles.shape[0], DUMP_MAX_ROWS, replace=False))
+        particles, weights = particles[idx], weights[idx]
+        arrays["sample_index"] = idx
+    arrays["particles"], arrays["weights"] = particles, weights
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def kernel_pass(pf, eng, frames):
@@ -469,8 +558,10 @@ def main():
     sid = rank if args.stream_id < 0 else args.stream_id
     cfg = syn.StreamConfig(base.name, M=base.M, B=base.B, N=args.particles or base.N, heavy=base.heavy, seed=sid)
     n_frames = args.warmup + args.steps
-    kframes = 0 if args.no_timing else (args.kernel_frames or max(20, args.steps))
-    st = syn.make_stream(cfg, n_frames + kframes)
+    full = args.full  # everything beside the headline figure
+    kframes = (args.kernel_frames or max(20, args.steps)) if full and not args.no_timing else 0
+    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    st = make_stream(cfg, n_frames + kframes, procs=max(1, min(16, cpus // world)))
     state = args.state or ("f16" if cfg.name == "C4" else "f32")
     state_dtype = {"f32": pf.STATE_F32, "f16": pf.STATE_F16, "f64": pf.STATE_F64}[state]
     # one GPU per rank; PFMPE_BENCH_DEVICE pins every rank to one device (rehearsing the multi-rank launch
@@ -518,6 +609,9 @@ def main():
     accepted = sum(o.accepted for o in outs)
     stats = eng.kernel_stats()
     eng.set_option(pf.OPT_TIMING, 0)
+    if args.dump_outputs and len(outs):  # before anything else steps the engine
+        dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"), eng,
+                     outs[len(outs) - 1])
     kiters = iters
     if kframes:  # the kernel pass: the stream's next kframes frames, every one bracketed (kernel_pass)
         stats, kouts = kernel_pass(pf, eng, frames[n_frames:n_frames + kframes])
@@ -537,7 +631,7 @@ def main():
     elapsed, total_updates = combine_ranks(dist, elapsed, updates)
 
     worst = None
-    if args.worst_frames > 0 and not args.occlude:  # untimed by the driver's contract: reported beside the line
+    if full and args.worst_frames > 0 and not args.occlude:  # untimed by the driver's contract: reported beside the line
         wf = occluded_frames(eng, st, sid, args.worst_frames, n_frames)
         eng.step(wf[0])  # warm the host-blob path
         prepared = eng.prepare_batch(wf[1:])
@@ -551,9 +645,9 @@ def main():
                  "accept_rate": sum(o.accepted for o in wo) / len(wo)}
 
     multi = None
-    default_line = world == 1 and config == "C2" and not args.config and not args.occlude
+    default_line = full and world == 1 and config == "C2" and not args.config and not args.occlude
     sweep = args.multi_sweep or ("1,4,8,16,32" if world == 1 and config == "C2" and not args.occlude else "")
-    if sweep == "none":
+    if sweep == "none" or not full:
         sweep = ""
     if sweep and rank == 0:  # untimed by the driver's contract: reported beside the line
         Sb = {"f32": 48, "f16": 24, "f64": 96}[state]
@@ -595,7 +689,7 @@ def main():
                          "pairs identical to the CPU oracle), timed like the main line")
 
     scale_ref = None
-    if world == 1 and config == "C2" and not args.config and not args.occlude and args.scale_ref_steps > 0:
+    if default_line and args.scale_ref_steps > 0:
         # the per-GPU workload of the --gpus N > 1 lines (one C5 stream per GPU) on this one GPU, so the
         # N = 1 point of a scaling curve exists for the same workload (untimed by the driver's contract)
         scale_ref = single_stream_point(pf, syn, syn.CONFIGS["C5"], args.scale_ref_steps, 10, prm.rng_mode, device,
@@ -658,7 +752,7 @@ def main():
                                             "launch gaps and the host round trip"},
                     "issue": issue_roof(pmc, dom, avg_s * 1e6)}
         cpu = None
-        if world == 1 and args.cpu_frames > 0:
+        if full and world == 1 and args.cpu_frames > 0:
             cpu = cpu_baseline(cfg, args.cpu_frames, args.c1_frames)
         line = {
             "metric": "particle-updates/sec (propagate+weight+resample) per GPU; frames/sec at N_particles",

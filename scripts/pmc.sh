@@ -1,6 +1,7 @@
 #!/bin/bash
 # PMC passes (each its own rocprofv3 run, no trace domains): pmc.sh <tag> <bench args...>
-cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out; export TMPDIR=/tmp
+# Output under $PFMPE_OUT (default bench_out).
+cd "$(dirname "$0")/.."; out=${PFMPE_OUT:-bench_out}; mkdir -p $out; export TMPDIR=/tmp
 tag=$1; shift
 i=0
 for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVE_CYCLES" \
@@ -8,7 +9,7 @@ for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD S
            "SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS" \
            "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d gpurun_out/pmc_$tag/p$i -o run -- python3 bench.py --cpu-frames 0 --no-timing "$@" > gpurun_out/pmc_${tag}_p$i.log 2>&1
-  rc=$?; echo "pass $i rc=$rc"; if [ $rc -ne 0 ]; then tail -5 gpurun_out/pmc_${tag}_p$i.log; exit $rc; fi
+  timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $out/pmc_$tag/p$i -o run -- python3 bench.py --full --cpu-frames 0 --no-timing "$@" > $out/pmc_${tag}_p$i.log 2>&1
+  rc=$?; echo "pass $i rc=$rc"; if [ $rc -ne 0 ]; then tail -5 $out/pmc_${tag}_p$i.log; exit $rc; fi
 done
-python3 scripts/pmc_summary.py gpurun_out/pmc_$tag --json gpurun_out/pmc_$tag.json
+python3 scripts/pmc_summary.py $out/pmc_$tag --json $out/pmc_$tag.json

@@ -3,7 +3,7 @@
   python3 scripts/trace_check.py <trace dir> <bench log of the traced run> [--untraced <bench log of the same
                                  command without the profiler>] [--warmup W --steps S]
 
-bench.py times its main line without HIP-event brackets and then runs a kernel pass of K more frames with every
+bench.py --full times its main line without HIP-event brackets and then runs a kernel pass of K more frames with every
 frame bracketed (bench.py kernel_pass); roofline.avg_us is that pass's average of the dominant kernel.  Under the
 profiler the HIP events read long (its own completion signals on every dispatch), so the line to check is the same
 command's run WITHOUT the profiler (--untraced); the traced run's own line is printed beside it.  The trace holds the
