@@ -3352,6 +3352,23 @@ struct ResampleLds {
   int map[kWaves][64];
 };
 
+// The in-launch frames' tail, two independent steps (each exact: no arithmetic, association or RNG use changes;
+// the defines exist for A/B builds):
+//  PFMPE_TAIL_PUBLISH_EARLY  the block's count partial and winner candidate are published BEFORE its scatter (they
+//    need the counts and the staged rows, not the new prior, which nobody reads before the next launch);
+//  PFMPE_TAIL_KT_IN_COUNTS   k_frame2: K_total = F(run) is evaluated by lane 1 of the count phase's block-uniform
+//    F(rin) call (wave 0) instead of serially by one lane inside the top, where every wave of every block waits.
+#ifndef PFMPE_TAIL_PUBLISH_EARLY
+#define PFMPE_TAIL_PUBLISH_EARLY 1
+#endif
+#ifndef PFMPE_TAIL_KT_IN_COUNTS
+#define PFMPE_TAIL_KT_IN_COUNTS 1
+#endif
+// k_frame2's hand-over from the top to the count phase (LDS; PFMPE_TAIL_KT_IN_COUNTS)
+struct Frame2Tail {
+  double run;  // the top's running max over the groups: K_total = F(run)
+  int kt;      // K_total (<= N), stored by wave 0 before the barrier that publishes sh.hi
+};
 // ---- stratified resampling of one block (PE:666-682) + count partials -> winner -> frame record.
 // wd: the thread's kept raw weight (0 for invalid lanes); P: its kept propagated particle when have_P,
 // else regenerated here from A (P_in unused).  Called by every thread; the caller checked c.done && c.accepted.
@@ -3368,8 +3385,10 @@ __device__ __forceinline__ void resample_phase(
     CountPart* __restrict__ cpart, CountPart* __restrict__ cgroup, uint32_t* __restrict__ gcount,
     uint32_t* __restrict__ tcount, uint32_t* __restrict__ counts, RecOut* __restrict__ out, int32_t seq,
     uint64_t* __restrict__ stamps, uint32_t* __restrict__ flat, int blk, const RawState<SP>* raw_in = nullptr,
-    unsigned long long* __restrict__ winkey = nullptr) {
+    unsigned long long* __restrict__ winkey = nullptr, Frame2Tail* f2 = nullptr) {
   constexpr bool INLAUNCH = MODE != 0;
+  constexpr bool EARLY = INLAUNCH && PFMPE_TAIL_PUBLISH_EARLY;      // publish, then scatter
+  constexpr bool KT_HERE = MODE == 2 && PFMPE_TAIL_KT_IN_COUNTS;    // f2: K_total = F(f2->run) is evaluated here
   // fp16 stored set (RAW): the wave stages its kept particles' stored values as they are (12 halves, 24 B a
   // row) and the scatter copies them out unchanged, no widening / narrowing (raw_in: the lane's values)
   constexpr bool RAWROW = RAW && !std::is_same<T, SP>::value;
@@ -3380,7 +3399,9 @@ __device__ __forceinline__ void resample_phase(
   const bool valid = n < N;
   const int kiter = c.kept_iter, iters = c.iters;
   const double S = c.S;
-  const int64_t Kt = c.K_total;
+  // (constant after inlining: k_frame's flat count barrier is MODE 2 without the hand-over)
+  const bool kt_here = KT_HERE && f2 != nullptr;
+  int64_t Kt = c.K_total;
 
   // fp32 weights of an M >= 4 frame, all in [0, 32) in this wave: the in-wave prefix as a fixed-point integer scan
   // (wave_incl_sum_fx, exact and equal to the fp64 scan); otherwise the fp64 scan.  Wave-uniform choice.
@@ -3435,11 +3456,22 @@ __device__ __forceinline__ void resample_phase(
   int hi = count_targets_wave<T, RNG>(fa, iters, R, valid);  // every lane (one basic block); invalid lanes:
   hi = valid ? hi : N;                                         // their R is the wave's last, the result unused
   if (lane == 63) sh.hi[wv] = hi;
+  int lo0 = 0;
+  if (kt_here && wv == 0) {  // F(rin) as below, before the barrier, with K_total = F(run) in lane 1 of the same call
+                             // (count_targets(run), which the top would otherwise evaluate in one lane while every
+                             // wave of every block waits); both lanes take the rare paths
+    lo0 = count_targets_wave<T, RNG>(fa, iters, lane == 1 ? f2->run : rin, lane <= 1);
+    const int kt = lane_value(lo0, 1);
+    if (lane == 0) f2->kt = kt;
+  }
   __syncthreads();
   int lo = wave_shr1(hi, 0);
-  if (wv == 0) {  // F(rin), block-uniform: every lane of wave 0 takes the straight-line common case together (rin is
-                  // the same in every lane), only lane 0 the rare paths
-    const int lo0 = count_targets_wave<T, RNG>(fa, iters, rin, lane == 0);
+  if (kt_here) {
+    Kt = f2->kt;
+    if (lane == 0) lo = wv == 0 ? lo0 : sh.hi[wv - 1];
+  } else if (wv == 0) {  // F(rin), block-uniform: every lane of wave 0 takes the straight-line common case together
+                         // (rin is the same in every lane), only lane 0 the rare paths
+    lo0 = count_targets_wave<T, RNG>(fa, iters, rin, lane == 0);
     if (lane == 0) lo = lo0;
   } else if (lane == 0) {
     lo = sh.hi[wv - 1];
@@ -3538,7 +3570,8 @@ __device__ __forceinline__ void resample_phase(
 #pragma unroll
     for (int q = 0; q < 12; ++q) rows[lane].q[q] = P[q];  // also read by wave 0 for the block candidate
   }
-  if (we > wa) {
+  auto scatter = [&]() __attribute__((always_inline)) {
+    if (we <= wa) return;
     int* map = sh.map[wv];
     int carry = -1;
     if (stamps && threadIdx.x == 0) stamp_max(stamps, 21, rt_now());
@@ -3575,125 +3608,139 @@ __device__ __forceinline__ void resample_phase(
         }
       }
     }
-  }
-
-  if (stamps && threadIdx.x == 0) stamp_max(stamps, 12, rt_now());
+  };
+  // In-launch frames (EARLY): the block's count partial and winner candidate need the counts (sh.c / sh.ci) and the
+  // staged rows, not the new prior, which nobody reads before the next launch (stream order).  So after the one
+  // barrier that makes those visible, wave 0 publishes the partial and wave 1 the candidate, waves 2 and 3 scatter at
+  // once, and waves 0 and 1 scatter after publishing; block 0's wave 0 polls and writes the frame record before its
+  // own scatter (the record waits for nothing of block 0's that it does not need).  After publishing, no wave but
+  // block 0's wave 0 waits for anything, so blocks still retire without waiting once the host has the record.
+  // Otherwise (k_resample): scatter, barrier, block partial.
+  auto scatter_end = [&]() __attribute__((always_inline)) {
+    scatter();
+    if (stamps && threadIdx.x == 0) stamp_max(stamps, 12, rt_now());
+  };
+  if (!EARLY) scatter_end();
   __syncthreads();
-  if (!INLAUNCH) {  // block partial + the block argmax's kept pose (plain stores: the launch boundary
-                    // publishes them); a block without copies has no propagated row, k_resample_final regenerates
-    if (wv == 0) {
-      int bv = sh.c[0], bi = sh.ci[0];
-      for (int w = 1; w < kWaves; ++w) cmb_max(bv, bi, sh.c[w], sh.ci[w]);
-      if (lane == 0) cpart[blk] = CountPart{bv, bi};
-      // one-stream k_resample: the block's candidate also goes into the sharded winner keys (max count, then the
-      // lowest index: count in the high word, 2^31 - 1 - index in the low one), so k_resample_final reads
-      // kWinShards keys instead of every block's partial (C4: 39k partials, three round trips)
-      if (winkey && lane == 0 && bv >= 0)
-        __hip_atomic_fetch_max(winkey + (blk & (kWinShards - 1)) * kWinStride, win_key(bv, bi), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-      const int loc = bi - blk * kBlock;
-      if (!RAW && lane < 12 && bv > 0) ((T*)(cand + blk))[lane] = sh.rows[loc >> 6][loc & 63].q[lane];
-      if (stamps && lane == 0) stamp_max(stamps, 5, rt_now());
+  auto publish = [&]() __attribute__((always_inline)) {
+    if (!INLAUNCH) {  // block partial + the block argmax's kept pose (plain stores: the launch boundary
+                      // publishes them); a block without copies has no propagated row, k_resample_final regenerates
+      if (wv == 0) {
+        int bv = sh.c[0], bi = sh.ci[0];
+        for (int w = 1; w < kWaves; ++w) cmb_max(bv, bi, sh.c[w], sh.ci[w]);
+        if (lane == 0) cpart[blk] = CountPart{bv, bi};
+        // one-stream k_resample: the block's candidate also goes into the sharded winner keys (max count, then the
+        // lowest index: count in the high word, 2^31 - 1 - index in the low one), so k_resample_final reads
+        // kWinShards keys instead of every block's partial (C4: 39k partials, three round trips)
+        if (winkey && lane == 0 && bv >= 0)
+          __hip_atomic_fetch_max(winkey + (blk & (kWinShards - 1)) * kWinStride, win_key(bv, bi), __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+        const int loc = bi - blk * kBlock;
+        if (!RAW && lane < 12 && bv > 0) ((T*)(cand + blk))[lane] = sh.rows[loc >> 6][loc & 63].q[lane];
+        if (stamps && lane == 0) stamp_max(stamps, 5, rt_now());
+      }
+      return;
     }
-    return;
-  }
-  if (wv == 1) {  // this block's winner candidate, in parallel with wave 0's arrival
-    int cbv = sh.c[0], cbi = sh.ci[0];
-    for (int w = 1; w < kWaves; ++w) cmb_max(cbv, cbi, sh.c[w], sh.ci[w]);
-    // a candidate with copies was propagated by its lane (staged rows); with no copies anywhere in the
-    // block (only possible when every count of the frame is 0: the winner is particle 0, PE:685) it is
-    // regenerated here
-    const int loc = cbi - blk * kBlock;
-    T Pc[12];
-    if (cbv > 0 && (!RAW || std::is_same<T, SP>::value)) {  // RAW rows are poses unless the state is fp16 deltas
+    if (wv == 1) {  // this block's winner candidate, in parallel with wave 0's arrival
+      int cbv = sh.c[0], cbi = sh.ci[0];
+      for (int w = 1; w < kWaves; ++w) cmb_max(cbv, cbi, sh.c[w], sh.ci[w]);
+      // a candidate with copies was propagated by its lane (staged rows); with no copies anywhere in the
+      // block (only possible when every count of the frame is 0: the winner is particle 0, PE:685) it is
+      // regenerated here
+      const int loc = cbi - blk * kBlock;
+      T Pc[12];
+      if (cbv > 0 && (!RAW || std::is_same<T, SP>::value)) {  // RAW rows are poses unless the state is fp16 deltas
 #pragma unroll
-      for (int q = 0; q < 12; ++q) Pc[q] = sh.rows[loc >> 6][loc & 63].q[q];
-    } else {
-      make_particle<T, RNG, SP>(fa, sc, prior, cbi, kiter, Pc);
+        for (int q = 0; q < 12; ++q) Pc[q] = sh.rows[loc >> 6][loc & 63].q[q];
+      } else {
+        make_particle<T, RNG, SP>(fa, sc, prior, cbi, kiter, Pc);
+      }
+      const uint32_t pl = cand_payload<T, MAXM>(fa, sc, tb, Pc, sh.ccorr);
+      if (lane < kCandGran) st_wt(&cand[blk].g[lane], ((uint64_t)(uint32_t)seq << 32) | pl);
+      if (stamps && lane == 0) stamp_max(stamps, 22, rt_now());
+      return;
     }
-    const uint32_t pl = cand_payload<T, MAXM>(fa, sc, tb, Pc, sh.ccorr);
-    if (lane < kCandGran) st_wt(&cand[blk].g[lane], ((uint64_t)(uint32_t)seq << 32) | pl);
-    if (stamps && lane == 0) stamp_max(stamps, 22, rt_now());
-    return;
-  }
-  if (wv != 0) return;
+    if (wv != 0) return;
 
-  if (MODE == 2) {  // flat: the count partial as two granules {count, index}; block 0 polls every block's and finishes
-    {
-      int bv = sh.c[0], bi = sh.ci[0];
-      for (int w = 1; w < kWaves; ++w) cmb_max(bv, bi, sh.c[w], sh.ci[w]);
-      if (lane < 2) store_granule((uint64_t*)cpart + 2 * blk + lane, fa.gtag, (uint32_t)(lane ? bi : bv));
-      if (stamps && lane == 0) stamp_max(stamps, 5, rt_now());
-    }
-    if (blk != 0) return;
-    // every count partial of the frame (nblk <= kFlatMaxGroups * kGroup = 8 per lane), one 16-B load each, all in
-    // flight together, re-read until every tag is this frame's (bounded: abandoned); then combined, a lane past
-    // nblk holding the identity (count -1)
-    int bv = -1, bi = 0x7fffffff;
-    {
-      u32x4_t cp[kFlatMaxGroups] = {};
-      const uint64_t t0 = rt_now();
-      for (;;) {
+    if (MODE == 2) {  // flat: the count partial as two granules {count, index}; block 0 polls every block's and finishes
+      {
+        int bv = sh.c[0], bi = sh.ci[0];
+        for (int w = 1; w < kWaves; ++w) cmb_max(bv, bi, sh.c[w], sh.ci[w]);
+        if (lane < 2) store_granule((uint64_t*)cpart + 2 * blk + lane, fa.gtag, (uint32_t)(lane ? bi : bv));
+        if (stamps && lane == 0) stamp_max(stamps, 5, rt_now());
+      }
+      if (blk != 0) return;
+      // every count partial of the frame (nblk <= kFlatMaxGroups * kGroup = 8 per lane), one 16-B load each, all in
+      // flight together, re-read until every tag is this frame's (bounded: abandoned); then combined, a lane past
+      // nblk holding the identity (count -1)
+      int bv = -1, bi = 0x7fffffff;
+      {
+        u32x4_t cp[kFlatMaxGroups] = {};
+        const uint64_t t0 = rt_now();
+        for (;;) {
 #pragma unroll
-        for (int j = 0; j < kFlatMaxGroups; ++j) {
-          const int t = lane + 64 * j;
-          cp[j] = ld_gran2_issue((const uint64_t*)cpart + 2 * (t < fa.nblk ? t : 0));
+          for (int j = 0; j < kFlatMaxGroups; ++j) {
+            const int t = lane + 64 * j;
+            cp[j] = ld_gran2_issue((const uint64_t*)cpart + 2 * (t < fa.nblk ? t : 0));
+          }
+          asm volatile("s_waitcnt vmcnt(0)" : "+v"(cp[0]), "+v"(cp[1]), "+v"(cp[2]), "+v"(cp[3]), "+v"(cp[4]), "+v"(cp[5]),
+                       "+v"(cp[6]), "+v"(cp[7])::"memory");
+          static_assert(kFlatMaxGroups == 8, "the wait's operand list");
+          bool stale = false;
+#pragma unroll
+          for (int j = 0; j < kFlatMaxGroups; ++j)
+            stale |= lane + 64 * j < fa.nblk && (cp[j].y != fa.gtag || cp[j].w != fa.gtag);
+          if (!__builtin_amdgcn_ballot_w64(stale)) break;
+          if (rt_now() - t0 > fa.wait_ticks) return;  // abandoned
+          __builtin_amdgcn_s_sleep(1);
         }
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(cp[0]), "+v"(cp[1]), "+v"(cp[2]), "+v"(cp[3]), "+v"(cp[4]), "+v"(cp[5]),
-                     "+v"(cp[6]), "+v"(cp[7])::"memory");
-        static_assert(kFlatMaxGroups == 8, "the wait's operand list");
-        bool stale = false;
 #pragma unroll
         for (int j = 0; j < kFlatMaxGroups; ++j)
-          stale |= lane + 64 * j < fa.nblk && (cp[j].y != fa.gtag || cp[j].w != fa.gtag);
-        if (!__builtin_amdgcn_ballot_w64(stale)) break;
-        if (rt_now() - t0 > fa.wait_ticks) return;  // abandoned
-        __builtin_amdgcn_s_sleep(1);
+          if (lane + 64 * j < fa.nblk) cmb_max(bv, bi, (int)cp[j].x, (int)cp[j].z);
       }
-#pragma unroll
-      for (int j = 0; j < kFlatMaxGroups; ++j)
-        if (lane + 64 * j < fa.nblk) cmb_max(bv, bi, (int)cp[j].x, (int)cp[j].z);
+      wave_argmax(bv, bi);
+      if (stamps && lane == 0) stamps[6] = rt_now();
+      finalize_frame<T, RNG, MAXM, SP>(fa, sc, c, ctrl, prior, bi, cand, mlpose, rec, out, 2 * seq + 1, stamps);
+      if (stamps && lane == 0) stamps[7] = rt_now();
+      return;
     }
-    wave_argmax(bv, bi);
+    int last = 0;
+    if (lane == 0) {
+      int bv = sh.c[0], bi = sh.ci[0];
+      for (int w = 1; w < kWaves; ++w) cmb_max(bv, bi, sh.c[w], sh.ci[w]);
+      st_wt(cpart + blk, pack2(bv, bi));
+      if (stamps) stamp_max(stamps, 5, rt_now());
+      last = arrive_last(gcount + g, min(fa.gsz, fa.nblk - g * fa.gsz)) ? 1 : 0;
+    }
+    if (!lane_value(last, 0)) return;
+    // group: max count over its blocks (first index on ties)
+    int bv = -1, bi = 0x7fffffff;
+    {
+      const int b0 = g * fa.gsz, nb = min(fa.gsz, fa.nblk - b0);
+      for (int t = lane; t < nb; t += 64) {
+        const uint64_t cp = ld_wt(cpart + b0 + t);
+        cmb_max(bv, bi, lo32(cp), hi32(cp));
+      }
+      wave_argmax(bv, bi);
+    }
+    if (fa.ngrp > 1) {
+      if (lane == 0) st_wt(cgroup + g, pack2(bv, bi));
+      if (!wave_arrive_last(tcount, fa.ngrp)) return;
+      bv = -1;
+      bi = 0x7fffffff;
+      for (int gg = lane; gg < fa.ngrp; gg += 64) {
+        const uint64_t cp = ld_wt(cgroup + gg);
+        cmb_max(bv, bi, lo32(cp), hi32(cp));
+      }
+      wave_argmax(bv, bi);
+    }
     if (stamps && lane == 0) stamps[6] = rt_now();
+    // winner = argmax resample count, first index (PE:685-686)
     finalize_frame<T, RNG, MAXM, SP>(fa, sc, c, ctrl, prior, bi, cand, mlpose, rec, out, 2 * seq + 1, stamps);
     if (stamps && lane == 0) stamps[7] = rt_now();
-    return;
-  }
-  int last = 0;
-  if (lane == 0) {
-    int bv = sh.c[0], bi = sh.ci[0];
-    for (int w = 1; w < kWaves; ++w) cmb_max(bv, bi, sh.c[w], sh.ci[w]);
-    st_wt(cpart + blk, pack2(bv, bi));
-    if (stamps) stamp_max(stamps, 5, rt_now());
-    last = arrive_last(gcount + g, min(fa.gsz, fa.nblk - g * fa.gsz)) ? 1 : 0;
-  }
-  if (!lane_value(last, 0)) return;
-  // group: max count over its blocks (first index on ties)
-  int bv = -1, bi = 0x7fffffff;
-  {
-    const int b0 = g * fa.gsz, nb = min(fa.gsz, fa.nblk - b0);
-    for (int t = lane; t < nb; t += 64) {
-      const uint64_t cp = ld_wt(cpart + b0 + t);
-      cmb_max(bv, bi, lo32(cp), hi32(cp));
-    }
-    wave_argmax(bv, bi);
-  }
-  if (fa.ngrp > 1) {
-    if (lane == 0) st_wt(cgroup + g, pack2(bv, bi));
-    if (!wave_arrive_last(tcount, fa.ngrp)) return;
-    bv = -1;
-    bi = 0x7fffffff;
-    for (int gg = lane; gg < fa.ngrp; gg += 64) {
-      const uint64_t cp = ld_wt(cgroup + gg);
-      cmb_max(bv, bi, lo32(cp), hi32(cp));
-    }
-    wave_argmax(bv, bi);
-  }
-  if (stamps && lane == 0) stamps[6] = rt_now();
-  // winner = argmax resample count, first index (PE:685-686)
-  finalize_frame<T, RNG, MAXM, SP>(fa, sc, c, ctrl, prior, bi, cand, mlpose, rec, out, 2 * seq + 1, stamps);
-  if (stamps && lane == 0) stamps[7] = rt_now();
+  };
+  publish();
+  if (EARLY) scatter_end();  // (also after an abandoned poll: the new prior is complete either way)
 }
 
 // ---- launch 2 of the two-launch path: stratified resampling + winner + frame record.  One block's work
@@ -4544,6 +4591,7 @@ struct Frame2Lds {
   int dirty[kWaves];                // group_math2: a wave's blocks may hold a negative or NaN weight
   GroupScan gs;                     // this block's group prefix / running max (kept slot)
   Ctrl c;
+  Frame2Tail tail;                  // the top's running max, then K_total (the count phase)
   int abort;
 };
 
@@ -4679,7 +4727,8 @@ __device__ __forceinline__ double lanes8_incl_sum(double x) {
 // slot).  Returns the new control record (wave-uniform) and the lane's group G / Gin when done.
 template <typename T, int RNG, typename KeptF, typename ArgF>
 __device__ __forceinline__ Ctrl top_math_regs(const FrameArgsT<T>& fa, Ctrl c, int iter, int slot, const GroupPart& q0,
-                                              KeptF qk, ArgF garg, double* G_out, double* Gin_out) {
+                                              KeptF qk, ArgF garg, double* G_out, double* Gin_out,
+                                              double* run_out) {
   const int lane = lane_id();
   const int ngrp = fa.ngrp;
   // the kept-slot sum chain, speculatively for kept slot == this slot (the kept iteration is an earlier
@@ -4732,9 +4781,16 @@ __device__ __forceinline__ Ctrl top_math_regs(const FrameArgsT<T>& fa, Ctrl c, i
     c.accepted = (S != 0.0 && highest > fa.accept_thr) ? 1 : 0;  // PE:633
     if (c.accepted) {
       c.most_likely_idx = c.best_idx;
+#if PFMPE_TAIL_KT_IN_COUNTS
+      // K_total = F(run) is left to the count phase (resample_phase, MODE 2: lane 1 of wave 0's F(rin) call), so
+      // the other waves' wait for the top does not include one lane's Philox evaluation
+      *run_out = run;
+      c.K_total = 0;
+#else
       int64_t kt = lane == 0 ? count_targets<T, RNG>(fa, c.iters, run) : 0;
       c.K_total = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)kt, 0)) |
                             ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)kt >> 32), 0) << 32));
+#endif
     } else {
       c.most_likely_idx = (S < 0.0) ? ani : ami;
       c.K_total = 0;
@@ -4936,8 +4992,9 @@ __device__ __forceinline__ bool frame2_body(
           cmb_min(mnv, mni, fl.wa[ks][w].minw, fl.wa[ks][w].argmin);
         }
       };
-      double G = 0.0, Gin = -INFINITY;
-      const Ctrl cn = top_math_regs<T, RNG>(fa, c, iter, slot, q0, qk, garg, &G, &Gin);
+      double G = 0.0, Gin = -INFINITY, run = -INFINITY;
+      const Ctrl cn = top_math_regs<T, RNG>(fa, c, iter, slot, q0, qk, garg, &G, &Gin, &run);
+      if (lane == 0) fl.tail.run = run;
       if (lane == g_own) {
         fl.gs.G = G;
         fl.gs.Gin = Gin;
@@ -4964,7 +5021,7 @@ __device__ __forceinline__ bool frame2_body(
   const GroupScan gs = fl.gs;
   resample_phase<T, RNG, MAXM, SP, 2>(fa, sc, c, ctrl, table, prior, post, wd, A, P, have_P, bs, gs, rsh, rec,
                                                  tb, cand, mlpose, cpart, nullptr, nullptr, nullptr, counts, out, seq,
-                                                 stamps, flat, blk);
+                                                 stamps, flat, blk, nullptr, nullptr, &fl.tail);
   return true;
 }
 
