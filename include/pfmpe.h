@@ -303,6 +303,51 @@ int pfmpe_get_weights(pfmpe_ctx* ctx, double* out);
 /* counterMeas of the last step (PE:524, 678): N uint32; requires PFMPE_OPT_RECORD_COUNTS. */
 int pfmpe_get_counts(pfmpe_ctx* ctx, uint32_t* out);
 
+/* ------------------------------------------------------------- statistics of the particle cloud */
+/* Posterior mean, 6x6 covariance and effective sample size of a particle set, reduced on the device (the
+ * particles stay in HBM; 60 doubles come back).  The covariance is in the coordinates of the reference's
+ * pose_covariance_ (A.inverse() of the Gauss-Newton step, PE:2004, getPoseCovariance): twists [upsilon; omega]
+ * (translation part first, exponentialMap / logarithmMap PE:2194-2296) of a left perturbation of a reference
+ * pose, T = exp(xi) * T_ref, as in T_new = exponentialMap(dT) * predicted_pose_ (PE:1876).
+ *
+ * Definition.  For particle pose T_i = [R_i | t_i] and the caller's T_ref = [R_r | t_r]:
+ *   D = T_i * T_ref^-1 with T_ref^-1 = [R_r^T | -R_r^T t_r]:  D_R = R_i R_r^T,  d = t_i - D_R t_r
+ *   a = 1/2 (D_R[2,1] - D_R[1,2], D_R[0,2] - D_R[2,0], D_R[1,0] - D_R[0,1]),  s = |a|,  c = 1/2 (tr D_R - 1)
+ *   phi = atan2(s, c);  omega = f a,  f = phi / s when s > 1e-8, else 1 + s^2 / 6
+ *   upsilon = (I - 1/2 omega^ + k omega^ omega^) d,
+ *     k = (1 - phi sin phi / (2 (1 - cos phi))) / phi^2 when phi >= 1e-4, else 1/12 + phi^2 / 720
+ *     (1 - cos phi is evaluated as 2 sin^2(phi / 2))
+ *   xi_i = [upsilon; omega];  a pose bit-equal to T_ref has xi_i = 0 exactly.
+ * The formula is applied to the stored matrices as they are: fp32 / fp16 state is only approximately
+ * orthonormal and is not re-orthonormalised.  Clouds near phi = pi are out of scope (omega is ill-defined there).
+ * With weights w_i >= 0:
+ *   W = sum w,  mu = sum w xi / W,  C = sum w xi xi^T / W - mu mu^T (symmetric, row-major, both triangles),
+ *   ESS = W^2 / sum w^2,  mean_pose = exp(mu) * T_ref (exp as PE:2194-2226),
+ *   max_trans = max |upsilon_i|, max_rot = max |omega_i| over particles with w_i > 0 (the cloud's extent).
+ * mean_pose is ONE step toward the intrinsic mean: a caller who wants to iterate calls again with mean_pose
+ * as the reference.  All arithmetic is fp64 for every state type; the sums have a fixed order that depends on
+ * N alone, so a repeated call returns the same bits.
+ *
+ * Blocking; runs on the context's stream (after the last frame, before the next).  Changes nothing the next
+ * frame reads.  Not timed by PFMPE_OPT_TIMING (there is no kernel-statistics slot for it; regenerating the
+ * WEIGHTED set counts as aux, as for the particle read-back).
+ * Errors: PFMPE_E_ARG for a bad `which`, a NULL pointer or a non-finite reference pose; PFMPE_E_STATE with no
+ * particle set, and for WEIGHTED before the first step. */
+enum { PFMPE_CLOUD_WEIGHTED = 0,   /* kept propagated set of the last step with probPart as weights
+                                      (the rows of pfmpe_get_particles(0) and pfmpe_get_weights)            */
+       PFMPE_CLOUD_POSTERIOR = 1 };/* current prior = resampled set, unit weights (pfmpe_get_particles(1)) */
+typedef struct {
+  int64_t n;               /* particles reduced                                  */
+  int32_t degenerate;      /* 1: W == 0 (all weights zero); means / cov are 0 and mean_pose = ref */
+  int32_t pad;
+  double wsum, ess;        /* W, ESS (0 when degenerate)                         */
+  double mean_twist[6];    /* mu                                                 */
+  double cov[36];          /* C                                                  */
+  double mean_pose[12];
+  double max_trans, max_rot;
+} pfmpe_cloud_out;
+int pfmpe_cloud_stats(pfmpe_ctx* ctx, int which, const double* ref_pose12, pfmpe_cloud_out* out);
+
 /* Engine options (value semantics in brackets; defaults first):
  *   PFMPE_OPT_RECORD_COUNTS [0|1]  keep counterMeas on device for pfmpe_get_counts
  *   PFMPE_OPT_PRUNE         [1|0]  exact x-window blob pruning in the likelihood (0 = scan all B blobs)
@@ -390,6 +435,8 @@ const char* pfmpe_kernel_name(int kernel);
 /* j-th (0-based) uniform_real_distribution<double>(a,b) draw of a default_random_engine(seed) */
 double pfmpe_host_ref_uniform(uint32_t seed, uint64_t j, double a, double b);
 void pfmpe_host_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* twist6 = xi of pose12 about ref_pose12 (the definition at the cloud statistics above), as the kernel forms it */
+void pfmpe_host_pose_twist(const double* pose12, const double* ref_pose12, double* twist6);
 
 #ifdef __cplusplus
 }

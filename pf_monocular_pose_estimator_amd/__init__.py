@@ -13,6 +13,7 @@ from ._capi import (  # noqa: F401
     DIAG_SERIAL_TOP, DIAG_NO_PK, DIAG_CORRUPT_DESC, DIAG_NO_DEFER, DIAG_BLOCK_RESAMPLE, DIAG_MIN_SIDE, DIAG_ABANDON_FINISH, OPT_DEFER_RESAMPLE, OK, E_ARG, E_HIP, E_CAP, E_STATE,
     SHAPE_TWO_LAUNCH, SHAPE_FRAME, SHAPE_FRAME2, INFO_FUSED, INFO_FUSED_FALLBACKS, INFO_LAST_SHAPE,
     INFO_GUARD_SKIPS, INFO_N, INFO_LAST_WEIGH_PASS, INFO_LAST_GRID, INFO_LAST_RESAMPLE, RESAMPLE_BLOCKS, RESAMPLE_OWNERS, WEIGH_BLOCKS, WEIGH_STREAM, WEIGH_PK,
+    CLOUD_WEIGHTED, CLOUD_POSTERIOR, CloudOut, host_pose_twist,
 )
 
 __all__ = [

@@ -32,6 +32,7 @@ INFO_FUSED, INFO_FUSED_FALLBACKS, INFO_LAST_SHAPE, INFO_GUARD_SKIPS, INFO_N, INF
 INFO_LAST_GRID, INFO_LAST_RESAMPLE = 7, 8
 WEIGH_BLOCKS, WEIGH_STREAM, WEIGH_PK = 0, 1, 2
 RESAMPLE_BLOCKS, RESAMPLE_OWNERS = 0, 1
+CLOUD_WEIGHTED, CLOUD_POSTERIOR = 0, 1
 K_PROPAGATE, K_RESAMPLE, K_AUX, K_FRAME, K_ROI, K_FINAL, K_P3P_HIST, K_P3P_CHECK, K_DETECT, K_COUNT = range(10)
 
 # every symbol include/pfmpe.h declares (tests check the .so exports all of them)
@@ -45,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "pfmpe_parse_marker_yaml", "pfmpe_default_launch_config", "pfmpe_parse_launch", "pfmpe_parse_camera_info",
     "pfmpe_write_blob_stream", "pfmpe_read_blob_stream", "pfmpe_stage_blob_stream",
     "pfmpe_default_detect_params", "pfmpe_stage_image", "pfmpe_find_leds", "pfmpe_get_info",
+    "pfmpe_cloud_stats", "pfmpe_host_pose_twist",
 )
 
 
@@ -141,6 +143,18 @@ class FrameOut(C.Structure):
         }
 
 
+class CloudOut(C.Structure):
+    _fields_ = [("n", C.c_int64), ("degenerate", C.c_int32), ("pad", C.c_int32),
+                ("wsum", C.c_double), ("ess", C.c_double), ("mean_twist", C.c_double * 6),
+                ("cov", C.c_double * 36), ("mean_pose", C.c_double * 12),
+                ("max_trans", C.c_double), ("max_rot", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"n": self.n, "degenerate": self.degenerate, "wsum": self.wsum, "ess": self.ess,
+                "mean_twist": np.array(self.mean_twist), "cov": np.array(self.cov).reshape(6, 6),
+                "mean_pose": np.array(self.mean_pose), "max_trans": self.max_trans, "max_rot": self.max_rot}
+
+
 _lib = None
 
 
@@ -180,6 +194,8 @@ def load() -> C.CDLL:
         "pfmpe_kernel_name": (C.c_char_p, [I]),
         "pfmpe_host_ref_uniform": (D, [C.c_uint32, U64, D, D]),
         "pfmpe_host_philox": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "pfmpe_host_pose_twist": (None, [dp, dp, dp]),
+        "pfmpe_cloud_stats": (I, [P, I, dp, C.POINTER(CloudOut)]),
         "pfmpe_predict_roi": (I, [P, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
         "pfmpe_default_init_params": (None, [C.POINTER(InitParams)]),
         "pfmpe_p3p_histogram": (I, [P, dp, I, C.POINTER(C.c_uint32)]),
@@ -235,6 +251,7 @@ class Engine:
         self.max_particles = max_particles
         self.N = 0
         self.M = 0
+        self._last_out = None  # the last step's FrameOut (cloud_stats' default reference)
 
     def close(self):
         if self.ctx:
@@ -279,6 +296,7 @@ class Engine:
         p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
         self._chk(self.lib.pfmpe_set_prior(self.ctx, _dptr(p), p.shape[0]))
         self.N = p.shape[0]
+        self._last_out = None
 
     def stage_blob_bank(self, frames):
         offs = np.zeros(len(frames) + 1, dtype=np.int32)
@@ -319,6 +337,7 @@ class Engine:
     def step(self, frame: FrameIn) -> FrameOut:
         out = FrameOut()
         self._chk(self.lib.pfmpe_step(self.ctx, C.byref(frame), C.byref(out)))
+        self._last_out = out
         return out
 
     def step_batch(self, frames) -> list:
@@ -339,6 +358,7 @@ class Engine:
         n, arr_in, arr_out = prepared
         done = C.c_int()
         self._chk(self.lib.pfmpe_step_batch(self.ctx, arr_in, n, arr_out, C.byref(done)))
+        self._last_out = arr_out[n - 1] if n else self._last_out
         return arr_out
 
     @staticmethod
@@ -352,7 +372,10 @@ class Engine:
         arr_in = (FrameIn * S)(*frames)
         arr_out = (FrameOut * S)()
         engines[0]._chk(engines[0].lib.pfmpe_step_multi(ctxs, S, arr_in, arr_out))
-        return list(arr_out)
+        outs = list(arr_out)
+        for e, o in zip(engines, outs):
+            e._last_out = o
+        return outs
 
     def predict_roi(self, prediction, predicted_pose, D, image_w, image_h, border, cam_move_inv=None) -> dict:
         """Region of interest for the next detection (PE:396-412): {"roi": [x, y, w, h], "bbox": [...]}."""
@@ -392,6 +415,7 @@ class Engine:
         d = out.as_dict()
         if d["found"]:
             self.N = int(n_particles) if n_particles else (self.N or self.max_particles)
+            self._last_out = None
         return d, h
 
     def stage_image(self, image: np.ndarray):
@@ -446,6 +470,23 @@ class Engine:
         out = np.empty(self.N, dtype=np.uint32)
         self._chk(self.lib.pfmpe_get_counts(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
+
+    def cloud_stats(self, which: int = CLOUD_POSTERIOR, ref=None) -> dict:
+        """Mean twist, 6x6 covariance ([upsilon; omega], left perturbation of `ref`), ESS, mean pose and extent of
+        the particle cloud, reduced on the device (pfmpe_cloud_stats).  which: CLOUD_POSTERIOR (the current prior,
+        unit weights) or CLOUD_WEIGHTED (the last step's kept propagated set with its raw weights).  ref None: the
+        last step's winner_pose when it resampled, else its most_likely_pose; before any step a ref is required."""
+        if ref is None:
+            lo = self._last_out
+            if lo is None:
+                raise ValueError("cloud_stats: no step yet on this particle set, pass ref")
+            ref = lo.winner_pose if lo.resampled else lo.most_likely_pose
+        r = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).reshape(-1)[:12])
+        if r.size != 12:
+            raise ValueError("cloud_stats: ref must hold 12 values (3x4) or a 4x4")
+        out = CloudOut()
+        self._chk(self.lib.pfmpe_cloud_stats(self.ctx, int(which), _dptr(r), C.byref(out)))
+        return out.as_dict()
 
     def kernel_stats(self) -> dict:
         res = {}
@@ -531,6 +572,15 @@ def read_blob_stream(path):
 
 def host_ref_uniform(seed: int, j: int, a: float, b: float) -> float:
     return load().pfmpe_host_ref_uniform(seed, j, a, b)
+
+
+def host_pose_twist(pose, ref) -> np.ndarray:
+    """Twist [upsilon; omega] of pose * ref^-1 (poses: 12 values, or 4x4), by the code the cloud kernel runs."""
+    p = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(-1)[:12])
+    r = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).reshape(-1)[:12])
+    out = np.zeros(6)
+    load().pfmpe_host_pose_twist(_dptr(p), _dptr(r), _dptr(out))
+    return out
 
 
 def host_philox(ctr, key):

@@ -91,6 +91,7 @@ struct pfmpe_ctx {
   Cand* d_cand = nullptr;          // per-block winner candidates
   double* d_mlpose = nullptr;      // most likely pose (12)
   double* d_roi = nullptr;         // ROI box [4] + per-block partials
+  double* d_cloud = nullptr;       // cloud statistics: result row + per-block partial rows (pfmpe_cloud_stats)
   unsigned char* d_init = nullptr; // initialisation scratch (pfmpe_init.hip), grown on demand
   size_t init_cap = 0;
   unsigned char* d_det = nullptr;  // detector scratch (pfmpe_detect.hip), grown on demand

@@ -89,7 +89,7 @@ size_t build_table(const pfmpe_ctx* c, const double* blobs, int B, unsigned char
 void free_all(pfmpe_ctx* c) {
   void* dev[] = {c->d_state[0], c->d_state[1], c->d_w[0], c->d_w[1], c->d_prop[0], c->d_prop[1], c->d_part[0], c->d_part[1],
                  c->d_bscan[0], c->d_bscan[1], c->d_gpart[0], c->d_gpart[1], c->d_gscan, c->d_cpart, c->d_winkey,
-                 c->d_cgroup, c->d_counters, c->d_ctrl, c->d_gen, c->d_cand, c->d_mlpose, c->d_flat, c->d_roi, c->d_gran, c->d_init, c->d_det, c->d_img, c->d_table, c->d_bank, c->d_xfer, c->d_counts,
+                 c->d_cgroup, c->d_counters, c->d_ctrl, c->d_gen, c->d_cand, c->d_mlpose, c->d_flat, c->d_roi, c->d_cloud, c->d_gran, c->d_init, c->d_det, c->d_img, c->d_table, c->d_bank, c->d_xfer, c->d_counts,
                  c->d_stamps, c->d_owner[0], c->d_owner[1]};
   for (void* p : dev)
     if (p) (void)hipFree(p);
@@ -738,6 +738,117 @@ int pfmpe_get_counts(pfmpe_ctx* c, uint32_t* out) {
   return PFMPE_OK;
 }
 
+namespace {
+// exponentialMap (PE:2194-2226): twist [upsilon; omega] -> pose
+void host_exp_map(const double* xi, double* pose) {
+  const double* u = xi;
+  const double* w = xi + 3;
+  const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), th2 = th * th;
+  const double O[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+  double O2[9], R[9], V[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) O2[i * 3 + j] = O[i * 3] * O[j] + O[i * 3 + 1] * O[3 + j] + O[i * 3 + 2] * O[6 + j];
+  for (int i = 0; i < 9; ++i) {
+    const double I = (i % 4 == 0) ? 1.0 : 0.0;
+    R[i] = I;
+    V[i] = I;
+    if (th != 0) {
+      const double s = std::sin(th), c = std::cos(th);
+      R[i] = I + O[i] / th * s + O2[i] / th2 * (1 - c);
+      V[i] = I + (1 - c) / th2 * O[i] + (th - s) / (th2 * th) * O2[i];
+    }
+  }
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) pose[i * 4 + j] = R[i * 3 + j];
+    pose[i * 4 + 3] = V[i * 3] * u[0] + V[i * 3 + 1] * u[1] + V[i * 3 + 2] * u[2];
+  }
+}
+}  // namespace
+
+int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_out* out) {
+  if (!c) return PFMPE_E_ARG;
+  if (!ref || !out || (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR))
+    return fail(c, PFMPE_E_ARG, "cloud_stats: bad arguments");
+  for (int q = 0; q < 12; ++q)
+    if (!std::isfinite(ref[q])) return fail(c, PFMPE_E_ARG, "cloud_stats: non-finite reference pose");
+  if (!c->has_prior) return fail(c, PFMPE_E_STATE, "cloud_stats: no particle set");
+  if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_stats(weighted): no step yet");
+  RET(set_device(c));
+  // scratch of the call's own (nothing a frame reads): the result row, then one partial row per block
+  if (!c->d_cloud)
+    HIPCHK(c, hipMalloc((void**)&c->d_cloud, ((size_t)kCloudMaxBlocks + 1) * kCloudWords * sizeof(double)));
+  const int N = c->N;
+  const int nblk = cloud_blocks(N);
+  CloudArgs ca{};
+  std::memcpy(ca.ref, ref, sizeof(ca.ref));
+  ca.N = N;
+  double* part = c->d_cloud + kCloudWords;
+  if (which == PFMPE_CLOUD_WEIGHTED) {
+    // the kept propagated set as get_particles(0) delivers it (d_xfer is written and read inside one blocking call
+    // by every user), weighted by the kept iteration's raw weights
+    RET(ensure_xfer(c));
+    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx], c->d_xfer));
+    ca.dense = c->d_xfer;
+    ca.w = c->d_w[c->last_kept_slot];
+    if (c->state_dtype == PFMPE_STATE_F64)
+      hipLaunchKernelGGL((k_cloud_partials<double, double, true>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
+                         (const double*)nullptr, part);
+    else
+      hipLaunchKernelGGL((k_cloud_partials<float, float, true>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
+                         (const float*)nullptr, part);
+  } else {
+    std::memcpy(ca.anchor, c->anchor[c->prior_idx], sizeof(ca.anchor));
+    ca.ld = c->ld;
+    ca.owner = prior_owner_ptr(c);
+    const void* st = c->d_state[c->prior_idx];
+    if (c->state_dtype == PFMPE_STATE_F64)
+      hipLaunchKernelGGL((k_cloud_partials<double, double, false>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
+                         (const double*)st, part);
+    else if (c->state_dtype == PFMPE_STATE_F16)
+      hipLaunchKernelGGL((k_cloud_partials<float, __half, false>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
+                         (const __half*)st, part);
+    else
+      hipLaunchKernelGGL((k_cloud_partials<float, float, false>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
+                         (const float*)st, part);
+  }
+  hipLaunchKernelGGL((k_cloud_final<double>), dim3(1), dim3(kCloudSegs * kCloudWords), 0, c->stream, part, nblk, c->d_cloud);
+  HIPCHK(c, hipGetLastError());
+  double r[kCloudWords];
+  HIPCHK(c, hipMemcpyAsync(r, c->d_cloud, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  RET(harvest_timing(c));  // (a weighted call's regeneration is bracketed like get_particles(0)'s)
+
+  std::memset(out, 0, sizeof(*out));
+  out->n = N;
+  out->wsum = r[0];
+  if (!(r[0] > 0.0)) {  // all weights zero (the re-initialisation branch): no mean to speak of
+    out->degenerate = 1;
+    std::memcpy(out->mean_pose, ref, sizeof(out->mean_pose));
+    return PFMPE_OK;
+  }
+  const double W = r[0];
+  out->ess = W * W / r[1];
+  for (int q = 0; q < 6; ++q) out->mean_twist[q] = r[2 + q] / W;
+  int k = 8;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j, ++k) {
+      const double v = r[k] / W - out->mean_twist[i] * out->mean_twist[j];
+      out->cov[i * 6 + j] = v;
+      out->cov[j * 6 + i] = v;
+    }
+  out->max_trans = std::sqrt(r[kCloudSums]);
+  out->max_rot = std::sqrt(r[kCloudSums + 1]);
+  // mean_pose = exp(mu) * ref: one step toward the intrinsic mean
+  double E[12];
+  host_exp_map(out->mean_twist, E);
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j)
+      out->mean_pose[i * 4 + j] = E[i * 4] * ref[j] + E[i * 4 + 1] * ref[4 + j] + E[i * 4 + 2] * ref[8 + j];
+    out->mean_pose[i * 4 + 3] = E[i * 4] * ref[3] + E[i * 4 + 1] * ref[7] + E[i * 4 + 2] * ref[11] + E[i * 4 + 3];
+  }
+  return PFMPE_OK;
+}
+
 // Undocumented diagnostic: reset (out == NULL) or read the kStamps stamps of the last frame (diag & 4).
 int pfmpe_debug_stamps(pfmpe_ctx* c, uint64_t* out) {
   if (!c || !c->d_stamps) return PFMPE_E_STATE;
@@ -828,6 +939,11 @@ void pfmpe_host_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t ou
   out[1] = o.y;
   out[2] = o.z;
   out[3] = o.w;
+}
+
+// the twist the cloud-statistics kernel forms for one particle
+void pfmpe_host_pose_twist(const double* pose12, const double* ref_pose12, double* twist6) {
+  pose_twist(pose12, ref_pose12, twist6);
 }
 
 }  // extern "C"

@@ -1,0 +1,106 @@
+"""The twist of the cloud statistics (pfmpe_host_pose_twist: the code k_cloud_partials runs per particle) on the CPU:
+against the oracle's logarithmMap / exponentialMap, at the branch switches, and the binding's layout."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import pf_monocular_pose_estimator_amd as pf
+from pf_monocular_pose_estimator_amd import _capi
+from oracle import pforacle as orc
+
+import cloud_ref
+
+
+def _rand_rot(rng):
+    q = rng.normal(size=4)
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def _rand_ref(rng):
+    T = np.eye(4)
+    T[:3, :3] = _rand_rot(rng)
+    T[:3, 3] = rng.uniform(-1, 1, 3) + [0, 0, 2]
+    return T
+
+
+def _inv(T):
+    Ti = np.eye(4)
+    Ti[:3, :3] = T[:3, :3].T
+    Ti[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return Ti
+
+
+def _pose_about(rng, Tref, wnorm):
+    """T = exp(xi) * T_ref with |omega| = wnorm and a translation part of up to 1 m."""
+    w = rng.normal(size=3)
+    xi = np.concatenate([rng.uniform(-1, 1, 3) / np.sqrt(3), w / np.linalg.norm(w) * wnorm])
+    D = np.vstack([np.asarray(orc.exp_map(xi)).reshape(3, 4), [0, 0, 0, 1]])
+    return D @ Tref
+
+
+def test_twist_agrees_with_the_oracle_log_and_exp():
+    rng = np.random.default_rng(5)
+    worst_log = worst_exp = 0.0
+    for _ in range(600):
+        Tref = _rand_ref(rng)
+        T = _pose_about(rng, Tref, rng.uniform(0.005, 1.0))
+        xi = pf.host_pose_twist(T, Tref)
+        D = (T @ _inv(Tref))[:3].reshape(12)
+        want = np.asarray(orc.log_map(D))
+        worst_log = max(worst_log, np.max(np.abs(xi - want)) / np.max(np.abs(want)))
+        back = np.asarray(orc.exp_map(xi)).reshape(12)
+        worst_exp = max(worst_exp, np.max(np.abs(back - D)) / np.max(np.abs(D)))
+    print(f"worst relative difference: log {worst_log:.3e}, exp round trip {worst_exp:.3e}")
+    assert worst_log <= 1e-9
+    assert worst_exp <= 1e-9
+
+
+def test_equal_poses_give_exact_zeros():
+    rng = np.random.default_rng(6)
+    for _ in range(50):
+        T = _rand_ref(rng)
+        assert np.array_equal(pf.host_pose_twist(T, T), np.zeros(6))
+        T32 = T[:3].astype(np.float32).astype(np.float64)  # not orthonormal to double precision
+        assert np.array_equal(pf.host_pose_twist(T32, T32), np.zeros(6))
+
+
+@pytest.mark.parametrize("wnorm", [1e-10, 0.999e-8, 1.001e-8, 0.999e-4, 1.001e-4])
+def test_branches_agree_at_the_switches(wnorm):
+    """Either side of the s switch (1e-8) and of the phi switch (1e-4), and far below both: the branch taken and the
+    other branch's formula (the numpy restatement with the thresholds moved) agree to 1e-12 absolute."""
+    rng = np.random.default_rng(7)
+    for _ in range(20):
+        Tref = _rand_ref(rng)
+        T = _pose_about(rng, Tref, wnorm)
+        got = pf.host_pose_twist(T, Tref)
+        for s_sw in (0.0, 1.0):          # always phi / s, always the series
+            for phi_sw in (0.0, 10.0):   # always the closed form of k, always the series
+                other = cloud_ref.twists(T[:3].reshape(1, 12), Tref[:3].reshape(12), s_sw, phi_sw)[0]
+                assert np.max(np.abs(got - other)) <= 1e-12, (wnorm, s_sw, phi_sw, got, other)
+
+
+def test_numpy_restatement_matches_the_host_code():
+    """tests/cloud_ref.py is the reference of the GPU tests: same operations in the same order, so it differs from
+    the engine's code by libm rounding alone (a few ulp of sin / atan2), also where t_i - D_R t_r cancels (poses
+    rounded to fp32 / fp16 steps next to the reference)."""
+    rng = np.random.default_rng(8)
+    Tref = _rand_ref(rng)
+    P = np.stack([_pose_about(rng, Tref, w)[:3].reshape(12) for w in rng.uniform(0, 0.05, 300)])
+    P[100:200] = P[100:200].astype(np.float32)
+    P[200:] = Tref[:3].reshape(12) + (P[200:] - Tref[:3].reshape(12)).astype(np.float16)
+    P[200:205] = Tref[:3].reshape(12).astype(np.float32)
+    got = np.stack([pf.host_pose_twist(p, Tref) for p in P])
+    want = cloud_ref.twists(P, Tref[:3].reshape(12))
+    assert np.max(np.abs(got - want) / np.max(np.abs(want), axis=1, keepdims=True)) <= 1e-13
+
+
+def test_binding_and_layout():
+    assert ctypes.sizeof(_capi.CloudOut) == 8 * 60
+    assert (pf.CLOUD_WEIGHTED, pf.CLOUD_POSTERIOR) == (0, 1)
+    assert "pfmpe_cloud_stats" in _capi.EXPORTED_SYMBOLS and "pfmpe_host_pose_twist" in _capi.EXPORTED_SYMBOLS
+    lib = pf.load()
+    assert hasattr(lib, "pfmpe_cloud_stats") and hasattr(lib, "pfmpe_host_pose_twist")
