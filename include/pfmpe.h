@@ -348,6 +348,57 @@ typedef struct {
 } pfmpe_cloud_out;
 int pfmpe_cloud_stats(pfmpe_ctx* ctx, int which, const double* ref_pose12, pfmpe_cloud_out* out);
 
+/* ------------------------------------------------------------- LED-blob association of the particle cloud */
+/* The reference keeps the correspondences of every particle (correspondencesVec, PE:2385-2445, read at PE:688); a
+ * step reports the winner's only (pfmpe_frame_out.corr).  These calls derive every particle's pairs on the device
+ * and return them as rows, or counted: which blob each LED matched, over the whole set.
+ *
+ * Sets.  `which` as for pfmpe_get_particles: PFMPE_ASSOC_PROPAGATED the kept propagated set of the last step
+ * (the set correspondencesVec belongs to), PFMPE_ASSOC_POSTERIOR the current prior (the resampled set).  Every
+ * particle casts one vote per LED; weights are not used (the posterior carries them as multiplicities), so every
+ * number is an integer and a repeated call returns the same bits.
+ *
+ * Definition.  The pairs of particle i are those the step's likelihood lists for pose i in the context's compute
+ * type (fp64 for F64 state, fp32 for F32 / F16 state), with the poses pfmpe_get_particles(which) returns, the blobs
+ * given here and the context's current tol, tol_PF, model, K and pruning option: LED j's nearest blob (lowest blob
+ * index on a tie); extraction in ascending (distance, LED) order; the reference's break at the first distance above
+ * tol_PF and at most min(B, M) pairs; LEDs used once, blobs free to repeat; 1-based (LED, blob) rows padded with
+ * zeros to PFMPE_MAX_MARKERS rows as in pfmpe_frame_out.corr; no pairs for a particle whose likelihood
+ * short-circuits (B = 0, a NaN distance at LED 1 / blob 1).
+ * votes[m * (B + 1) + b], b >= 1, counts the particles that paired LED m + 1 with blob b; column 0 counts those that
+ * left LED m + 1 unpaired, so every row sums to n.
+ *
+ * Blobs are the caller's (the context keeps no frame's list): a host list, or a frame of the staged blob bank.
+ * Both device calls are blocking, run on the context's stream, change nothing a later frame reads and are not timed
+ * by PFMPE_OPT_TIMING (regenerating the propagated set counts as aux, as for the particle read-back).
+ * Errors: PFMPE_E_ARG for a bad `which`, a NULL in / out, NULL blobs with B > 0 and no bank frame, B < 0, a bank
+ * frame out of range, first < 0, count < 0 or first + count > N, NULL corr / n_corr with count > 0; PFMPE_E_CAP for
+ * B > max_blobs; PFMPE_E_STATE without a model or a particle set, and for PROPAGATED before the first step. */
+enum { PFMPE_ASSOC_PROPAGATED = 0, PFMPE_ASSOC_POSTERIOR = 1 };
+typedef struct {
+  const double* blobs;  /* B x 2 undistorted px, host pointer (ignored if bank_frame >= 0)          */
+  int32_t B;            /* (a bank frame brings its own count, returned in out->B; B < 0 is refused) */
+  int32_t bank_frame;   /* -1: use `blobs`; >= 0: that frame of the staged blob bank               */
+} pfmpe_assoc_in;
+typedef struct {
+  int64_t n;                                   /* particles examined (= every LED row's vote total)  */
+  int32_t M, B;                                /* shape of the votes table                           */
+  int64_t n_any;                               /* particles with at least one pair                   */
+  uint32_t matched[PFMPE_MAX_MARKERS];         /* n - votes[m][0]                                    */
+  uint32_t mode_blob[PFMPE_MAX_MARKERS];       /* 1-based blob with the most votes of LED m (lowest
+                                                  index on a tie); 0 when no particle matched LED m   */
+  uint32_t mode_votes[PFMPE_MAX_MARKERS];
+  uint32_t second_votes[PFMPE_MAX_MARKERS];    /* votes of the runner-up blob (0 if none)            */
+  uint32_t npairs_hist[PFMPE_MAX_MARKERS + 1]; /* particles with exactly k pairs                     */
+  uint32_t pad;
+} pfmpe_assoc_out;                             /* 352 bytes */
+/* votes: M x (B + 1) words, row-major, may be NULL */
+int pfmpe_assoc_stats(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, pfmpe_assoc_out* out, uint32_t* votes);
+/* the rows of particles first .. first + count - 1 (the reference's correspondencesVec[i]):
+ * corr count x 2*PFMPE_MAX_MARKERS words, n_corr count pair counts */
+int pfmpe_get_pairs(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, int64_t first, int32_t count,
+                    uint32_t* corr, int32_t* n_corr);
+
 /* Engine options (value semantics in brackets; defaults first):
  *   PFMPE_OPT_RECORD_COUNTS [0|1]  keep counterMeas on device for pfmpe_get_counts
  *   PFMPE_OPT_PRUNE         [1|0]  exact x-window blob pruning in the likelihood (0 = scan all B blobs)
@@ -437,6 +488,10 @@ double pfmpe_host_ref_uniform(uint32_t seed, uint64_t j, double a, double b);
 void pfmpe_host_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 /* twist6 = xi of pose12 about ref_pose12 (the definition at the cloud statistics above), as the kernel forms it */
 void pfmpe_host_pose_twist(const double* pose12, const double* ref_pose12, double* twist6);
+/* n, M, B, matched and the mode fields of `out` from a votes table (M x (B + 1), row-major; the other fields are
+ * zeroed), the function pfmpe_assoc_stats calls after its read-back.  PFMPE_E_ARG for a NULL pointer, M outside
+ * 1 .. PFMPE_MAX_MARKERS, B < 0, or rows that do not all sum to the same n. */
+int pfmpe_host_assoc_summary(const uint32_t* votes, int M, int B, pfmpe_assoc_out* out);
 
 #ifdef __cplusplus
 }

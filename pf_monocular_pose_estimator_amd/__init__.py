@@ -14,6 +14,7 @@ from ._capi import (  # noqa: F401
     SHAPE_TWO_LAUNCH, SHAPE_FRAME, SHAPE_FRAME2, INFO_FUSED, INFO_FUSED_FALLBACKS, INFO_LAST_SHAPE,
     INFO_GUARD_SKIPS, INFO_N, INFO_LAST_WEIGH_PASS, INFO_LAST_GRID, INFO_LAST_RESAMPLE, RESAMPLE_BLOCKS, RESAMPLE_OWNERS, WEIGH_BLOCKS, WEIGH_STREAM, WEIGH_PK,
     CLOUD_WEIGHTED, CLOUD_POSTERIOR, CloudOut, host_pose_twist,
+    ASSOC_PROPAGATED, ASSOC_POSTERIOR, DIAG_ASSOC_DIRECT, AssocIn, AssocOut, host_assoc_summary,
 )
 
 __all__ = [

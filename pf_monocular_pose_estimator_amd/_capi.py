@@ -26,6 +26,7 @@ OPT_DIAG = 99  # undocumented diagnostic switches (csrc/pf_kernels.hpp kDiag*)
 DIAG_LAG_LOADS, DIAG_ABANDON, DIAG_NO_STREAM, DIAG_FORCE_STREAM, DIAG_SERIAL_TOP = 64, 128, 512, 1024, 2048
 DIAG_NO_PK, DIAG_CORRUPT_DESC, DIAG_NO_DEFER, DIAG_BLOCK_RESAMPLE, DIAG_MIN_SIDE = 4096, 8192, 16384, 32768, 65536
 DIAG_ABANDON_FINISH = 131072
+DIAG_ASSOC_DIRECT = 262144  # assoc_stats: every vote straight into the device table (the path of tables too large for LDS)
 OPT_DEFER_RESAMPLE = 9
 SHAPE_TWO_LAUNCH, SHAPE_FRAME, SHAPE_FRAME2 = 0, 1, 2
 INFO_FUSED, INFO_FUSED_FALLBACKS, INFO_LAST_SHAPE, INFO_GUARD_SKIPS, INFO_N, INFO_LAST_WEIGH_PASS = 1, 2, 3, 4, 5, 6
@@ -33,6 +34,7 @@ INFO_LAST_GRID, INFO_LAST_RESAMPLE = 7, 8
 WEIGH_BLOCKS, WEIGH_STREAM, WEIGH_PK = 0, 1, 2
 RESAMPLE_BLOCKS, RESAMPLE_OWNERS = 0, 1
 CLOUD_WEIGHTED, CLOUD_POSTERIOR = 0, 1
+ASSOC_PROPAGATED, ASSOC_POSTERIOR = 0, 1
 K_PROPAGATE, K_RESAMPLE, K_AUX, K_FRAME, K_ROI, K_FINAL, K_P3P_HIST, K_P3P_CHECK, K_DETECT, K_COUNT = range(10)
 
 # every symbol include/pfmpe.h declares (tests check the .so exports all of them)
@@ -47,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "pfmpe_write_blob_stream", "pfmpe_read_blob_stream", "pfmpe_stage_blob_stream",
     "pfmpe_default_detect_params", "pfmpe_stage_image", "pfmpe_find_leds", "pfmpe_get_info",
     "pfmpe_cloud_stats", "pfmpe_host_pose_twist",
+    "pfmpe_assoc_stats", "pfmpe_get_pairs", "pfmpe_host_assoc_summary",
 )
 
 
@@ -155,6 +158,26 @@ class CloudOut(C.Structure):
                 "mean_pose": np.array(self.mean_pose), "max_trans": self.max_trans, "max_rot": self.max_rot}
 
 
+class AssocIn(C.Structure):
+    _fields_ = [("blobs", C.POINTER(C.c_double)), ("B", C.c_int32), ("bank_frame", C.c_int32)]
+
+
+class AssocOut(C.Structure):
+    _fields_ = [("n", C.c_int64), ("M", C.c_int32), ("B", C.c_int32), ("n_any", C.c_int64),
+                ("matched", C.c_uint32 * MAX_MARKERS), ("mode_blob", C.c_uint32 * MAX_MARKERS),
+                ("mode_votes", C.c_uint32 * MAX_MARKERS), ("second_votes", C.c_uint32 * MAX_MARKERS),
+                ("npairs_hist", C.c_uint32 * (MAX_MARKERS + 1)), ("pad", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        """The arrays trimmed to the M LEDs (npairs_hist to M + 1 counts)."""
+        M = self.M
+        d = {"n": self.n, "M": M, "B": self.B, "n_any": self.n_any}
+        for k in ("matched", "mode_blob", "mode_votes", "second_votes"):
+            d[k] = np.array(getattr(self, k)[:M], dtype=np.uint32)
+        d["npairs_hist"] = np.array(self.npairs_hist[: M + 1], dtype=np.uint32)
+        return d
+
+
 _lib = None
 
 
@@ -196,6 +219,10 @@ def load() -> C.CDLL:
         "pfmpe_host_philox": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "pfmpe_host_pose_twist": (None, [dp, dp, dp]),
         "pfmpe_cloud_stats": (I, [P, I, dp, C.POINTER(CloudOut)]),
+        "pfmpe_assoc_stats": (I, [P, I, C.POINTER(AssocIn), C.POINTER(AssocOut), C.POINTER(C.c_uint32)]),
+        "pfmpe_get_pairs": (I, [P, I, C.POINTER(AssocIn), C.c_int64, C.c_int32, C.POINTER(C.c_uint32),
+                                C.POINTER(C.c_int32)]),
+        "pfmpe_host_assoc_summary": (I, [C.POINTER(C.c_uint32), I, I, C.POINTER(AssocOut)]),
         "pfmpe_predict_roi": (I, [P, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
         "pfmpe_default_init_params": (None, [C.POINTER(InitParams)]),
         "pfmpe_p3p_histogram": (I, [P, dp, I, C.POINTER(C.c_uint32)]),
@@ -488,6 +515,52 @@ class Engine:
         self._chk(self.lib.pfmpe_cloud_stats(self.ctx, int(which), _dptr(r), C.byref(out)))
         return out.as_dict()
 
+    @staticmethod
+    def _assoc_in(blobs, bank_frame):
+        ai = AssocIn()
+        keep = None
+        if blobs is not None and bank_frame < 0:
+            keep = np.ascontiguousarray(blobs, dtype=np.float64).reshape(-1, 2)
+            ai.blobs = _dptr(keep)
+            ai.B = keep.shape[0]
+        ai.bank_frame = int(bank_frame)
+        return ai, keep
+
+    def assoc_stats(self, which: int = ASSOC_POSTERIOR, blobs=None, bank_frame: int = -1, want_votes: bool = True) -> dict:
+        """Which blob each LED matched, counted over a particle set on the device (pfmpe_assoc_stats).  which:
+        ASSOC_POSTERIOR (the current prior) or ASSOC_PROPAGATED (the last step's kept propagated set); blobs: the
+        frame's B x 2 list, or bank_frame: a frame of the staged bank.  Returns AssocOut.as_dict() plus, with
+        want_votes, "votes": the (M, B + 1) uint32 table (column 0: particles that left the LED unpaired)."""
+        ai, keep = self._assoc_in(blobs, bank_frame)
+        out = AssocOut()
+        votes = None
+        vp = C.POINTER(C.c_uint32)()
+        if want_votes:
+            nb = keep.shape[0] if keep is not None else 0
+            if bank_frame >= 0:  # the frame's count comes back in out.B: room for the largest frame
+                nb = MAX_BLOBS
+            votes = np.zeros(max(self.M, 1) * (nb + 1), dtype=np.uint32)
+            vp = votes.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._chk(self.lib.pfmpe_assoc_stats(self.ctx, int(which), C.byref(ai), C.byref(out), vp))
+        d = out.as_dict()
+        if want_votes:
+            d["votes"] = votes[: out.M * (out.B + 1)].reshape(out.M, out.B + 1).copy()
+        return d
+
+    def get_pairs(self, which: int, blobs=None, bank_frame: int = -1, first: int = 0, count=None):
+        """The pairs of particles first .. first + count - 1 of a set (pfmpe_get_pairs; count None: to the end):
+        (corr[count, MAX_MARKERS, 2] uint32 of 1-based (LED, blob) rows padded with zeros, n_corr[count] int32)."""
+        ai, keep = self._assoc_in(blobs, bank_frame)
+        if count is None:
+            count = self.N - int(first)
+        n = max(int(count), 0)
+        corr = np.zeros((n, MAX_MARKERS, 2), dtype=np.uint32)
+        n_corr = np.zeros(n, dtype=np.int32)
+        self._chk(self.lib.pfmpe_get_pairs(self.ctx, int(which), C.byref(ai), int(first), int(count),
+                                           corr.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                           n_corr.ctypes.data_as(C.POINTER(C.c_int32))))
+        return corr, n_corr
+
     def kernel_stats(self) -> dict:
         res = {}
         for k in range(K_COUNT):
@@ -581,6 +654,22 @@ def host_pose_twist(pose, ref) -> np.ndarray:
     out = np.zeros(6)
     load().pfmpe_host_pose_twist(_dptr(p), _dptr(r), _dptr(out))
     return out
+
+
+def host_assoc_summary(votes) -> dict:
+    """n, matched and the mode / runner-up fields of an (M, B + 1) votes table (pfmpe_host_assoc_summary, the code
+    assoc_stats runs after its read-back); ValueError when the rows do not all sum to the same n."""
+    v = np.ascontiguousarray(votes, dtype=np.uint32)
+    if v.ndim != 2 or v.shape[1] < 1:
+        raise ValueError("host_assoc_summary: votes must be an (M, B + 1) table")
+    out = AssocOut()
+    rc = load().pfmpe_host_assoc_summary(v.ctypes.data_as(C.POINTER(C.c_uint32)), v.shape[0], v.shape[1] - 1,
+                                         C.byref(out))
+    if rc != OK:
+        raise PFError(rc, "host_assoc_summary: bad table (rows must sum to one n, 1 <= M <= %d)" % MAX_MARKERS)
+    d = out.as_dict()
+    del d["n_any"], d["npairs_hist"]
+    return d
 
 
 def host_philox(ctr, key):

@@ -1653,8 +1653,10 @@ enum : int {
   kDiagMinSide = 65536,      // k_frame2: run the zmin scans (group_zmin2) even when no weight can be negative (tests)
   kDiagAbandonFinish = 131072,  // k_resample_owners(_multi): the finishing wave gives up before polling the arrivals
                                 // (the two-launch recovery tests)
-  kDiagBlockResample = 32768  // deferred two-launch frames resample with the block-per-256 k_resample instead of
+  kDiagBlockResample = 32768, // deferred two-launch frames resample with the block-per-256 k_resample instead of
                               // k_resample_owners' wave per 256 (A/B, identity tests)
+  kDiagAssocDirect = 262144   // pfmpe_assoc_stats: every vote straight into the device table even when the bins fit
+                              // in LDS (tests: both voting paths on one input)
 };
 __device__ __forceinline__ uint64_t rt_now() { return __builtin_amdgcn_s_memrealtime(); }
 // per-block stamps go to the block's own row (plain stores, no contended atomics); the host reduces rows
@@ -5358,6 +5360,109 @@ __global__ __launch_bounds__(kCloudSegs* kCloudWords) void k_cloud_final(const V
   if (sg == 0) {
     for (int s = 1; s < kCloudSegs; ++s) v = sum ? v + sh[s][q] : (sh[s][q] > v ? sh[s][q] : v);
     out[q] = v;
+  }
+}
+
+// ---- LED-blob association of the cloud (pfmpe_assoc_stats / pfmpe_get_pairs; the definition is in include/pfmpe.h):
+// every particle's pairs by the weighing kernels' per-lane path (project_markers, the NaN-at-origin rule,
+// column_minima, score_minima<PAIRS>), then either one vote per pair into integer bins or the particle's row.
+struct AssocArgs {
+  const double* dense;   // DENSE: N x 12 poses (the regenerated kept set)
+  uint32_t* votes;       // votes mode: M x B bins (LED m + 1 with blob b + 1 at m * B + b), then the M + 1 bins of the
+                         // pair count; null: rows mode
+  uint32_t* corr;        // rows mode: 2 * kMaxMarkers words per particle of the range (16-byte aligned)
+  int32_t* n_corr;       // rows mode: its pair count
+  int32_t first, count;  // the particles first .. first + count - 1
+  int32_t lds_votes;     // votes mode: the block's bins in LDS behind the blob table, flushed once per block; 0: every
+                         // vote straight into `votes` (the bins do not fit beside the table)
+  int32_t pad;
+};
+// a block per 256 particles up to 1024 blocks (as cloud_blocks), grid-stride beyond
+constexpr int kAssocMaxBlocks = 1024;
+// the workgroup's LDS: the blob table, the bins and the frame constants must fit
+constexpr size_t kAssocLdsLimit = 64 * 1024;
+__host__ __device__ inline int assoc_bins(int M, int B) { return M * B + M + 1; }
+// DENSE = false: the resident prior through StateIO / the owner indices (fa.owner, fa.anc_in, fa.ld), exactly the
+// rows k_export writes.  DENSE = true: N x 12 doubles, narrowed to T (exact: they are widened T values).  The bins
+// are integers, so the order of the adds does not matter: returnless LDS adds per vote, then one device-scope add
+// per non-zero bin and block into the table the host cleared.  No waits on other blocks.
+template <typename T, typename SP, bool DENSE, int MAXM, bool PRUNE>
+__global__ __launch_bounds__(kBlock) void k_assoc_votes(const FrameArgsT<T> fa, const AssocArgs aa,
+                                                       const unsigned char* __restrict__ table,
+                                                       const SP* __restrict__ st) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ LdsConst<T> sc;
+  const int M = fa.M, B = fa.B;
+  const int nbins = assoc_bins(M, B);
+  const bool lds = aa.votes && aa.lds_votes;
+  uint32_t* bins = (uint32_t*)(smem + BlobTable<T>::lds_bytes((size_t)fa.tbytes));
+  copy_table(table, smem, (size_t)fa.tbytes);
+  stage_consts(fa, sc);
+  if (lds)
+    for (int i = threadIdx.x; i < nbins; i += kBlock) bins[i] = 0u;
+  __syncthreads();  // table, constants and cleared bins visible
+  const LdsBlobs<T> tb = view_table<T>(smem, B);
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < aa.count; i += stride) {
+    const int64_t n = (int64_t)aa.first + i;
+    T P[12];
+    if constexpr (DENSE) {
+#pragma unroll
+      for (int q = 0; q < 12; ++q) P[q] = (T)aa.dense[12 * n + q];
+    } else {
+      const int64_t r = fa.owner ? (int64_t)fa.owner[n] : n;
+#pragma unroll
+      for (int q = 0; q < 12; ++q) P[q] = StateIO<T, SP>::load(st[plane_index<SP>(q, r, fa.ld)], fa.anc_in[q]);
+    }
+    T u[MAXM], v[MAXM];
+    project_markers<T, MAXM>(fa, sc, P, u, v);
+    uint32_t pairs[2 * MAXM];
+#pragma unroll
+    for (int q = 0; q < 2 * MAXM; ++q) pairs[q] = 0u;
+    int np = 0;
+    if (B > 0 && !nan_at_origin_tb(fa, tb, u[0], v[0])) {  // else the step's likelihood short-circuits: no pairs
+      T m[MAXM];
+      int r[MAXM];
+      (void)column_minima<T, MAXM, PRUNE>(fa, u, v, tb, m, r);
+      (void)score_minima<T, MAXM, true>(fa, m, r, pairs, &np);
+    }
+    if (aa.votes) {
+      // each add through its own pointer (the LDS add as ds_add_u32 without a return value, not a flat atomic)
+      auto vote = [&](int idx) {
+        if (lds)
+          (void)__hip_atomic_fetch_add(bins + idx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else
+          (void)__hip_atomic_fetch_add(aa.votes + idx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      };
+#pragma unroll
+      for (int k = 0; k < MAXM; ++k)
+        if (k < np) vote(((int)pairs[2 * k] - 1) * B + ((int)pairs[2 * k + 1] - 1));
+      vote(M * B + np);
+    } else {
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      u32x4* row = (u32x4*)(aa.corr + (size_t)i * (2 * kMaxMarkers));
+#pragma unroll
+      for (int g = 0; g < 2 * kMaxMarkers / 4; ++g) {
+        u32x4 w = {0u, 0u, 0u, 0u};
+        if (4 * g < 2 * MAXM) {
+          w.x = pairs[4 * g];
+          w.y = pairs[4 * g + 1];
+        }
+        if (4 * g + 2 < 2 * MAXM) {
+          w.z = pairs[4 * g + 2];
+          w.w = pairs[4 * g + 3];
+        }
+        row[g] = w;
+      }
+      aa.n_corr[i] = np;
+    }
+  }
+  if (lds) {
+    __syncthreads();  // every wave's votes are in the bins
+    for (int i = threadIdx.x; i < nbins; i += kBlock) {
+      const uint32_t x = bins[i];
+      if (x) (void)__hip_atomic_fetch_add(aa.votes + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
 }
 

@@ -92,6 +92,8 @@ struct pfmpe_ctx {
   double* d_mlpose = nullptr;      // most likely pose (12)
   double* d_roi = nullptr;         // ROI box [4] + per-block partials
   double* d_cloud = nullptr;       // cloud statistics: result row + per-block partial rows (pfmpe_cloud_stats)
+  uint32_t* d_assoc = nullptr;     // association votes: M x B bins + the pair-count bins (pfmpe_assoc_stats)
+  uint32_t* d_pairs = nullptr;     // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
   unsigned char* d_init = nullptr; // initialisation scratch (pfmpe_init.hip), grown on demand
   size_t init_cap = 0;
   unsigned char* d_det = nullptr;  // detector scratch (pfmpe_detect.hip), grown on demand
@@ -427,6 +429,12 @@ inline int ensure_prop(pfmpe_ctx* c) {
 inline const uint32_t* prior_owner_ptr(const pfmpe_ctx* c) {
   return c->prior_owner >= 0 ? c->d_owner[c->prior_owner] : nullptr;
 }
+
+// k_assoc_votes for the context's state type, marker bucket and pruning option on its stream (pfmpe_assoc.hip, a TU
+// of its own): the particles aa.first .. + aa.count of the regenerated kept set (aa.dense) or of the resident prior,
+// against the blob table `table` (device, tbytes, grid header gh) of B blobs, with the context's current model and
+// parameters.  aa.lds_votes is set here.  Not bracketed by the timing events.
+int assoc_launch(pfmpe_ctx* c, int B, const unsigned char* table, size_t tbytes, const GridHdr& gh, AssocArgs aa);
 
 // Batch scratch layout (pfmpe_step_multi), the same in the pinned host image and in HBM: host-supplied blob
 // tables [0, tbytes), then `na` stream descriptors from doff, then the uint16 block -> stream map of `total`

@@ -89,7 +89,7 @@ size_t build_table(const pfmpe_ctx* c, const double* blobs, int B, unsigned char
 void free_all(pfmpe_ctx* c) {
   void* dev[] = {c->d_state[0], c->d_state[1], c->d_w[0], c->d_w[1], c->d_prop[0], c->d_prop[1], c->d_part[0], c->d_part[1],
                  c->d_bscan[0], c->d_bscan[1], c->d_gpart[0], c->d_gpart[1], c->d_gscan, c->d_cpart, c->d_winkey,
-                 c->d_cgroup, c->d_counters, c->d_ctrl, c->d_gen, c->d_cand, c->d_mlpose, c->d_flat, c->d_roi, c->d_cloud, c->d_gran, c->d_init, c->d_det, c->d_img, c->d_table, c->d_bank, c->d_xfer, c->d_counts,
+                 c->d_cgroup, c->d_counters, c->d_ctrl, c->d_gen, c->d_cand, c->d_mlpose, c->d_flat, c->d_roi, c->d_cloud, c->d_assoc, c->d_pairs, c->d_gran, c->d_init, c->d_det, c->d_img, c->d_table, c->d_bank, c->d_xfer, c->d_counts,
                  c->d_stamps, c->d_owner[0], c->d_owner[1]};
   for (void* p : dev)
     if (p) (void)hipFree(p);
@@ -846,6 +846,149 @@ int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_ou
       out->mean_pose[i * 4 + j] = E[i * 4] * ref[j] + E[i * 4 + 1] * ref[4 + j] + E[i * 4 + 2] * ref[8 + j];
     out->mean_pose[i * 4 + 3] = E[i * 4] * ref[3] + E[i * 4 + 1] * ref[7] + E[i * 4 + 2] * ref[11] + E[i * 4 + 3];
   }
+  return PFMPE_OK;
+}
+
+int pfmpe_host_assoc_summary(const uint32_t* votes, int M, int B, pfmpe_assoc_out* out) {
+  if (!votes || !out || M < 1 || M > kMaxMarkers || B < 0) return PFMPE_E_ARG;
+  std::memset(out, 0, sizeof(*out));
+  out->M = M;
+  out->B = B;
+  for (int m = 0; m < M; ++m) {
+    const uint32_t* row = votes + (size_t)m * (B + 1);
+    int64_t sum = 0;
+    uint32_t best = 0, second = 0, arg = 0;
+    for (int b = 0; b <= B; ++b) sum += row[b];
+    for (int b = 1; b <= B; ++b) {  // a strict test keeps the lowest blob index among equal vote counts
+      if (row[b] > best) {
+        second = best;
+        best = row[b];
+        arg = (uint32_t)b;
+      } else if (row[b] > second) {
+        second = row[b];
+      }
+    }
+    if (m == 0) out->n = sum;
+    if (sum != out->n) return PFMPE_E_ARG;
+    out->matched[m] = (uint32_t)(sum - row[0]);
+    out->mode_blob[m] = best ? arg : 0u;
+    out->mode_votes[m] = best;
+    out->second_votes[m] = second;
+  }
+  return PFMPE_OK;
+}
+
+namespace {
+// pair rows per get_pairs launch (the chunk buffer d_pairs: 132 B per particle)
+constexpr int kPairsChunk = 1 << 16;
+
+// The argument and state checks shared by pfmpe_assoc_stats / pfmpe_get_pairs, then the call's blob table built
+// into d_table (every frame that reads d_table writes it first) and, for the propagated set, the kept set
+// regenerated into d_xfer (written and read inside one blocking call by every user).
+int assoc_prepare(pfmpe_ctx* c, const char* who, int which, const pfmpe_assoc_in* in, int* B_out, size_t* tbytes,
+                  GridHdr* gh, AssocArgs* aa) {
+  const std::string w(who);
+  if (!in || (which != PFMPE_ASSOC_PROPAGATED && which != PFMPE_ASSOC_POSTERIOR))
+    return fail(c, PFMPE_E_ARG, w + ": bad arguments");
+  if (in->B < 0) return fail(c, PFMPE_E_ARG, w + ": B < 0");
+  const double* blobs = in->blobs;
+  int B = in->B;
+  if (in->bank_frame >= 0) {
+    if (c->bank_offsets.empty() || in->bank_frame >= (int)c->bank_offsets.size() - 1)
+      return fail(c, PFMPE_E_ARG, w + ": bank_frame out of range");
+    B = c->bank_offsets[in->bank_frame + 1] - c->bank_offsets[in->bank_frame];
+    blobs = c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame];
+  } else if (B > 0 && !blobs) {
+    return fail(c, PFMPE_E_ARG, w + ": null blobs");
+  }
+  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, w + ": B exceeds max_blobs");
+  if (!c->has_model || !c->has_prior) return fail(c, PFMPE_E_STATE, w + ": set_model and a particle set first");
+  if (which == PFMPE_ASSOC_PROPAGATED && !c->has_last) return fail(c, PFMPE_E_STATE, w + "(propagated): no step yet");
+  RET(set_device(c));
+  *tbytes = build_table(c, blobs, B, c->h_table);
+  *gh = *(const GridHdr*)(c->h_table + grid_off(c, B));
+  HIPCHK(c, hipMemcpyAsync(c->d_table, c->h_table, *tbytes, hipMemcpyHostToDevice, c->stream));
+  *aa = AssocArgs{};
+  if (which == PFMPE_ASSOC_PROPAGATED) {
+    RET(ensure_xfer(c));
+    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx], c->d_xfer));
+    aa->dense = c->d_xfer;
+  }
+  *B_out = B;
+  return PFMPE_OK;
+}
+}  // namespace
+
+int pfmpe_assoc_stats(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, pfmpe_assoc_out* out, uint32_t* votes) {
+  if (!c) return PFMPE_E_ARG;
+  if (!out) return fail(c, PFMPE_E_ARG, "assoc_stats: null out");
+  int B = 0;
+  size_t tbytes = 0;
+  GridHdr gh{};
+  AssocArgs aa{};
+  RET(assoc_prepare(c, "assoc_stats", which, in, &B, &tbytes, &gh, &aa));
+  // scratch of the call's own: the bins of the largest table
+  if (!c->d_assoc)
+    HIPCHK(c, hipMalloc((void**)&c->d_assoc, (size_t)assoc_bins(kMaxMarkers, kMaxBlobs) * sizeof(uint32_t)));
+  const int M = c->M, N = c->N;
+  const int nbins = assoc_bins(M, B);
+  HIPCHK(c, hipMemsetAsync(c->d_assoc, 0, (size_t)nbins * sizeof(uint32_t), c->stream));
+  aa.votes = c->d_assoc;
+  aa.first = 0;
+  aa.count = N;
+  RET(assoc_launch(c, B, c->d_table, tbytes, gh, aa));
+  std::vector<uint32_t> bins(nbins);
+  HIPCHK(c, hipMemcpyAsync(bins.data(), c->d_assoc, (size_t)nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  RET(harvest_timing(c));  // (a propagated call's regeneration is bracketed like the particle read-back's)
+
+  // column 0 is not voted: n minus the row's votes
+  std::vector<uint32_t> tab((size_t)M * (B + 1));
+  for (int m = 0; m < M; ++m) {
+    uint32_t sum = 0;
+    for (int b = 0; b < B; ++b) {
+      tab[(size_t)m * (B + 1) + 1 + b] = bins[(size_t)m * B + b];
+      sum += bins[(size_t)m * B + b];
+    }
+    tab[(size_t)m * (B + 1)] = (uint32_t)N - sum;
+  }
+  if (pfmpe_host_assoc_summary(tab.data(), M, B, out) != PFMPE_OK)
+    return fail(c, PFMPE_E_STATE, "assoc_stats: inconsistent votes table");
+  for (int k = 0; k <= M; ++k) out->npairs_hist[k] = bins[(size_t)M * B + k];
+  out->n_any = (int64_t)N - (int64_t)out->npairs_hist[0];
+  if (votes) std::memcpy(votes, tab.data(), tab.size() * sizeof(uint32_t));
+  return PFMPE_OK;
+}
+
+int pfmpe_get_pairs(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, int64_t first, int32_t count, uint32_t* corr,
+                    int32_t* n_corr) {
+  if (!c) return PFMPE_E_ARG;
+  if (first < 0 || count < 0 || (count > 0 && (!corr || !n_corr)))
+    return fail(c, PFMPE_E_ARG, "get_pairs: bad range or null output");
+  if (c->has_prior && first + (int64_t)count > (int64_t)c->N)
+    return fail(c, PFMPE_E_ARG, "get_pairs: first + count exceeds the particle count");
+  int B = 0;
+  size_t tbytes = 0;
+  GridHdr gh{};
+  AssocArgs aa{};
+  RET(assoc_prepare(c, "get_pairs", which, in, &B, &tbytes, &gh, &aa));
+  constexpr size_t kRow = 2 * kMaxMarkers;
+  const int cap = std::min(c->max_particles, kPairsChunk);
+  if (!c->d_pairs) HIPCHK(c, hipMalloc((void**)&c->d_pairs, (size_t)cap * (kRow + 1) * sizeof(uint32_t)));
+  aa.corr = c->d_pairs;
+  aa.n_corr = (int32_t*)(c->d_pairs + (size_t)cap * kRow);
+  for (int64_t done = 0; done < count; done += cap) {
+    const int n = (int)std::min<int64_t>(cap, count - done);
+    aa.first = (int32_t)(first + done);
+    aa.count = n;
+    RET(assoc_launch(c, B, c->d_table, tbytes, gh, aa));
+    HIPCHK(c, hipMemcpyAsync(corr + (size_t)done * kRow, aa.corr, (size_t)n * kRow * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(n_corr + done, aa.n_corr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the chunk buffer is reused
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  RET(harvest_timing(c));
   return PFMPE_OK;
 }
 
