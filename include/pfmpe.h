@@ -399,6 +399,80 @@ int pfmpe_assoc_stats(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, pfmpe
 int pfmpe_get_pairs(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, int64_t first, int32_t count,
                     uint32_t* corr, int32_t* n_corr);
 
+/* ------------------------------------------------------------------- Gauss-Newton refinement of hypotheses */
+/* Replaces PoseEstimator::optimisePose (PE:1805-2009): the reference refines the winner of the PF step over its
+ * correspondences and publishes that pose and pose_covariance_ = A.inverse() (PE:2004).  pfmpe_refine_poses does so
+ * for K caller-given hypotheses (K = 1 with pfmpe_frame_out.most_likely_pose / .corr is the reference's step);
+ * pfmpe_refine_cloud refines every particle of a set from its own pairs, one lane per particle, and names the best.
+ *
+ * Definition, per hypothesis, fp64 for every state type (the formulas of PE:1805-2009 in their order, unfused):
+ * at most max_iter iterations; rows with blob index 0 are skipped; per pair e = z - project2d(pose, LED) through the
+ * full K (PE:1017-1034) and the 2 x 6 Jacobian of computeJacobian (PE:2163-2192) on the camera-frame point with
+ * fx = K[0], fy = K[4]; A += J^T J, b += J^T e in row order; dT = A.ldlt().solve(b) with Eigen's symmetric diagonal
+ * pivoting (dT = 0 when a pivot is exactly 0); pose = exponentialMap(dT) * pose (PE:2194-2226); stop when
+ * max |dT| <= converged.  At the last allowed iteration the reference's rule (PE:1886-1895) with its `=+`: e_init and
+ * e_end are the error norms of the last used pair at iteration 0 and at the last iteration, and the start pose is
+ * restored when e_init < e_end.  The covariance is the inverse of the last A formed, column by column through the
+ * same factors, all zeros when a pivot was 0.  rms_before / rms_after = sqrt(mean |z - uv|^2) over the used pairs at
+ * the start pose and at the returned pose (not computed by the reference).
+ * The iteration count is not stable: convergence ends in rounding noise around `converged`, so a change of one ulp
+ * in the start pose moves it, also across max_iter.  The refined pose of a converged hypothesis is stable.
+ *
+ * CLOUD: hypothesis i is particle first + i of set `which` (PFMPE_ASSOC_PROPAGATED / _POSTERIOR): its start pose is
+ * the 12 doubles pfmpe_get_particles(which) returns for it, its rows those pfmpe_get_pairs(which) returns for it.
+ * The summary always covers all N particles; rows / cov cover the requested range.
+ * Best hypothesis: most pairs, then the smallest rms_after, then the lowest index, among those with at least one pair
+ * and a finite rms_after.  Every number of the summary is an integer or belongs to one hypothesis: a repeated call
+ * returns the same bits.
+ *
+ * Both device calls are blocking, run on the context's stream, change nothing a later frame reads and are not timed
+ * by PFMPE_OPT_TIMING (regenerating the propagated set counts as aux, as for the particle read-back).  params NULL:
+ * the defaults.  K = 0 / count = 0 are valid (CLOUD: the summary still covers all N).
+ * Errors: PFMPE_E_ARG for a NULL out or blobs descriptor, NULL blobs with B > 0 and no bank frame, B < 0, a bank
+ * frame out of range, NULL poses / corr with K > 0, K < 0, an LED index above M (or 0 beside a blob) or a blob index
+ * above B in corr, a non-finite start pose, a bad `which`, first < 0, count < 0 or first + count > N, max_iter
+ * outside 1..10000, a negative or NaN converged; PFMPE_E_CAP for B > max_blobs or K > max_particles; PFMPE_E_STATE
+ * without a model, CLOUD without a particle set, and for PROPAGATED before the first step. */
+typedef struct {
+  int32_t max_iter;             /* 500  (PE:1810), 1..10000                                        */
+  int32_t revert_on_divergence; /* 1    (PE:1886-1892); 0 keeps the last iterate                   */
+  double  converged;            /* 1e-13 (PE:1809), >= 0                                           */
+} pfmpe_refine_params;
+void pfmpe_default_refine_params(pfmpe_refine_params* p);
+
+enum { PFMPE_REFINE_NO_PAIRS = 0, PFMPE_REFINE_CONVERGED = 1, PFMPE_REFINE_CAP_KEPT = 2, PFMPE_REFINE_CAP_REVERTED = 3 };
+typedef struct {
+  double pose[12];              /* refined pose; the start pose for NO_PAIRS / CAP_REVERTED         */
+  double rms_before, rms_after; /* px; 0 for NO_PAIRS                                               */
+  int32_t iters;                /* PubData.numIter when converged, else max_iter                    */
+  int32_t n_pairs;              /* rows used (blob != 0)                                            */
+  int32_t status, pad;
+} pfmpe_refine_row;             /* 128 bytes */
+
+typedef struct {
+  int64_t n, n_with_pairs, n_converged, n_cap_kept, n_cap_reverted;
+  int64_t iters_total; int32_t iters_max; int32_t pad;
+  int64_t best;                 /* index within the call (LIST: row; CLOUD: particle index), -1 if none */
+  pfmpe_refine_row best_row;
+  double best_cov[36];          /* pose_covariance_ = A.inverse() (PE:2004) of the best hypothesis  */
+} pfmpe_refine_out;
+
+/* optimisePose for K caller-given hypotheses: poses K x 12, corr K x 2*PFMPE_MAX_MARKERS (1-based (LED, blob)
+ * rows, zero padded, as pfmpe_frame_out.corr).  rows (K) and cov (K x 36) may be NULL. */
+int pfmpe_refine_poses(pfmpe_ctx* ctx, const pfmpe_assoc_in* blobs, const pfmpe_refine_params* params,
+                       const double* poses, const uint32_t* corr, int32_t K, pfmpe_refine_out* out,
+                       pfmpe_refine_row* rows, double* cov);
+/* every particle of set `which` (PFMPE_ASSOC_PROPAGATED / _POSTERIOR) from its own pairs; the summary covers all
+ * N, rows / cov (may be NULL) cover particles first .. first + count - 1 */
+int pfmpe_refine_cloud(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* blobs, const pfmpe_refine_params* params,
+                       int64_t first, int32_t count, pfmpe_refine_out* out, pfmpe_refine_row* rows, double* cov);
+/* host-only: the same __host__ __device__ code for one hypothesis (no GPU, no context).  corr: n_rows rows (any
+ * count).  PFMPE_E_ARG for a NULL pointer, M < 1, B < 0, n_rows < 0, a bad index, a non-finite start pose or bad
+ * parameters, as above.  params may be NULL, cov36 may be NULL. */
+int pfmpe_host_optimise_pose(const double* markers_xyz, int M, const double* K, const double* blobs, int B,
+                             const uint32_t* corr, int n_rows, const pfmpe_refine_params* params, const double* pose12,
+                             pfmpe_refine_row* row, double* cov36);
+
 /* Engine options (value semantics in brackets; defaults first):
  *   PFMPE_OPT_RECORD_COUNTS [0|1]  keep counterMeas on device for pfmpe_get_counts
  *   PFMPE_OPT_PRUNE         [1|0]  exact x-window blob pruning in the likelihood (0 = scan all B blobs)

@@ -15,6 +15,8 @@ from ._capi import (  # noqa: F401
     INFO_GUARD_SKIPS, INFO_N, INFO_LAST_WEIGH_PASS, INFO_LAST_GRID, INFO_LAST_RESAMPLE, RESAMPLE_BLOCKS, RESAMPLE_OWNERS, WEIGH_BLOCKS, WEIGH_STREAM, WEIGH_PK,
     CLOUD_WEIGHTED, CLOUD_POSTERIOR, CloudOut, host_pose_twist,
     ASSOC_PROPAGATED, ASSOC_POSTERIOR, DIAG_ASSOC_DIRECT, AssocIn, AssocOut, host_assoc_summary,
+    REFINE_NO_PAIRS, REFINE_CONVERGED, REFINE_CAP_KEPT, REFINE_CAP_REVERTED, REFINE_ROW_DTYPE, RefineParams, RefineRow,
+    RefineOut, default_refine_params, host_optimise_pose,
 )
 
 __all__ = [

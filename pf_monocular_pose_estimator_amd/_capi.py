@@ -35,6 +35,7 @@ WEIGH_BLOCKS, WEIGH_STREAM, WEIGH_PK = 0, 1, 2
 RESAMPLE_BLOCKS, RESAMPLE_OWNERS = 0, 1
 CLOUD_WEIGHTED, CLOUD_POSTERIOR = 0, 1
 ASSOC_PROPAGATED, ASSOC_POSTERIOR = 0, 1
+REFINE_NO_PAIRS, REFINE_CONVERGED, REFINE_CAP_KEPT, REFINE_CAP_REVERTED = 0, 1, 2, 3
 K_PROPAGATE, K_RESAMPLE, K_AUX, K_FRAME, K_ROI, K_FINAL, K_P3P_HIST, K_P3P_CHECK, K_DETECT, K_COUNT = range(10)
 
 # every symbol include/pfmpe.h declares (tests check the .so exports all of them)
@@ -50,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "pfmpe_default_detect_params", "pfmpe_stage_image", "pfmpe_find_leds", "pfmpe_get_info",
     "pfmpe_cloud_stats", "pfmpe_host_pose_twist",
     "pfmpe_assoc_stats", "pfmpe_get_pairs", "pfmpe_host_assoc_summary",
+    "pfmpe_default_refine_params", "pfmpe_refine_poses", "pfmpe_refine_cloud", "pfmpe_host_optimise_pose",
 )
 
 
@@ -178,6 +180,33 @@ class AssocOut(C.Structure):
         return d
 
 
+class RefineParams(C.Structure):
+    _fields_ = [("max_iter", C.c_int32), ("revert_on_divergence", C.c_int32), ("converged", C.c_double)]
+
+
+class RefineRow(C.Structure):
+    _fields_ = [("pose", C.c_double * 12), ("rms_before", C.c_double), ("rms_after", C.c_double),
+                ("iters", C.c_int32), ("n_pairs", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+# pfmpe_refine_row as a numpy record (128 bytes)
+REFINE_ROW_DTYPE = np.dtype([("pose", np.float64, 12), ("rms_before", np.float64), ("rms_after", np.float64),
+                             ("iters", np.int32), ("n_pairs", np.int32), ("status", np.int32), ("pad", np.int32)])
+
+
+class RefineOut(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_with_pairs", C.c_int64), ("n_converged", C.c_int64), ("n_cap_kept", C.c_int64),
+                ("n_cap_reverted", C.c_int64), ("iters_total", C.c_int64), ("iters_max", C.c_int32), ("pad", C.c_int32),
+                ("best", C.c_int64), ("best_row", RefineRow), ("best_cov", C.c_double * 36)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k in ("n", "n_with_pairs", "n_converged", "n_cap_kept", "n_cap_reverted",
+                                           "iters_total", "iters_max", "best")}
+        d["best_row"] = np.frombuffer(bytes(self.best_row), dtype=REFINE_ROW_DTYPE)[0].copy()
+        d["best_cov"] = np.array(self.best_cov).reshape(6, 6)
+        return d
+
+
 _lib = None
 
 
@@ -223,6 +252,13 @@ def load() -> C.CDLL:
         "pfmpe_get_pairs": (I, [P, I, C.POINTER(AssocIn), C.c_int64, C.c_int32, C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_int32)]),
         "pfmpe_host_assoc_summary": (I, [C.POINTER(C.c_uint32), I, I, C.POINTER(AssocOut)]),
+        "pfmpe_default_refine_params": (None, [C.POINTER(RefineParams)]),
+        "pfmpe_refine_poses": (I, [P, C.POINTER(AssocIn), C.POINTER(RefineParams), dp, C.POINTER(C.c_uint32), C.c_int32,
+                                   C.POINTER(RefineOut), P, dp]),
+        "pfmpe_refine_cloud": (I, [P, I, C.POINTER(AssocIn), C.POINTER(RefineParams), C.c_int64, C.c_int32,
+                                   C.POINTER(RefineOut), P, dp]),
+        "pfmpe_host_optimise_pose": (I, [dp, I, dp, dp, I, C.POINTER(C.c_uint32), I, C.POINTER(RefineParams), dp,
+                                         C.POINTER(RefineRow), dp]),
         "pfmpe_predict_roi": (I, [P, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
         "pfmpe_default_init_params": (None, [C.POINTER(InitParams)]),
         "pfmpe_p3p_histogram": (I, [P, dp, I, C.POINTER(C.c_uint32)]),
@@ -561,6 +597,53 @@ class Engine:
                                            n_corr.ctypes.data_as(C.POINTER(C.c_int32))))
         return corr, n_corr
 
+    def _refine_result(self, out, rows, cov):
+        d = out.as_dict()
+        d["rows"] = rows
+        if cov is not None:
+            d["cov"] = cov
+        return d
+
+    def refine_poses(self, poses, pairs, blobs=None, bank_frame: int = -1, params=None, want_cov: bool = False) -> dict:
+        """Gauss-Newton (optimisePose) of K hypotheses on the device (pfmpe_refine_poses).  poses: K x 12 (or K 3x4 /
+        4x4 matrices); pairs: K x MAX_MARKERS x 2 1-based (LED, blob) rows padded with zeros (FrameOut.corr, get_pairs);
+        blobs: the frame's B x 2 list, or bank_frame.  Returns the summary (RefineOut.as_dict()) plus "rows", a
+        REFINE_ROW_DTYPE array of K records, and with want_cov "cov" (K, 6, 6)."""
+        ai, keep = self._assoc_in(blobs, bank_frame)
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, MAX_MARKERS, 2)
+        k = pairs.shape[0]
+        poses = np.asarray(poses, dtype=np.float64)
+        if poses.shape[-2:] == (4, 4):
+            poses = poses[..., :3, :]
+        poses = np.ascontiguousarray(poses.reshape(-1, 12))
+        if poses.shape[0] != k:
+            raise ValueError("refine_poses: one pair table per pose")
+        rows = np.zeros(k, dtype=REFINE_ROW_DTYPE)
+        cov = np.zeros((k, 6, 6), dtype=np.float64) if want_cov else None
+        out = RefineOut()
+        self._chk(self.lib.pfmpe_refine_poses(
+            self.ctx, C.byref(ai), C.byref(params) if params is not None else None, _dptr(poses),
+            pairs.ctypes.data_as(C.POINTER(C.c_uint32)), k, C.byref(out), rows.ctypes.data_as(C.c_void_p),
+            _dptr(cov) if want_cov else None))
+        return self._refine_result(out, rows, cov)
+
+    def refine_cloud(self, which: int, blobs=None, bank_frame: int = -1, first: int = 0, count=None, params=None,
+                     want_cov: bool = False) -> dict:
+        """Gauss-Newton of every particle of a set from its own pairs (pfmpe_refine_cloud).  The summary covers all N
+        particles; "rows" (and "cov" with want_cov) cover particles first .. first + count - 1 (count None: to the
+        end; count 0: the summary alone)."""
+        ai, keep = self._assoc_in(blobs, bank_frame)
+        if count is None:
+            count = self.N - int(first)
+        n = max(int(count), 0)
+        rows = np.zeros(n, dtype=REFINE_ROW_DTYPE)
+        cov = np.zeros((n, 6, 6), dtype=np.float64) if want_cov else None
+        out = RefineOut()
+        self._chk(self.lib.pfmpe_refine_cloud(
+            self.ctx, int(which), C.byref(ai), C.byref(params) if params is not None else None, int(first), int(count),
+            C.byref(out), rows.ctypes.data_as(C.c_void_p) if n else None, _dptr(cov) if (want_cov and n) else None))
+        return self._refine_result(out, rows, cov)
+
     def kernel_stats(self) -> dict:
         res = {}
         for k in range(K_COUNT):
@@ -654,6 +737,35 @@ def host_pose_twist(pose, ref) -> np.ndarray:
     out = np.zeros(6)
     load().pfmpe_host_pose_twist(_dptr(p), _dptr(r), _dptr(out))
     return out
+
+
+def default_refine_params() -> RefineParams:
+    p = RefineParams()
+    load().pfmpe_default_refine_params(C.byref(p))
+    return p
+
+
+def host_optimise_pose(markers, K, blobs, pairs, pose, params=None):
+    """optimisePose of one hypothesis on the host (pfmpe_host_optimise_pose: the code a lane of k_refine runs).  pairs:
+    (n, 2) 1-based (LED, blob) rows, blob 0 rows skipped.  Returns (row, cov): a REFINE_ROW_DTYPE record and (6, 6)."""
+    m = np.ascontiguousarray(markers, dtype=np.float64).reshape(-1, 3)
+    k = np.ascontiguousarray(K, dtype=np.float64).reshape(-1)
+    b = np.ascontiguousarray(blobs, dtype=np.float64).reshape(-1, 2)
+    c = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    p = np.asarray(pose, dtype=np.float64)
+    if p.shape == (4, 4):
+        p = p[:3, :]
+    p = np.ascontiguousarray(p.reshape(-1))
+    if k.size != 9 or p.size != 12:
+        raise ValueError("host_optimise_pose: K must be 3x3 and pose 3x4 (or 4x4)")
+    row = RefineRow()
+    cov = np.zeros((6, 6), dtype=np.float64)
+    rc = load().pfmpe_host_optimise_pose(_dptr(m), m.shape[0], _dptr(k), _dptr(b), b.shape[0],
+                                         c.ctypes.data_as(C.POINTER(C.c_uint32)), c.shape[0],
+                                         C.byref(params) if params is not None else None, _dptr(p), C.byref(row), _dptr(cov))
+    if rc != OK:
+        raise PFError(rc, "host_optimise_pose: bad arguments")
+    return np.frombuffer(bytes(row), dtype=REFINE_ROW_DTYPE)[0].copy(), cov
 
 
 def host_assoc_summary(votes) -> dict:

@@ -94,6 +94,7 @@ struct pfmpe_ctx {
   double* d_cloud = nullptr;       // cloud statistics: result row + per-block partial rows (pfmpe_cloud_stats)
   uint32_t* d_assoc = nullptr;     // association votes: M x B bins + the pair-count bins (pfmpe_assoc_stats)
   uint32_t* d_pairs = nullptr;     // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
+  unsigned char* d_refine = nullptr; // Gauss-Newton refinement scratch (RefineBuf layout, pfmpe_refine_*)
   unsigned char* d_init = nullptr; // initialisation scratch (pfmpe_init.hip), grown on demand
   size_t init_cap = 0;
   unsigned char* d_det = nullptr;  // detector scratch (pfmpe_detect.hip), grown on demand
@@ -435,6 +436,35 @@ inline const uint32_t* prior_owner_ptr(const pfmpe_ctx* c) {
 // against the blob table `table` (device, tbytes, grid header gh) of B blobs, with the context's current model and
 // parameters.  aa.lds_votes is set here.  Not bracketed by the timing events.
 int assoc_launch(pfmpe_ctx* c, int B, const unsigned char* table, size_t tbytes, const GridHdr& gh, AssocArgs aa);
+
+// Gauss-Newton refinement scratch (pfmpe_refine_poses / pfmpe_refine_cloud; pfmpe_refine.hip), one allocation: the
+// call's summary, the model in fp64 (markers, K, the call's blobs), one partial per block, then the rows and
+// covariances of one chunk of hypotheses.  Hypotheses are refined a chunk at a time (the pair rows of a chunk are in
+// d_pairs, kPairsChunk rows at most), so the scratch does not grow with the particle count.
+constexpr int kPairsChunk = 1 << 16;  // pair rows per get_pairs / refine launch (d_pairs: 132 B per particle)
+constexpr int kRefineMaxBlocks = kPairsChunk / kBlock;
+struct RefinePart {
+  int64_t n_with, n_conv, n_kept, n_rev, it_total;
+  int32_t it_max, best_np;
+  double best_rms;
+  int64_t best;  // index within the call, -1: none
+};
+struct RefineBuf {
+  static constexpr size_t kOut = 0;
+  static constexpr size_t kMarkers = 512;
+  static constexpr size_t kK = kMarkers + kMaxMarkers * 3 * sizeof(double);
+  static constexpr size_t kBlobs = kK + 16 * sizeof(double);
+  static size_t part(int max_blobs) { return (kBlobs + (size_t)max_blobs * 2 * sizeof(double) + 255) / 256 * 256; }
+  static size_t rows(int max_blobs) { return part(max_blobs) + kRefineMaxBlocks * sizeof(RefinePart); }
+  static size_t cov(int max_blobs, int cap) { return rows(max_blobs) + (size_t)cap * sizeof(pfmpe_refine_row); }
+  static size_t bytes(int max_blobs, int cap) { return cov(max_blobs, cap) + (size_t)cap * 36 * sizeof(double); }
+};
+static_assert(sizeof(pfmpe_refine_row) == 128 && sizeof(pfmpe_refine_out) <= RefineBuf::kMarkers, "refine layout");
+// One chunk: k_refine over `count` hypotheses (start poses at poses + 12 * i, rows at corr + 2 * kMaxMarkers * i,
+// i = 0 .. count - 1; index within the call base + i), then k_refine_fold of its partials into the summary at
+// d_refine (begun anew when `begin`).  d_refine holds the model and the blobs already.
+int refine_launch(pfmpe_ctx* c, const pfmpe_refine_params& prm, const double* poses, const uint32_t* corr, int64_t base,
+                  int count, int cap, bool begin);
 
 // Batch scratch layout (pfmpe_step_multi), the same in the pinned host image and in HBM: host-supplied blob
 // tables [0, tbytes), then `na` stream descriptors from doff, then the uint16 block -> stream map of `total`

@@ -4,6 +4,7 @@
 // The launch sequences live in pfmpe_ctx.hpp (Seq) and are instantiated per (state type, RNG) in the
 // pfmpe_k_*.hip translation units.
 #include "pfmpe_ctx.hpp"
+#include "pf_gn.hpp"
 
 using namespace pfmpe;
 using namespace pfmpe_impl;
@@ -89,7 +90,7 @@ size_t build_table(const pfmpe_ctx* c, const double* blobs, int B, unsigned char
 void free_all(pfmpe_ctx* c) {
   void* dev[] = {c->d_state[0], c->d_state[1], c->d_w[0], c->d_w[1], c->d_prop[0], c->d_prop[1], c->d_part[0], c->d_part[1],
                  c->d_bscan[0], c->d_bscan[1], c->d_gpart[0], c->d_gpart[1], c->d_gscan, c->d_cpart, c->d_winkey,
-                 c->d_cgroup, c->d_counters, c->d_ctrl, c->d_gen, c->d_cand, c->d_mlpose, c->d_flat, c->d_roi, c->d_cloud, c->d_assoc, c->d_pairs, c->d_gran, c->d_init, c->d_det, c->d_img, c->d_table, c->d_bank, c->d_xfer, c->d_counts,
+                 c->d_cgroup, c->d_counters, c->d_ctrl, c->d_gen, c->d_cand, c->d_mlpose, c->d_flat, c->d_roi, c->d_cloud, c->d_assoc, c->d_pairs, c->d_refine, c->d_gran, c->d_init, c->d_det, c->d_img, c->d_table, c->d_bank, c->d_xfer, c->d_counts,
                  c->d_stamps, c->d_owner[0], c->d_owner[1]};
   for (void* p : dev)
     if (p) (void)hipFree(p);
@@ -879,9 +880,6 @@ int pfmpe_host_assoc_summary(const uint32_t* votes, int M, int B, pfmpe_assoc_ou
 }
 
 namespace {
-// pair rows per get_pairs launch (the chunk buffer d_pairs: 132 B per particle)
-constexpr int kPairsChunk = 1 << 16;
-
 // The argument and state checks shared by pfmpe_assoc_stats / pfmpe_get_pairs, then the call's blob table built
 // into d_table (every frame that reads d_table writes it first) and, for the propagated set, the kept set
 // regenerated into d_xfer (written and read inside one blocking call by every user).
@@ -989,6 +987,176 @@ int pfmpe_get_pairs(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, int64_t f
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RET(harvest_timing(c));
+  return PFMPE_OK;
+}
+
+// ---- Gauss-Newton refinement (optimisePose, PE:1805-2009): pf_gn.hpp on the host here, k_refine in pfmpe_refine.hip
+void pfmpe_default_refine_params(pfmpe_refine_params* p) {
+  if (!p) return;
+  p->max_iter = 500;
+  p->revert_on_divergence = 1;
+  p->converged = 1e-13;
+}
+
+namespace {
+bool refine_params_ok(const pfmpe_refine_params& p) {
+  return p.max_iter >= 1 && p.max_iter <= 10000 && p.converged >= 0.0;  // (a NaN fails the comparison)
+}
+// the rows' indices: LED 1 .. M beside a blob, never above M; blob 0 .. B
+bool refine_corr_ok(const uint32_t* corr, size_t n_rows, int M, int B) {
+  for (size_t j = 0; j < n_rows; ++j) {
+    const uint32_t led = corr[2 * j], blob = corr[2 * j + 1];
+    if (led > (uint32_t)M || blob > (uint32_t)B || (blob != 0u && led == 0u)) return false;
+  }
+  return true;
+}
+bool refine_poses_finite(const double* poses, size_t n) {
+  for (size_t q = 0; q < 12 * n; ++q)
+    if (!std::isfinite(poses[q])) return false;
+  return true;
+}
+
+// the scratch, the model and the call's blobs in fp64 (enqueued on the stream; `stage` must outlive the copy)
+int refine_stage(pfmpe_ctx* c, const double* blobs, int B, int cap, std::vector<double>& stage) {
+  if (!c->d_refine) HIPCHK(c, hipMalloc((void**)&c->d_refine, RefineBuf::bytes(c->max_blobs, cap)));
+  const size_t words = (RefineBuf::kBlobs - RefineBuf::kMarkers) / sizeof(double) + 2 * (size_t)B;
+  stage.assign(words, 0.0);
+  std::memcpy(stage.data(), c->markers, sizeof(c->markers));
+  std::memcpy(stage.data() + (RefineBuf::kK - RefineBuf::kMarkers) / sizeof(double), c->K, sizeof(c->K));
+  if (B > 0) std::memcpy(stage.data() + (RefineBuf::kBlobs - RefineBuf::kMarkers) / sizeof(double), blobs, 2 * (size_t)B * sizeof(double));
+  HIPCHK(c, hipMemcpyAsync(c->d_refine + RefineBuf::kMarkers, stage.data(), words * sizeof(double), hipMemcpyHostToDevice,
+                           c->stream));
+  return PFMPE_OK;
+}
+// a chunk's rows and covariances, hypotheses lo .. hi - 1 of the chunk, to the caller's arrays at index `at`
+int refine_fetch(pfmpe_ctx* c, int cap, int lo, int hi, pfmpe_refine_row* rows, double* cov, int64_t at) {
+  if (hi <= lo) return PFMPE_OK;
+  const unsigned char* d = c->d_refine;
+  if (rows)
+    HIPCHK(c, hipMemcpyAsync(rows + at, d + RefineBuf::rows(c->max_blobs) + (size_t)lo * sizeof(pfmpe_refine_row),
+                             (size_t)(hi - lo) * sizeof(pfmpe_refine_row), hipMemcpyDeviceToHost, c->stream));
+  if (cov)
+    HIPCHK(c, hipMemcpyAsync(cov + 36 * at, d + RefineBuf::cov(c->max_blobs, cap) + (size_t)lo * 36 * sizeof(double),
+                             (size_t)(hi - lo) * 36 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return PFMPE_OK;
+}
+int refine_finish(pfmpe_ctx* c, int64_t n, pfmpe_refine_out* out) {
+  HIPCHK(c, hipMemcpyAsync(out, c->d_refine + RefineBuf::kOut, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  RET(harvest_timing(c));  // (a propagated call's regeneration is bracketed like the particle read-back's)
+  out->n = n;
+  return PFMPE_OK;
+}
+}  // namespace
+
+int pfmpe_refine_poses(pfmpe_ctx* c, const pfmpe_assoc_in* in, const pfmpe_refine_params* params, const double* poses,
+                       const uint32_t* corr, int32_t K, pfmpe_refine_out* out, pfmpe_refine_row* rows, double* cov) {
+  if (!c) return PFMPE_E_ARG;
+  pfmpe_refine_params prm;
+  pfmpe_default_refine_params(&prm);
+  if (params) prm = *params;
+  if (!out || !in || K < 0 || (K > 0 && (!poses || !corr))) return fail(c, PFMPE_E_ARG, "refine_poses: bad arguments");
+  if (!refine_params_ok(prm)) return fail(c, PFMPE_E_ARG, "refine_poses: bad parameters");
+  if (in->B < 0) return fail(c, PFMPE_E_ARG, "refine_poses: B < 0");
+  const double* blobs = in->blobs;
+  int B = in->B;
+  if (in->bank_frame >= 0) {
+    if (c->bank_offsets.empty() || in->bank_frame >= (int)c->bank_offsets.size() - 1)
+      return fail(c, PFMPE_E_ARG, "refine_poses: bank_frame out of range");
+    B = c->bank_offsets[in->bank_frame + 1] - c->bank_offsets[in->bank_frame];
+    blobs = c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame];
+  } else if (B > 0 && !blobs) {
+    return fail(c, PFMPE_E_ARG, "refine_poses: null blobs");
+  }
+  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, "refine_poses: B exceeds max_blobs");
+  if (K > c->max_particles) return fail(c, PFMPE_E_CAP, "refine_poses: K exceeds max_particles");
+  if (!c->has_model) return fail(c, PFMPE_E_STATE, "refine_poses: set_model first");
+  if (K > 0 && !refine_corr_ok(corr, (size_t)K * kMaxMarkers, c->M, B))
+    return fail(c, PFMPE_E_ARG, "refine_poses: LED or blob index out of range");
+  if (K > 0 && !refine_poses_finite(poses, (size_t)K)) return fail(c, PFMPE_E_ARG, "refine_poses: non-finite start pose");
+  RET(set_device(c));
+  RET(ensure_xfer(c));
+  constexpr size_t kRow = 2 * kMaxMarkers;
+  const int cap = std::min(c->max_particles, kPairsChunk);
+  if (!c->d_pairs) HIPCHK(c, hipMalloc((void**)&c->d_pairs, (size_t)cap * (kRow + 1) * sizeof(uint32_t)));
+  std::vector<double> stage;
+  RET(refine_stage(c, blobs, B, cap, stage));
+  // d_xfer is written and read inside one blocking call by every user
+  if (K > 0) HIPCHK(c, hipMemcpyAsync(c->d_xfer, poses, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  int64_t done = 0;
+  do {  // (K = 0: one empty chunk writes the empty summary)
+    const int n = (int)std::min<int64_t>(cap, (int64_t)K - done);
+    if (n > 0)
+      HIPCHK(c, hipMemcpyAsync(c->d_pairs, corr + (size_t)done * kRow, (size_t)n * kRow * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, c->stream));
+    RET(refine_launch(c, prm, c->d_xfer + 12 * done, c->d_pairs, done, n, cap, done == 0));
+    RET(refine_fetch(c, cap, 0, n, rows, cov, done));
+    done += n;
+  } while (done < K);
+  return refine_finish(c, K, out);
+}
+
+int pfmpe_refine_cloud(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, const pfmpe_refine_params* params,
+                       int64_t first, int32_t count, pfmpe_refine_out* out, pfmpe_refine_row* rows, double* cov) {
+  if (!c) return PFMPE_E_ARG;
+  pfmpe_refine_params prm;
+  pfmpe_default_refine_params(&prm);
+  if (params) prm = *params;
+  if (!out || first < 0 || count < 0) return fail(c, PFMPE_E_ARG, "refine_cloud: null out or bad range");
+  if (c->has_prior && first + (int64_t)count > (int64_t)c->N)
+    return fail(c, PFMPE_E_ARG, "refine_cloud: first + count exceeds the particle count");
+  if (!refine_params_ok(prm)) return fail(c, PFMPE_E_ARG, "refine_cloud: bad parameters");
+  int B = 0;
+  size_t tbytes = 0;
+  GridHdr gh{};
+  AssocArgs aa{};
+  RET(assoc_prepare(c, "refine_cloud", which, in, &B, &tbytes, &gh, &aa));
+  const double* blobs = in->bank_frame >= 0 ? c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame] : in->blobs;
+  const int N = c->N;
+  // the start poses as get_particles delivers them: the propagated set is in d_xfer already (assoc_prepare)
+  if (which == PFMPE_ASSOC_POSTERIOR) {
+    RET(ensure_xfer(c));
+    if (c->state_dtype == PFMPE_STATE_F64)
+      launch_export<double, double>(c, N, c->anchor[c->prior_idx]);
+    else if (c->state_dtype == PFMPE_STATE_F16)
+      launch_export<float, __half>(c, N, c->anchor[c->prior_idx]);
+    else
+      launch_export<float, float>(c, N, c->anchor[c->prior_idx]);
+    HIPCHK(c, hipGetLastError());
+  }
+  constexpr size_t kRow = 2 * kMaxMarkers;
+  const int cap = std::min(c->max_particles, kPairsChunk);
+  if (!c->d_pairs) HIPCHK(c, hipMalloc((void**)&c->d_pairs, (size_t)cap * (kRow + 1) * sizeof(uint32_t)));
+  std::vector<double> stage;
+  RET(refine_stage(c, blobs, B, cap, stage));
+  aa.corr = c->d_pairs;
+  aa.n_corr = (int32_t*)(c->d_pairs + (size_t)cap * kRow);
+  for (int64_t done = 0; done < N; done += cap) {
+    const int n = (int)std::min<int64_t>(cap, (int64_t)N - done);
+    aa.first = (int32_t)done;
+    aa.count = n;
+    RET(assoc_launch(c, B, c->d_table, tbytes, gh, aa));
+    RET(refine_launch(c, prm, c->d_xfer + 12 * done, c->d_pairs, done, n, cap, done == 0));
+    const int64_t lo = std::max<int64_t>(first, done), hi = std::min<int64_t>(first + count, done + n);
+    RET(refine_fetch(c, cap, (int)(lo - done), (int)(hi - done), rows, cov, lo - first));
+  }
+  return refine_finish(c, N, out);
+}
+
+int pfmpe_host_optimise_pose(const double* markers_xyz, int M, const double* K, const double* blobs, int B,
+                             const uint32_t* corr, int n_rows, const pfmpe_refine_params* params, const double* pose12,
+                             pfmpe_refine_row* row, double* cov36) {
+  pfmpe_refine_params prm;
+  pfmpe_default_refine_params(&prm);
+  if (params) prm = *params;
+  if (!markers_xyz || !K || !pose12 || !row || M < 1 || B < 0 || n_rows < 0 || (B > 0 && !blobs) || (n_rows > 0 && !corr))
+    return PFMPE_E_ARG;
+  if (!refine_params_ok(prm) || !refine_corr_ok(corr, (size_t)n_rows, M, B) || !refine_poses_finite(pose12, 1))
+    return PFMPE_E_ARG;
+  double cov[36];
+  gn_optimise(markers_xyz, K, blobs, corr, n_rows, prm.max_iter, prm.revert_on_divergence ? 1 : 0, prm.converged, pose12,
+              *row, cov);
+  if (cov36) std::memcpy(cov36, cov, sizeof(cov));
   return PFMPE_OK;
 }
 

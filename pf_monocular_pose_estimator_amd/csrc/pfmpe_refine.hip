@@ -1,0 +1,179 @@
+// pfmpe_refine.hip — k_refine / k_refine_fold (pfmpe_refine_poses / pfmpe_refine_cloud) and their launch: Gauss-Newton
+// (pf_gn.hpp) of one hypothesis per lane, fp64 for every state type, and the call's summary.  A TU of its own so it
+// builds beside the others.
+#include "pfmpe_ctx.hpp"
+#include "pf_gn.hpp"
+
+namespace pfmpe_impl {
+using namespace pfmpe;
+
+namespace {
+constexpr int kWave = 64;
+struct RefineArgs {
+  const double* poses;     // start poses of the chunk, 12 doubles each
+  const uint32_t* corr;    // pair rows of the chunk, 2 * kMaxMarkers words each
+  const double* markers;   // M x 3
+  const double* K;         // 3 x 3
+  const double* blobs;     // B x 2
+  pfmpe_refine_row* rows;  // the chunk's rows
+  double* cov;             // the chunk's covariances, 36 doubles each
+  RefinePart* part;        // one partial per block
+  int64_t base;            // index within the call of the chunk's first hypothesis
+  int32_t count, max_iter, revert, pad;
+  double converged;
+};
+
+__device__ inline void part_merge(RefinePart& a, const RefinePart& b) {
+  a.n_with += b.n_with;
+  a.n_conv += b.n_conv;
+  a.n_kept += b.n_kept;
+  a.n_rev += b.n_rev;
+  a.it_total += b.it_total;
+  a.it_max = b.it_max > a.it_max ? b.it_max : a.it_max;
+  if (gn_better(b.best_np, b.best_rms, b.best, a.best_np, a.best_rms, a.best)) {
+    a.best_np = b.best_np;
+    a.best_rms = b.best_rms;
+    a.best = b.best;
+  }
+}
+// every lane gets the wave's merged partial (sums of integers and a total order: the tree's shape does not matter)
+__device__ inline void part_wave_merge(RefinePart& p) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) {
+    RefinePart o;
+    o.n_with = __shfl_xor((long long)p.n_with, m);
+    o.n_conv = __shfl_xor((long long)p.n_conv, m);
+    o.n_kept = __shfl_xor((long long)p.n_kept, m);
+    o.n_rev = __shfl_xor((long long)p.n_rev, m);
+    o.it_total = __shfl_xor((long long)p.it_total, m);
+    o.it_max = __shfl_xor(p.it_max, m);
+    o.best_np = __shfl_xor(p.best_np, m);
+    o.best_rms = __shfl_xor(p.best_rms, m);
+    o.best = __shfl_xor((long long)p.best, m);
+    part_merge(p, o);
+  }
+}
+__device__ inline RefinePart part_zero() {
+  RefinePart p;
+  p.n_with = p.n_conv = p.n_kept = p.n_rev = p.it_total = 0;
+  p.it_max = 0;
+  p.best_np = 0;
+  p.best_rms = 0.0;
+  p.best = -1;
+  return p;
+}
+
+// One lane per hypothesis, grid-stride.  Lanes of a wave stop at different iterations: the wave runs as long as its
+// slowest lane (no compaction).  The row and the covariance go to the chunk's buffers; the lane's counts and best key
+// are merged per wave, then per block in wave order through LDS, into one partial per block.  No atomics, no waits
+// on other blocks: k_refine_fold is a second launch.
+__global__ __launch_bounds__(kBlock) void k_refine(const RefineArgs ra) {
+  __shared__ RefinePart sh[kWaves];
+  RefinePart acc = part_zero();
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < ra.count; i += stride) {
+    pfmpe_refine_row r;
+    gn_optimise(ra.markers, ra.K, ra.blobs, ra.corr + (size_t)i * (2 * kMaxMarkers), kMaxMarkers, ra.max_iter,
+                ra.revert, ra.converged, ra.poses + 12 * (size_t)i, r, ra.cov + 36 * (size_t)i);
+    ra.rows[i] = r;
+    RefinePart h = part_zero();
+    h.n_with = r.n_pairs > 0 ? 1 : 0;
+    h.n_conv = r.status == PFMPE_REFINE_CONVERGED ? 1 : 0;
+    h.n_kept = r.status == PFMPE_REFINE_CAP_KEPT ? 1 : 0;
+    h.n_rev = r.status == PFMPE_REFINE_CAP_REVERTED ? 1 : 0;
+    h.it_total = r.iters;
+    h.it_max = r.iters;
+    if (gn_eligible(r)) {
+      h.best_np = r.n_pairs;
+      h.best_rms = r.rms_after;
+      h.best = ra.base + i;
+    }
+    part_merge(acc, h);
+  }
+  part_wave_merge(acc);
+  if (lane_id() == 0) sh[wave_id()] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; ++w) part_merge(acc, sh[w]);
+    ra.part[blockIdx.x] = acc;
+  }
+}
+
+// One wave: the chunk's partials merged (lane l takes partials l, l + 64, ...), added to the call's summary, and the
+// chunk's best row and covariance copied into it when they beat the summary's.
+__global__ __launch_bounds__(kWave) void k_refine_fold(const RefinePart* __restrict__ part, int nblk,
+                                                      const pfmpe_refine_row* __restrict__ rows,
+                                                      const double* __restrict__ cov, int64_t base, int begin,
+                                                      pfmpe_refine_out* __restrict__ out) {
+  RefinePart p = part_zero();
+  for (int b = threadIdx.x; b < nblk; b += kWave) part_merge(p, part[b]);
+  part_wave_merge(p);
+  // the summary so far, read by every lane before lane 0 rewrites it
+  RefinePart s = part_zero();
+  if (!begin) {
+    s.n_with = out->n_with_pairs;
+    s.n_conv = out->n_converged;
+    s.n_kept = out->n_cap_kept;
+    s.n_rev = out->n_cap_reverted;
+    s.it_total = out->iters_total;
+    s.it_max = out->iters_max;
+    s.best = out->best;
+    s.best_np = out->best_row.n_pairs;
+    s.best_rms = out->best_row.rms_after;
+  }
+  const bool take = gn_better(p.best_np, p.best_rms, p.best, s.best_np, s.best_rms, s.best);
+  part_merge(s, p);
+  if (threadIdx.x == 0) {
+    out->n = 0;  // (the host's)
+    out->n_with_pairs = s.n_with;
+    out->n_converged = s.n_conv;
+    out->n_cap_kept = s.n_kept;
+    out->n_cap_reverted = s.n_rev;
+    out->iters_total = s.it_total;
+    out->iters_max = s.it_max;
+    out->pad = 0;
+    out->best = s.best;
+  }
+  constexpr int kRowWords = (int)(sizeof(pfmpe_refine_row) / sizeof(double));
+  double* brow = (double*)&out->best_row;
+  const int q = threadIdx.x;
+  if (take) {
+    const int64_t i = p.best - base;
+    if (q < kRowWords) brow[q] = ((const double*)(rows + i))[q];
+    else if (q < kRowWords + 36) out->best_cov[q - kRowWords] = cov[36 * i + (q - kRowWords)];
+  } else if (begin) {
+    if (q < kRowWords) brow[q] = 0.0;
+    else if (q < kRowWords + 36) out->best_cov[q - kRowWords] = 0.0;
+  }
+}
+static_assert(sizeof(pfmpe_refine_row) / sizeof(double) + 36 <= kWave, "k_refine_fold copies a word per lane");
+}  // namespace
+
+int refine_launch(pfmpe_ctx* c, const pfmpe_refine_params& prm, const double* poses, const uint32_t* corr, int64_t base,
+                  int count, int cap, bool begin) {
+  unsigned char* d = c->d_refine;
+  RefineArgs ra{};
+  ra.poses = poses;
+  ra.corr = corr;
+  ra.markers = (const double*)(d + RefineBuf::kMarkers);
+  ra.K = (const double*)(d + RefineBuf::kK);
+  ra.blobs = (const double*)(d + RefineBuf::kBlobs);
+  ra.rows = (pfmpe_refine_row*)(d + RefineBuf::rows(c->max_blobs));
+  ra.cov = (double*)(d + RefineBuf::cov(c->max_blobs, cap));
+  ra.part = (RefinePart*)(d + RefineBuf::part(c->max_blobs));
+  ra.base = base;
+  ra.count = count;
+  ra.max_iter = prm.max_iter;
+  ra.revert = prm.revert_on_divergence ? 1 : 0;
+  ra.converged = prm.converged;
+  int nblk = (count + kBlock - 1) / kBlock;
+  nblk = nblk < kRefineMaxBlocks ? nblk : kRefineMaxBlocks;
+  if (nblk > 0) hipLaunchKernelGGL(k_refine, dim3(nblk), dim3(kBlock), 0, c->stream, ra);
+  hipLaunchKernelGGL(k_refine_fold, dim3(1), dim3(kWave), 0, c->stream, (const RefinePart*)ra.part, nblk,
+                     (const pfmpe_refine_row*)ra.rows, (const double*)ra.cov, base, begin ? 1 : 0,
+                     (pfmpe_refine_out*)(d + RefineBuf::kOut));
+  HIPCHK(c, hipGetLastError());
+  return PFMPE_OK;
+}
+
+}  // namespace pfmpe_impl
