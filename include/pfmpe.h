@@ -258,6 +258,31 @@ int pfmpe_find_leds(pfmpe_ctx* ctx, const uint8_t* image, int width, int height,
                     const pfmpe_detect_params* params, double* blobs, float* distorted, int max_out,
                     pfmpe_detect_out* out);
 
+#define PFMPE_DETECT_MAX_ROIS 64
+
+/* R ROIs of one image, one launch sequence, one synchronise: the per-object findLeds calls of a multi-object
+ * tracker (the numUAV loop, PE:89, PE:442) and their retries on an enlarged ROI (PE:452-463) as one batch.
+ * params[r] is a complete pfmpe_detect_params with its own ROI, threshold, sigma, area limits, D, active_markers;
+ * ROIs may overlap, repeat, or be the whole image (roi_w / roi_h < 0).  blobs: R x max_out x 2 doubles,
+ * distorted: R x max_out x 2 floats (may be NULL), ROI r at offset r * 2 * max_out; out: R records.
+ * image = NULL uses the staged image.  ROI r's rows and out[r] are what the single-ROI call returns for params[r]
+ * (same detections, same order, same bits, while overflow is 0): out[r].n counts all detections,
+ * min(n, max_out, PFMPE_MAX_BLOBS) rows are written and nothing else of the arrays is touched.  Everything is
+ * checked before anything is staged or launched and out is untouched on an error: PFMPE_E_ARG (R < 1, a NULL
+ * pointer, max_out < 0, an ROI outside the image or gaussian_sigma outside (0, 5]: the error text names the
+ * entry, "find_leds_multi: roi <r>: ..."), PFMPE_E_CAP (R > PFMPE_DETECT_MAX_ROIS), PFMPE_E_STATE (no model, or
+ * image = NULL without a staged image of that size).  Blocking, on the context's stream; with PFMPE_OPT_TIMING
+ * the sequence is one PFMPE_K_DETECT bracket. */
+int pfmpe_find_leds_multi(pfmpe_ctx* ctx, const uint8_t* image, int width, int height, int pitch,
+                          const pfmpe_detect_params* params, int R, double* blobs, float* distorted,
+                          int max_out, pfmpe_detect_out* out);
+
+/* host-only: the reference's ROI enlargement (PE:429-432 with margin = ROI_distVal, PE:454-457 with margin = 20):
+ *   x' = max(x - margin, 0), y' = max(y - margin, 0),
+ *   w' = min(w + 2 margin, image_w - x'), h' = min(h + 2 margin, image_h - y')   (note: x', y', as the reference)
+ * roi / grown: x, y, w, h.  PFMPE_E_ARG for a NULL pointer, margin < 0 or an image side < 1. */
+int pfmpe_host_grow_roi(const int32_t roi[4], int32_t margin, int32_t image_w, int32_t image_h, int32_t grown[4]);
+
 /* ---------------------------------------- configuration files and recorded streams (§8f row 3) */
 /* Host-only (no GPU): pfmpe_io.cpp.  The reference reads these through ROS (rosparam / getParam /
  * dynamic_reconfigure, pf_mpe/src/monocular_pose_estimator.cpp:81-126, 479-527) and the CameraInfo topic.

@@ -17,6 +17,7 @@ from ._capi import (  # noqa: F401
     ASSOC_PROPAGATED, ASSOC_POSTERIOR, DIAG_ASSOC_DIRECT, AssocIn, AssocOut, host_assoc_summary,
     REFINE_NO_PAIRS, REFINE_CONVERGED, REFINE_CAP_KEPT, REFINE_CAP_REVERTED, REFINE_ROW_DTYPE, RefineParams, RefineRow,
     RefineOut, default_refine_params, host_optimise_pose,
+    DETECT_MAX_ROIS, DetectParams, DetectOut, host_grow_roi,
 )
 
 __all__ = [

@@ -52,7 +52,9 @@ EXPORTED_SYMBOLS = (
     "pfmpe_cloud_stats", "pfmpe_host_pose_twist",
     "pfmpe_assoc_stats", "pfmpe_get_pairs", "pfmpe_host_assoc_summary",
     "pfmpe_default_refine_params", "pfmpe_refine_poses", "pfmpe_refine_cloud", "pfmpe_host_optimise_pose",
+    "pfmpe_find_leds_multi", "pfmpe_host_grow_roi",
 )
+DETECT_MAX_ROIS = 64
 
 
 class Params(C.Structure):
@@ -275,6 +277,9 @@ def load() -> C.CDLL:
         "pfmpe_stage_image": (I, [P, C.POINTER(C.c_uint8), I, I, I]),
         "pfmpe_find_leds": (I, [P, C.POINTER(C.c_uint8), I, I, I, C.POINTER(DetectParams), dp,
                                 C.POINTER(C.c_float), I, C.POINTER(DetectOut)]),
+        "pfmpe_find_leds_multi": (I, [P, C.POINTER(C.c_uint8), I, I, I, C.POINTER(DetectParams), I, dp,
+                                      C.POINTER(C.c_float), I, C.POINTER(DetectOut)]),
+        "pfmpe_host_grow_roi": (I, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -512,6 +517,42 @@ class Engine:
         n = min(out.n, max_out)
         return blobs[:n].copy(), dist[:n].copy(), {"n": out.n, "n_components": out.n_components,
                                                     "overflow": out.overflow}
+
+    def find_leds_multi(self, image=None, rois=(), D=None, params=None, max_out=MAX_BLOBS):
+        """pfmpe_find_leds_multi: the ROIs `rois` ((x, y, w, h), or None for the whole image) of one image in one
+        launch sequence.  params: a dict of DetectParams fields for every ROI, or a list with one dict per ROI.
+        Returns one (undistorted, distorted, info) per ROI, each as find_leds returns it."""
+        R = len(rois)
+        per_roi = params if isinstance(params, (list, tuple)) else [params or {}] * R
+        if len(per_roi) != R:
+            raise ValueError("find_leds_multi: one params dict per ROI")
+        ps = (DetectParams * max(R, 1))()
+        for p, roi, kw in zip(ps, rois, per_roi):
+            self.lib.pfmpe_default_detect_params(C.byref(p))
+            if D is not None:
+                p.D[:] = list(np.asarray(D, np.float64).reshape(5))
+            if roi is not None:
+                p.roi_x, p.roi_y, p.roi_w, p.roi_h = [int(v) for v in roi]
+            for k, v in (kw or {}).items():
+                setattr(p, k, v)
+        blobs = np.zeros((max(R, 1), max(max_out, 1), 2))
+        dist = np.zeros((max(R, 1), max(max_out, 1), 2), dtype=np.float32)
+        outs = (DetectOut * max(R, 1))()
+        if image is not None:
+            img = np.ascontiguousarray(image, dtype=np.uint8)
+            ip, (h, w), pitch = img.ctypes.data_as(C.POINTER(C.c_uint8)), img.shape, img.strides[0]
+        else:
+            ip, (h, w) = C.POINTER(C.c_uint8)(), getattr(self, "_img_shape", (0, 0))
+            pitch = w
+        # the C arrays' ROI stride is 2 * max_out; the numpy rows are max(max_out, 1) wide, the same unless max_out = 0
+        self._chk(self.lib.pfmpe_find_leds_multi(self.ctx, ip, w, h, pitch, ps, R, _dptr(blobs),
+                                                 dist.ctypes.data_as(C.POINTER(C.c_float)), max_out, outs))
+        res = []
+        for r in range(R):
+            n = min(outs[r].n, max_out)
+            res.append((blobs[r, :n].copy(), dist[r, :n].copy(),
+                        {"n": outs[r].n, "n_components": outs[r].n_components, "overflow": outs[r].overflow}))
+        return res
 
     def stage_blob_stream(self, path) -> int:
         """Stage every frame of a PFMB stream file in the device blob bank; returns the frame count."""
@@ -782,6 +823,17 @@ def host_assoc_summary(votes) -> dict:
     d = out.as_dict()
     del d["n_any"], d["npairs_hist"]
     return d
+
+
+def host_grow_roi(roi, margin: int, image_w: int, image_h: int) -> tuple:
+    """The reference's ROI enlargement (PE:429-432 / PE:454-457, pfmpe_host_grow_roi): (x, y, w, h) grown by
+    `margin` on every side and clipped to the image as the reference clips it."""
+    src = (C.c_int32 * 4)(*[int(v) for v in roi])
+    dst = (C.c_int32 * 4)()
+    rc = load().pfmpe_host_grow_roi(src, int(margin), int(image_w), int(image_h), dst)
+    if rc != OK:
+        raise PFError(rc, "host_grow_roi: margin < 0 or an image side < 1")
+    return tuple(dst)
 
 
 def host_philox(ctr, key):

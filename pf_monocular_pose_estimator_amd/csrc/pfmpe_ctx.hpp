@@ -103,6 +103,13 @@ struct pfmpe_ctx {
   size_t img_cap = 0;
   int img_w = 0, img_h = 0, img_pitch = 0;
   void* h_det = nullptr;           // detector output record (pinned, host-mapped)
+  // pfmpe_find_leds_multi: the batch scratch (counters, batch head + descriptors, work list, then every ROI's
+  // regions; grown on demand), the pinned image of the head + descriptors, and R pinned, host-mapped output records
+  unsigned char* d_detm = nullptr;
+  size_t detm_cap = 0;
+  unsigned char* h_detm = nullptr;
+  void* h_detm_out = nullptr;
+  int detm_out_cap = 0;            // records in h_detm_out
   int num_cu = 0;
   bool coop = false;               // device supports cooperative launches
   int fused = 2;                   // PFMPE_OPT_FUSED: 2 flat one-launch (k_frame2), 1 tree (k_frame), 0 two launches

@@ -19,6 +19,9 @@
 //                  the centre + ROI offset as float, cvUndistortPoints (5 iterations, P = K)
 // The host orders the accepted detections as findContours returns them (reverse discovery = descending
 // root index) and returns image_points_ (undistorted px) plus the distorted centres.
+//
+// pfmpe_find_leds_multi runs the same stages over R ROIs of one image in one launch sequence (k_detm_*: flat
+// grids over all ROIs' tiles, pixels and components, one descriptor per ROI); the stage bodies are shared.
 #include "pfmpe_ctx.hpp"
 
 using namespace pfmpe;
@@ -57,13 +60,16 @@ __device__ __forceinline__ int refl101(int p, int len) {
   return p;
 }
 
-__global__ __launch_bounds__(kDetTile* kDetTile) void k_det_mask(const DetArgs a, const uint8_t* __restrict__ img,
-                                                                  uint8_t* __restrict__ mask) {
+// The stage bodies below are shared by the single-ROI kernels (k_det_*: `a` is the kernel argument) and their
+// batched forms (k_detm_*: `a` is the ROI's descriptor in device memory, the buffers are that ROI's); `a` is
+// wave-uniform either way.
+// one 16 x 16 tile at (x0, y0) of the ROI; the whole block
+__device__ __forceinline__ void det_mask_tile(const DetArgs& a, const uint8_t* __restrict__ img,
+                                              uint8_t* __restrict__ mask, const int x0, const int y0) {
   constexpr int T = kDetTile, HW = T + 2 * kDetMaxRadius;
   __shared__ int tb[HW][HW];    // thresholded tile + halo (rows, cols)
   __shared__ int rowp[HW][T];   // row pass
   const int r = a.radius, n = 2 * r + 1, span = T + 2 * r;
-  const int x0 = blockIdx.x * T, y0 = blockIdx.y * T;
   for (int i = threadIdx.x; i < span * span; i += blockDim.x) {
     const int ty = i / span, tx = i - ty * span;
     const int gy = refl101(y0 + ty - r, a.H), gx = refl101(x0 + tx - r, a.W);
@@ -87,6 +93,10 @@ __global__ __launch_bounds__(kDetTile* kDetTile) void k_det_mask(const DetArgs a
   const bool frame = x == 0 || y == 0 || x == a.W - 1 || y == a.H - 1;
   mask[(int64_t)y * a.W + x] = (v > 0 && !frame) ? 1 : 0;
 }
+__global__ __launch_bounds__(kDetTile* kDetTile) void k_det_mask(const DetArgs a, const uint8_t* __restrict__ img,
+                                                                  uint8_t* __restrict__ mask) {
+  det_mask_tile(a, img, mask, blockIdx.x * kDetTile, blockIdx.y * kDetTile);
+}
 
 // Labelling, tile-local first: a 32 x 32 tile (+1 halo) of the mask in LDS gives each pixel its 8-neighbour
 // bit mask (bit s = direction s of icvFetchContour's table: 0 +x, 1 (+x,-y), 2 -y, 3 (-x,-y), 4 -x,
@@ -99,11 +109,12 @@ __device__ __forceinline__ int lfind(const int* L, int i) {
   return i;
 }
 constexpr int kLabelBlock = 1024;
-__global__ __launch_bounds__(kLabelBlock) void k_det_label(const DetArgs a, const uint8_t* __restrict__ mask,
-                                                   uint8_t* __restrict__ nbr, int* __restrict__ label) {
+// one 32 x 32 tile at (x0, y0) of the ROI; the whole block (kLabelBlock threads)
+__device__ __forceinline__ void det_label_tile(const DetArgs& a, const uint8_t* __restrict__ mask,
+                                               uint8_t* __restrict__ nbr, int* __restrict__ label, const int x0,
+                                               const int y0) {
   __shared__ uint8_t m[kLT + 2][kLT + 2];
   __shared__ int L[kLT * kLT];
-  const int x0 = blockIdx.x * kLT, y0 = blockIdx.y * kLT;
   {  // branch-free: clamped in-bounds addresses, all loads in flight, then the selects
     constexpr int kN = ((kLT + 2) * (kLT + 2) + kLabelBlock - 1) / kLabelBlock;
     uint32_t v[kN];
@@ -171,6 +182,10 @@ __global__ __launch_bounds__(kLabelBlock) void k_det_label(const DetArgs a, cons
     label[g] = (y0 + r / kLT) * a.W + (x0 + r % kLT);
   }
 }
+__global__ __launch_bounds__(kLabelBlock) void k_det_label(const DetArgs a, const uint8_t* __restrict__ mask,
+                                                   uint8_t* __restrict__ nbr, int* __restrict__ label) {
+  det_label_tile(a, mask, nbr, label, blockIdx.x * kLT, blockIdx.y * kLT);
+}
 
 __device__ __forceinline__ int ld_label(const int* L, int i) {
   return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -196,8 +211,8 @@ __device__ __forceinline__ void unite(int* L, int a, int b) {
 }
 
 // the links that cross a tile border (the left column's W / NW, the top row's NW / N / NE)
-__global__ void k_det_merge(const DetArgs a, const uint8_t* __restrict__ nbr, int* __restrict__ label) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void det_merge_pixel(const DetArgs& a, const uint8_t* __restrict__ nbr,
+                                                int* __restrict__ label, const int64_t i) {
   if (i >= (int64_t)a.W * a.H) return;
   const int W = a.W;
   const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
@@ -209,6 +224,9 @@ __global__ void k_det_merge(const DetArgs a, const uint8_t* __restrict__ nbr, in
   if ((left || top) && (b & (1u << 3))) unite(label, (int)i, (int)i - W - 1);
   if (top && (b & (1u << 2))) unite(label, (int)i, (int)i - W);
   if ((top || right) && (b & (1u << 1))) unite(label, (int)i, (int)i - W + 1);
+}
+__global__ void k_det_merge(const DetArgs a, const uint8_t* __restrict__ nbr, int* __restrict__ label) {
+  det_merge_pixel(a, nbr, label, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ void k_det_roots(const DetArgs a, const uint8_t* __restrict__ mask, int* __restrict__ label,
@@ -228,14 +246,10 @@ __global__ void k_det_roots(const DetArgs a, const uint8_t* __restrict__ mask, i
 // y0 .. y0+63 from the root down, columns x0-31 .. x0+32) in LDS, then lane 0 follows the border there
 // (a point outside the window falls back to the global masks).
 constexpr int kWin = 64;
-__global__ __launch_bounds__(64) void k_det_trace(const DetArgs a, const uint8_t* __restrict__ nbr,
-                                                  const int* __restrict__ count, const int* __restrict__ roots,
-                                                  DetRecord* __restrict__ rec) {
-  __shared__ uint8_t win[kWin][kWin];
-  const int nc = min(*count, kDetMaxComponents);
-  for (int slot = blockIdx.x; slot < nc; slot += gridDim.x) {
-  __syncthreads();  // the previous slot's window reads are done
-  const int root = roots[slot];
+// the component whose raster-first pixel is `root`: its record goes to *dst; one wave, `win` its LDS window
+__device__ __forceinline__ void det_trace_component(const DetArgs& a, const uint8_t* __restrict__ nbr, const int root,
+                                                    uint8_t (*win)[kWin], DetRecord* __restrict__ dst) {
+  __syncthreads();  // the previous component's window reads are done
   const int W = a.W;
   const int x0 = root % W, y0 = root / W;
   const int wx = x0 - kWin / 2 + 1, wy = y0;
@@ -362,9 +376,15 @@ __global__ __launch_bounds__(64) void k_det_trace(const DetArgs a, const uint8_t
     o.ux = (double)(float)(xx * ww);
     o.uy = (double)(float)(yy * ww);
   }
-  rec[slot] = o;
+  *dst = o;
   }  // lane 0
-  }  // slots
+}
+__global__ __launch_bounds__(64) void k_det_trace(const DetArgs a, const uint8_t* __restrict__ nbr,
+                                                  const int* __restrict__ count, const int* __restrict__ roots,
+                                                  DetRecord* __restrict__ rec) {
+  __shared__ uint8_t win[kWin][kWin];
+  const int nc = min(*count, kDetMaxComponents);
+  for (int slot = blockIdx.x; slot < nc; slot += gridDim.x) det_trace_component(a, nbr, roots[slot], win, rec + slot);
 }
 
 // Output in findContours order (reverse discovery = descending root index), written straight into pinned
@@ -375,11 +395,12 @@ struct DetOutHost {
   float dist[2 * kMaxBlobs];
 };
 constexpr int kEmitBlock = 1024;
-__global__ __launch_bounds__(kEmitBlock) void k_det_emit(const int* __restrict__ count, const DetRecord* __restrict__ rec,
-                                                         DetOutHost* __restrict__ out) {
+// `total` components were counted, their records are rec[0 .. min(total, kDetMaxComponents)); the whole block
+__device__ __forceinline__ void det_emit_block(const int total, const DetRecord* __restrict__ rec,
+                                               DetOutHost* __restrict__ out) {
   __shared__ int kroot[kDetMaxComponents];
   __shared__ int nkept;
-  const int nc = min(*count, kDetMaxComponents);
+  const int nc = min(total, kDetMaxComponents);
   if (threadIdx.x == 0) nkept = 0;
   __syncthreads();
   for (int i = threadIdx.x; i < nc; i += kEmitBlock)
@@ -400,9 +421,124 @@ __global__ __launch_bounds__(kEmitBlock) void k_det_emit(const int* __restrict__
   }
   if (threadIdx.x == 0) {
     out->n = nk;
-    out->n_components = *count;
-    out->overflow = *count > kDetMaxComponents ? 1 : 0;
+    out->n_components = total;
+    out->overflow = total > kDetMaxComponents ? 1 : 0;
   }
+}
+__global__ __launch_bounds__(kEmitBlock) void k_det_emit(const int* __restrict__ count, const DetRecord* __restrict__ rec,
+                                                         DetOutHost* __restrict__ out) {
+  det_emit_block(*count, rec, out);
+}
+
+// ---------------------------------------------------------------------- R ROIs in one launch sequence
+// pfmpe_find_leds_multi: the six stages over a batch of ROIs of one image.  Each ROI has a descriptor (DetDesc: its
+// DetArgs and its own mask / nbr / label / roots / rec regions of the batch scratch, all in ROI-local pixel
+// indexing, so labels and roots are the numbers the single call computes and the output order is its order).  The
+// grids are flat: ROI r owns the blocks first[r] .. first[r + 1) of a stage (its 16 x 16 tiles, its 32 x 32 tiles,
+// its 256-pixel ranges), so a small ROI next to a large one launches its own tile count only.  A block finds its
+// ROI by one wave-wide comparison against the prefix (R <= 64 = the wave size: lane r holds first[r]), which
+// replaces a block -> ROI map and its upload.
+constexpr int kDetMaxRois = PFMPE_DETECT_MAX_ROIS;
+static_assert(kDetMaxRois <= 64, "det_roi_of_block compares one prefix entry per lane of a wave");
+struct DetBatch {  // head of the batch's device image, the descriptors follow
+  int R, pad[3];
+  int first16[kDetMaxRois], first32[kDetMaxRois], firstpix[kDetMaxRois];  // first block of ROI r per stage
+};
+struct DetDesc {
+  DetArgs a;
+  uint8_t* mask;
+  uint8_t* nbr;
+  int* label;
+  int* roots;
+  DetRecord* rec;
+  int tiles16_x, tiles32_x;  // tiles per tile row
+};
+// counters, zeroed per call: components per ROI, then the work list's length
+constexpr int kDetWorkCount = kDetMaxRois;
+constexpr size_t kDetCounterBytes = (kDetMaxRois + 1) * sizeof(int);
+
+__device__ __forceinline__ int det_roi_of_block(const int* __restrict__ first, const int R, const int b) {
+  const int lane = threadIdx.x & 63;
+  const bool le = lane < R && first[lane] <= b;  // first[0] = 0: at least one
+  return __builtin_amdgcn_readfirstlane(__popcll(__ballot(le)) - 1);
+}
+
+// The batch's first launch: the head and the descriptors from the host's pinned image into device memory (the
+// stages' blocks then read them from L2, not over the host link), and the counters to zero.  In place of an async
+// copy and a memset: measured at R = 1, those two commands cost the call 20 us of wall time over the single call.
+constexpr int kStageBlock = 1024;
+__global__ __launch_bounds__(kStageBlock) void k_detm_stage(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst,
+                                                            const int nwords, int* __restrict__ counters) {
+  for (int i = threadIdx.x; i < nwords; i += kStageBlock) dst[i] = src[i];
+  if (threadIdx.x <= kDetWorkCount) counters[threadIdx.x] = 0;
+}
+
+__global__ __launch_bounds__(kDetTile* kDetTile) void k_detm_mask(const DetBatch* __restrict__ hd,
+                                                                   const DetDesc* __restrict__ descs,
+                                                                   const uint8_t* __restrict__ img) {
+  const int roi = det_roi_of_block(hd->first16, hd->R, blockIdx.x);
+  const DetDesc& d = descs[roi];
+  const int t = blockIdx.x - hd->first16[roi];
+  const int ty = t / d.tiles16_x, tx = t - ty * d.tiles16_x;
+  det_mask_tile(d.a, img, d.mask, tx * kDetTile, ty * kDetTile);
+}
+
+__global__ __launch_bounds__(kLabelBlock) void k_detm_label(const DetBatch* __restrict__ hd,
+                                                            const DetDesc* __restrict__ descs) {
+  const int roi = det_roi_of_block(hd->first32, hd->R, blockIdx.x);
+  const DetDesc& d = descs[roi];
+  const int t = blockIdx.x - hd->first32[roi];
+  const int ty = t / d.tiles32_x, tx = t - ty * d.tiles32_x;
+  det_label_tile(d.a, d.mask, d.nbr, d.label, tx * kLT, ty * kLT);
+}
+
+constexpr int kPixBlock = 256;  // an ROI's pixels are rounded up to whole blocks: a block belongs to one ROI
+__global__ __launch_bounds__(kPixBlock) void k_detm_merge(const DetBatch* __restrict__ hd,
+                                                          const DetDesc* __restrict__ descs) {
+  const int roi = det_roi_of_block(hd->firstpix, hd->R, blockIdx.x);
+  const DetDesc& d = descs[roi];
+  det_merge_pixel(d.a, d.nbr, d.label, (int64_t)(blockIdx.x - hd->firstpix[roi]) * kPixBlock + threadIdx.x);
+}
+
+// A root takes a slot of its ROI and, while the ROI has slots left, an entry (roi << 16 | slot) of the flat work list.
+__global__ __launch_bounds__(kPixBlock) void k_detm_roots(const DetBatch* __restrict__ hd,
+                                                          const DetDesc* __restrict__ descs, int* __restrict__ counters,
+                                                          uint32_t* __restrict__ work) {
+  const int roi = det_roi_of_block(hd->firstpix, hd->R, blockIdx.x);
+  const DetDesc& d = descs[roi];
+  const int64_t i = (int64_t)(blockIdx.x - hd->firstpix[roi]) * kPixBlock + threadIdx.x;
+  if (i >= (int64_t)d.a.W * d.a.H || !d.mask[i]) return;
+  int* label = d.label;
+  int r = (int)i;
+  for (int p = label[r]; p != r; p = label[r]) r = p;
+  label[i] = r;
+  if (r == (int)i) {
+    const int s = atomicAdd(counters + roi, 1);
+    if (s < kDetMaxComponents) {
+      d.roots[s] = (int)i;
+      work[atomicAdd(counters + kDetWorkCount, 1)] = (uint32_t)roi << 16 | (uint32_t)s;
+    }
+  }
+}
+
+// Waves grid-stride over the work list, so they stay busy whatever the split of components between the ROIs.
+__global__ __launch_bounds__(64) void k_detm_trace(const DetDesc* __restrict__ descs, const int* __restrict__ counters,
+                                                   const uint32_t* __restrict__ work) {
+  __shared__ uint8_t win[kWin][kWin];
+  const int nw = counters[kDetWorkCount];  // <= R * kDetMaxComponents: only slots below the cap are listed
+  for (int w = blockIdx.x; w < nw; w += gridDim.x) {
+    const uint32_t e = __builtin_amdgcn_readfirstlane(work[w]);
+    const DetDesc& d = descs[e >> 16];
+    const int slot = (int)(e & 0xffffu);
+    det_trace_component(d.a, d.nbr, d.roots[slot], win, d.rec + slot);
+  }
+}
+
+// one block per ROI; out: R records in pinned host memory
+__global__ __launch_bounds__(kEmitBlock) void k_detm_emit(const DetDesc* __restrict__ descs,
+                                                          const int* __restrict__ counters,
+                                                          DetOutHost* __restrict__ out) {
+  det_emit_block(counters[blockIdx.x], descs[blockIdx.x].rec, out + blockIdx.x);
 }
 
 }  // namespace pfmpe
@@ -459,6 +595,79 @@ int det_buffers(pfmpe_ctx* c, int64_t npix, DetBuffers& b) {
   return PFMPE_OK;
 }
 
+// what is wrong with one ROI's parameters for a width x height image (nullptr: nothing)
+const char* det_check(const pfmpe_detect_params* prm, int width, int height) {
+  const int rx = prm->roi_w < 0 ? 0 : prm->roi_x, ry = prm->roi_h < 0 ? 0 : prm->roi_y;
+  const int W = prm->roi_w < 0 ? width : prm->roi_w, H = prm->roi_h < 0 ? height : prm->roi_h;
+  if (rx < 0 || ry < 0 || W < 1 || H < 1 || (int64_t)rx + W > width || (int64_t)ry + H > height)
+    return "ROI outside the image";
+  if (!(prm->gaussian_sigma > 0) || prm->gaussian_sigma > 5.0) return "gaussian_sigma must be in (0, 5]";
+  return nullptr;
+}
+
+// the kernels' arguments for one ROI (checked by det_check)
+DetArgs det_args(const pfmpe_ctx* c, const pfmpe_detect_params* prm, int width, int height, int pitch) {
+  DetArgs a{};
+  const int n = (int)std::nearbyint(prm->gaussian_sigma * 3 * 2 + 1) | 1;  // ksize from sigma for 8U (cvRound)
+  const std::vector<int> k = gaussian_q8(n, prm->gaussian_sigma);
+  for (int i = 0; i < n; ++i) a.k[i] = k[i];
+  a.radius = n / 2;
+  a.thr = prm->threshold_value;
+  a.active = prm->active_markers ? 1 : 0;
+  a.img_w = width;
+  a.img_h = height;
+  a.pitch = pitch;
+  a.rx = prm->roi_w < 0 ? 0 : prm->roi_x;
+  a.ry = prm->roi_h < 0 ? 0 : prm->roi_y;
+  a.W = prm->roi_w < 0 ? width : prm->roi_w;
+  a.H = prm->roi_h < 0 ? height : prm->roi_h;
+  std::memcpy(a.K, c->K, sizeof(a.K));
+  std::memcpy(a.D, prm->D, sizeof(a.D));
+  a.min_area = prm->min_blob_area;
+  a.max_area = prm->max_blob_area;
+  a.max_whd = prm->max_width_height_distortion;
+  a.max_circ = prm->max_circular_distortion;
+  return a;
+}
+
+// Batch scratch (pfmpe_find_leds_multi), one allocation: the counters, the batch head + R descriptors (the pinned
+// image h_detm is uploaded there), the work list, then per ROI mask | nbr | label | roots | rec, each 256-byte
+// aligned.  Fills the descriptors' pointers.
+constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+constexpr size_t kDetmHead = al256(kDetCounterBytes);
+constexpr size_t kDetmDesc = kDetmHead + al256(sizeof(DetBatch));
+int detm_buffers(pfmpe_ctx* c, int R, DetDesc* descs, size_t* o_work) {
+  *o_work = kDetmDesc + al256((size_t)R * sizeof(DetDesc));
+  size_t total = *o_work + al256((size_t)R * kDetMaxComponents * sizeof(uint32_t));
+  std::vector<size_t> base(R);
+  for (int r = 0; r < R; ++r) {
+    const size_t npix = (size_t)descs[r].a.W * descs[r].a.H;
+    base[r] = total;
+    total += 2 * al256(npix) + al256(npix * 4) + al256(kDetMaxComponents * sizeof(int)) +
+             al256(kDetMaxComponents * sizeof(DetRecord));
+  }
+  if (total > c->detm_cap) {
+    if (c->d_detm) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipFree(c->d_detm));
+      c->d_detm = nullptr;
+      c->detm_cap = 0;
+    }
+    HIPCHK(c, hipMalloc((void**)&c->d_detm, total));
+    c->detm_cap = total;
+  }
+  for (int r = 0; r < R; ++r) {
+    const size_t npix = (size_t)descs[r].a.W * descs[r].a.H;
+    unsigned char* p = c->d_detm + base[r];
+    descs[r].mask = p;
+    descs[r].nbr = (p += al256(npix));
+    descs[r].label = (int*)(p += al256(npix));
+    descs[r].roots = (int*)(p += al256(npix * 4));
+    descs[r].rec = (DetRecord*)(p += al256(kDetMaxComponents * sizeof(int)));
+  }
+  return PFMPE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -475,6 +684,20 @@ void pfmpe_default_detect_params(pfmpe_detect_params* p) {
   p->max_circular_distortion = 0.7;
   p->roi_w = -1;  // whole image
   p->roi_h = -1;
+}
+
+// PE:429-432 / PE:454-457: the width and height are clipped against the already moved x and y; 64-bit
+// intermediates, so no margin overflows
+int pfmpe_host_grow_roi(const int32_t roi[4], int32_t margin, int32_t image_w, int32_t image_h, int32_t grown[4]) {
+  if (!roi || !grown || margin < 0 || image_w < 1 || image_h < 1) return PFMPE_E_ARG;
+  const int64_t x = std::max<int64_t>((int64_t)roi[0] - margin, 0), y = std::max<int64_t>((int64_t)roi[1] - margin, 0);
+  const int64_t w = std::min<int64_t>((int64_t)roi[2] + 2 * (int64_t)margin, (int64_t)image_w - x);
+  const int64_t h = std::min<int64_t>((int64_t)roi[3] + 2 * (int64_t)margin, (int64_t)image_h - y);
+  grown[0] = (int32_t)x;
+  grown[1] = (int32_t)y;
+  grown[2] = (int32_t)w;
+  grown[3] = (int32_t)h;
+  return PFMPE_OK;
 }
 
 int pfmpe_stage_image(pfmpe_ctx* c, const uint8_t* image, int width, int height, int pitch) {
@@ -511,33 +734,10 @@ int pfmpe_find_leds(pfmpe_ctx* c, const uint8_t* image, int width, int height, i
   } else if (!c->d_img || c->img_w != width || c->img_h != height || c->img_pitch != pitch) {
     return fail(c, PFMPE_E_STATE, "find_leds: no staged image of this size (pfmpe_stage_image)");
   }
-  const int rx = prm->roi_w < 0 ? 0 : prm->roi_x, ry = prm->roi_h < 0 ? 0 : prm->roi_y;
-  const int W = prm->roi_w < 0 ? width : prm->roi_w, H = prm->roi_h < 0 ? height : prm->roi_h;
-  if (rx < 0 || ry < 0 || W < 1 || H < 1 || rx + W > width || ry + H > height)
-    return fail(c, PFMPE_E_ARG, "find_leds: ROI outside the image");
-  if (!(prm->gaussian_sigma > 0) || prm->gaussian_sigma > 5.0)
-    return fail(c, PFMPE_E_ARG, "find_leds: gaussian_sigma must be in (0, 5]");
+  if (const char* why = det_check(prm, width, height)) return fail(c, PFMPE_E_ARG, std::string("find_leds: ") + why);
   RET(set_device(c));
-  DetArgs a{};
-  const int n = (int)std::nearbyint(prm->gaussian_sigma * 3 * 2 + 1) | 1;  // ksize from sigma for 8U (cvRound)
-  const std::vector<int> k = gaussian_q8(n, prm->gaussian_sigma);
-  for (int i = 0; i < n; ++i) a.k[i] = k[i];
-  a.radius = n / 2;
-  a.thr = prm->threshold_value;
-  a.active = prm->active_markers ? 1 : 0;
-  a.img_w = width;
-  a.img_h = height;
-  a.pitch = pitch;
-  a.rx = rx;
-  a.ry = ry;
-  a.W = W;
-  a.H = H;
-  std::memcpy(a.K, c->K, sizeof(a.K));
-  std::memcpy(a.D, prm->D, sizeof(a.D));
-  a.min_area = prm->min_blob_area;
-  a.max_area = prm->max_blob_area;
-  a.max_whd = prm->max_width_height_distortion;
-  a.max_circ = prm->max_circular_distortion;
+  const DetArgs a = det_args(c, prm, width, height, pitch);
+  const int W = a.W, H = a.H;
   const int64_t npix = (int64_t)W * H;
   DetBuffers b;
   RET(det_buffers(c, npix, b));
@@ -573,6 +773,99 @@ int pfmpe_find_leds(pfmpe_ctx* c, const uint8_t* image, int width, int height, i
   out->n = m;
   out->n_components = nc;
   out->overflow = hout->overflow;
+  return PFMPE_OK;
+}
+
+int pfmpe_find_leds_multi(pfmpe_ctx* c, const uint8_t* image, int width, int height, int pitch,
+                          const pfmpe_detect_params* prm, int R, double* blobs, float* distorted, int max_out,
+                          pfmpe_detect_out* out) {
+  if (!c) return PFMPE_E_ARG;
+  if (!prm || !out || R < 1 || max_out < 0 || (max_out > 0 && !blobs))
+    return fail(c, PFMPE_E_ARG, "find_leds_multi: bad arguments");
+  if (R > PFMPE_DETECT_MAX_ROIS) return fail(c, PFMPE_E_CAP, "find_leds_multi: R exceeds PFMPE_DETECT_MAX_ROIS");
+  if (!c->has_model) return fail(c, PFMPE_E_STATE, "find_leds_multi: set_model first (K)");
+  if (image) {
+    if (width < 1 || height < 1 || pitch < width) return fail(c, PFMPE_E_ARG, "find_leds_multi: bad image");
+  } else if (!c->d_img || c->img_w != width || c->img_h != height || c->img_pitch != pitch) {
+    return fail(c, PFMPE_E_STATE, "find_leds_multi: no staged image of this size (pfmpe_stage_image)");
+  }
+  for (int r = 0; r < R; ++r)
+    if (const char* why = det_check(prm + r, width, height))
+      return fail(c, PFMPE_E_ARG, "find_leds_multi: roi " + std::to_string(r) + ": " + why);
+  if (image) RET(pfmpe_stage_image(c, image, width, height, pitch));
+  RET(set_device(c));
+  if (!c->h_detm) {
+    HIPCHK(c, hipHostMalloc((void**)&c->h_detm, al256(sizeof(DetBatch)) + kDetMaxRois * sizeof(DetDesc),
+                            hipHostMallocMapped | hipHostMallocCoherent));
+  }
+  if (R > c->detm_out_cap) {
+    if (c->h_detm_out) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipHostFree(c->h_detm_out));
+      c->h_detm_out = nullptr;
+      c->detm_out_cap = 0;
+    }
+    HIPCHK(c, hipHostMalloc((void**)&c->h_detm_out, (size_t)R * sizeof(DetOutHost),
+                            hipHostMallocMapped | hipHostMallocCoherent));
+    c->detm_out_cap = R;
+  }
+  // the pinned image of the batch head and the descriptors, then one upload
+  DetBatch* hd = (DetBatch*)c->h_detm;
+  DetDesc* descs = (DetDesc*)(c->h_detm + al256(sizeof(DetBatch)));
+  std::memset(hd, 0, sizeof(*hd));
+  hd->R = R;
+  int n16 = 0, n32 = 0, npb = 0;
+  for (int r = 0; r < R; ++r) {
+    DetDesc& d = descs[r];
+    d.a = det_args(c, prm + r, width, height, pitch);
+    d.tiles16_x = (d.a.W + kDetTile - 1) / kDetTile;
+    d.tiles32_x = (d.a.W + kLT - 1) / kLT;
+    hd->first16[r] = n16;
+    hd->first32[r] = n32;
+    hd->firstpix[r] = npb;
+    n16 += d.tiles16_x * ((d.a.H + kDetTile - 1) / kDetTile);
+    n32 += d.tiles32_x * ((d.a.H + kLT - 1) / kLT);
+    npb += (int)(((int64_t)d.a.W * d.a.H + kPixBlock - 1) / kPixBlock);
+  }
+  size_t o_work = 0;
+  RET(detm_buffers(c, R, descs, &o_work));
+  int* counters = (int*)c->d_detm;
+  const DetBatch* dhd = (const DetBatch*)(c->d_detm + kDetmHead);
+  const DetDesc* ddescs = (const DetDesc*)(c->d_detm + kDetmDesc);
+  uint32_t* work = (uint32_t*)(c->d_detm + o_work);
+  static_assert(sizeof(DetDesc) % sizeof(uint64_t) == 0, "k_detm_stage copies 8-byte words");
+  const int stage_words = (int)((al256(sizeof(DetBatch)) + (size_t)R * sizeof(DetDesc)) / sizeof(uint64_t));
+  const uint64_t* stage_src = nullptr;
+  HIPCHK(c, hipHostGetDevicePointer((void**)&stage_src, c->h_detm, 0));
+  DetOutHost* hout = (DetOutHost*)c->h_detm_out;
+  DetOutHost* dout = nullptr;
+  HIPCHK(c, hipHostGetDevicePointer((void**)&dout, hout, 0));
+  c->timing_now = c->timing > 0;
+  RET(launch(c, PFMPE_K_DETECT, [&] {
+    hipLaunchKernelGGL(k_detm_stage, dim3(1), dim3(kStageBlock), 0, c->stream, stage_src,
+                       (uint64_t*)(c->d_detm + kDetmHead), stage_words, counters);
+    hipLaunchKernelGGL(k_detm_mask, dim3(n16), dim3(kDetTile * kDetTile), 0, c->stream, dhd, ddescs, c->d_img);
+    hipLaunchKernelGGL(k_detm_label, dim3(n32), dim3(kLabelBlock), 0, c->stream, dhd, ddescs);
+    hipLaunchKernelGGL(k_detm_merge, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs);
+    hipLaunchKernelGGL(k_detm_roots, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs, counters, work);
+    hipLaunchKernelGGL(k_detm_trace, dim3(512), dim3(64), 0, c->stream, ddescs, (const int*)counters,
+                       (const uint32_t*)work);
+    hipLaunchKernelGGL(k_detm_emit, dim3(R), dim3(kEmitBlock), 0, c->stream, ddescs, (const int*)counters, dout);
+  }));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->timing_now) RET(harvest_timing(c));
+  c->timing_now = false;
+  for (int r = 0; r < R; ++r) {
+    const DetOutHost& h = hout[r];
+    const int nw = std::min(std::min(h.n, max_out), kMaxBlobs);
+    if (nw > 0) {
+      std::memcpy(blobs + (size_t)r * 2 * max_out, h.und, 2 * (size_t)nw * sizeof(double));
+      if (distorted) std::memcpy(distorted + (size_t)r * 2 * max_out, h.dist, 2 * (size_t)nw * sizeof(float));
+    }
+    out[r].n = h.n;
+    out[r].n_components = h.n_components;
+    out[r].overflow = h.overflow;
+  }
   return PFMPE_OK;
 }
 

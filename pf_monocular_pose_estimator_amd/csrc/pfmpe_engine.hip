@@ -99,6 +99,9 @@ void free_all(pfmpe_ctx* c) {
   c->h_out = nullptr;
   if (c->h_table) (void)hipHostFree(c->h_table);
   if (c->h_det) (void)hipHostFree(c->h_det);
+  if (c->d_detm) (void)hipFree(c->d_detm);
+  if (c->h_detm) (void)hipHostFree(c->h_detm);
+  if (c->h_detm_out) (void)hipHostFree(c->h_detm_out);
   for (auto& e : c->ev_pool) {
     (void)hipEventDestroy(e.a);
     (void)hipEventDestroy(e.b);
