@@ -185,6 +185,30 @@ typedef struct {
 } pfmpe_roi_out;
 int pfmpe_predict_roi(pfmpe_ctx* ctx, const pfmpe_roi_in* in, pfmpe_roi_out* out);
 
+#define PFMPE_ROI_MAX_STREAMS 64
+
+/* The single call above for one frame of each of S contexts (the numUAV loop, PE:89, at PE:396-412) as one launch
+ * sequence with one synchronise.  in[s] / out[s] belong to ctxs[s]; out[s] is what the single call on ctxs[s] with
+ * in[s] returns: the same rectangle and the same bits of bbox.  Contexts: distinct, on one device, of one state
+ * type; N, M, markers, K, the prior's storage (particle order or owner indices, fp16 anchor) and every field of
+ * in[s] are per stream.  Runs on ctxs[0]'s stream and uses ctxs[0]'s scratch; work a member has pending elsewhere is
+ * ordered before the batch; blocking, so nothing of the batch is pending when it returns.  Reads only: no context's
+ * state changes.  With PFMPE_OPT_TIMING on ctxs[0] the sequence is one PFMPE_K_ROI bracket on ctxs[0] (DESIGN.md
+ * §4.14: design and measured times).
+ * Everything is checked before anything is staged or launched, and out is untouched on an error: PFMPE_E_ARG
+ * (S < 1, NULL ctxs / in / out / ctxs[s], a context twice, a device or state-type mismatch, image_w / image_h < 1),
+ * PFMPE_E_CAP (S > PFMPE_ROI_MAX_STREAMS), PFMPE_E_STATE (a stream without model or prior); the text,
+ * "predict_roi_multi: stream <s>: ...", is the last-error text of ctxs[0]. */
+int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* in, pfmpe_roi_out* out);
+
+/* host-only (no GPU, no context): the code a lane of the ROI kernels runs, for N caller-given poses (N x 12 doubles,
+ * N >= 0; N = 0 leaves the markers at predicted_pose_ only), then the same host end (corner distortion, border,
+ * clamp, cv::Rect).  For poses = the rows pfmpe_get_particles returns for the prior it equals the device calls, for
+ * every state type.  PFMPE_E_ARG for a NULL pointer (poses may be NULL when N = 0), M outside 1..PFMPE_MAX_MARKERS,
+ * N < 0, an image side < 1; out is untouched then. */
+int pfmpe_host_predict_roi(const double* markers_xyz, int M, const double* K, const double* poses, int64_t N,
+                           const pfmpe_roi_in* in, pfmpe_roi_out* out);
+
 /* ------------------------------------------------- brute-force P3P (re)initialisation (§8f row 2) */
 /* PoseEstimator::initialise (PE:1503-1786) for the particle-filter configuration, run when the track is
  * lost (it_since_initialized_ < 1, PE:128-205).  Blobs are image_points_ (undistorted px).  Stages:
@@ -569,7 +593,7 @@ enum { PFMPE_K_PROPAGATE = 0, /* k_propagate_weigh (+ last-block iteration reduc
        PFMPE_K_RESAMPLE = 1,  /* k_resample / k_resample_owners: resampling           */
        PFMPE_K_AUX = 2,       /* hand-off kernels (k_group*, k_top*), regeneration   */
        PFMPE_K_FRAME = 3,     /* k_frame: the whole frame in one launch              */
-       PFMPE_K_ROI = 4,       /* k_roi + k_roi_final (pfmpe_predict_roi)             */
+       PFMPE_K_ROI = 4,       /* k_roi + k_roi_final (pfmpe_predict_roi), k_roi_multi* */
        PFMPE_K_FINAL = 5,     /* k_resample_final (non-deferred frames): the record   */
        PFMPE_K_P3P_HIST = 6,  /* k_p3p_hist: initialisation histogram                */
        PFMPE_K_P3P_CHECK = 7, /* k_p3p_check: checkCorrespondences of all candidates */

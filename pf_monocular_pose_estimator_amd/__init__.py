@@ -18,6 +18,7 @@ from ._capi import (  # noqa: F401
     REFINE_NO_PAIRS, REFINE_CONVERGED, REFINE_CAP_KEPT, REFINE_CAP_REVERTED, REFINE_ROW_DTYPE, RefineParams, RefineRow,
     RefineOut, default_refine_params, host_optimise_pose,
     DETECT_MAX_ROIS, DetectParams, DetectOut, host_grow_roi,
+    ROI_MAX_STREAMS, RoiIn, RoiOut, host_predict_roi,
 )
 
 __all__ = [

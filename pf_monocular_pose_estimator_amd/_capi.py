@@ -53,8 +53,10 @@ EXPORTED_SYMBOLS = (
     "pfmpe_assoc_stats", "pfmpe_get_pairs", "pfmpe_host_assoc_summary",
     "pfmpe_default_refine_params", "pfmpe_refine_poses", "pfmpe_refine_cloud", "pfmpe_host_optimise_pose",
     "pfmpe_find_leds_multi", "pfmpe_host_grow_roi",
+    "pfmpe_predict_roi_multi", "pfmpe_host_predict_roi",
 )
 DETECT_MAX_ROIS = 64
+ROI_MAX_STREAMS = 64
 
 
 class Params(C.Structure):
@@ -262,6 +264,8 @@ def load() -> C.CDLL:
         "pfmpe_host_optimise_pose": (I, [dp, I, dp, dp, I, C.POINTER(C.c_uint32), I, C.POINTER(RefineParams), dp,
                                          C.POINTER(RefineRow), dp]),
         "pfmpe_predict_roi": (I, [P, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
+        "pfmpe_predict_roi_multi": (I, [C.POINTER(P), I, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
+        "pfmpe_host_predict_roi": (I, [dp, I, dp, dp, I64, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
         "pfmpe_default_init_params": (None, [C.POINTER(InitParams)]),
         "pfmpe_p3p_histogram": (I, [P, dp, I, C.POINTER(C.c_uint32)]),
         "pfmpe_initialise": (I, [P, dp, I, C.POINTER(InitParams), C.POINTER(InitOut), C.POINTER(C.c_uint32)]),
@@ -445,8 +449,9 @@ class Engine:
             e._last_out = o
         return outs
 
-    def predict_roi(self, prediction, predicted_pose, D, image_w, image_h, border, cam_move_inv=None) -> dict:
-        """Region of interest for the next detection (PE:396-412): {"roi": [x, y, w, h], "bbox": [...]}."""
+    @staticmethod
+    def make_roi_in(prediction, predicted_pose, D, image_w, image_h, border, cam_move_inv=None) -> RoiIn:
+        """A RoiIn from the arguments of predict_roi (cam_move_inv None: the identity)."""
         ri = RoiIn()
         cm = np.eye(4)[:3].reshape(12) if cam_move_inv is None else np.asarray(cam_move_inv, np.float64).reshape(12)
         ri.cam_move_inv[:] = list(cm)
@@ -454,9 +459,27 @@ class Engine:
         ri.predicted_pose[:] = list(np.asarray(predicted_pose, np.float64).reshape(12))
         ri.D[:] = list(np.asarray(D, np.float64).reshape(5))
         ri.image_w, ri.image_h, ri.border = int(image_w), int(image_h), int(border)
+        return ri
+
+    def predict_roi(self, prediction, predicted_pose, D, image_w, image_h, border, cam_move_inv=None) -> dict:
+        """Region of interest for the next detection (PE:396-412): {"roi": [x, y, w, h], "bbox": [...]}."""
+        ri = self.make_roi_in(prediction, predicted_pose, D, image_w, image_h, border, cam_move_inv)
         ro = RoiOut()
         self._chk(self.lib.pfmpe_predict_roi(self.ctx, C.byref(ri), C.byref(ro)))
-        return {"roi": [ro.x, ro.y, ro.width, ro.height], "bbox": np.array(list(ro.bbox))}
+        return _roi_dict(ro)
+
+    @staticmethod
+    def predict_roi_multi(engines, ins) -> list:
+        """The ROI of one frame of each engine as ONE batch on the device (pfmpe_predict_roi_multi): ins[s] (a RoiIn,
+        make_roi_in) belongs to engines[s]; returns one {"roi", "bbox"} per engine, each what predict_roi returns."""
+        S = len(engines)
+        if S != len(ins) or S == 0:
+            raise ValueError("predict_roi_multi: one RoiIn per engine")
+        ctxs = (C.c_void_p * S)(*[e.ctx.value for e in engines])
+        arr_in = (RoiIn * S)(*ins)
+        arr_out = (RoiOut * S)()
+        engines[0]._chk(engines[0].lib.pfmpe_predict_roi_multi(ctxs, S, arr_in, arr_out))
+        return [_roi_dict(ro) for ro in arr_out]
 
     def p3p_histogram(self, blobs) -> np.ndarray:
         """Stage 1 of initialise (PE:1526-1716): the B x M correspondence histogram (uint32)."""
@@ -700,6 +723,26 @@ class Engine:
 
 def _enc(x):
     return x.encode() if isinstance(x, str) else x
+
+
+def _roi_dict(ro: RoiOut) -> dict:
+    return {"roi": [ro.x, ro.y, ro.width, ro.height], "bbox": np.array(list(ro.bbox))}
+
+
+def host_predict_roi(markers, K, poses, roi_in: RoiIn) -> dict:
+    """predict_roi on the host for caller-given poses (pfmpe_host_predict_roi: the code a lane of the ROI kernels
+    runs, then the same host end).  poses: N x 12 (N may be 0: the markers at predicted_pose_ only)."""
+    m = np.ascontiguousarray(markers, dtype=np.float64).reshape(-1, 3)
+    k = np.ascontiguousarray(K, dtype=np.float64).reshape(-1)
+    p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+    if k.size != 9:
+        raise ValueError("host_predict_roi: K must be 3x3")
+    ro = RoiOut()
+    rc = load().pfmpe_host_predict_roi(_dptr(m), m.shape[0], _dptr(k), _dptr(p) if p.shape[0] else None, p.shape[0],
+                                       C.byref(roi_in), C.byref(ro))
+    if rc != OK:
+        raise PFError(rc, "host_predict_roi: 1 <= M <= %d markers and image sides >= 1" % MAX_MARKERS)
+    return _roi_dict(ro)
 
 
 def parse_marker_yaml(text) -> np.ndarray:

@@ -110,6 +110,12 @@ struct pfmpe_ctx {
   unsigned char* h_detm = nullptr;
   void* h_detm_out = nullptr;
   int detm_out_cap = 0;            // records in h_detm_out
+  // pfmpe_predict_roi_multi (owned by the batch's first context): the batch scratch (head + descriptors, then one
+  // partial per block of the batch; grown on demand), and the pinned, host-mapped image of the head + descriptors
+  // followed by the result boxes of PFMPE_ROI_MAX_STREAMS streams
+  unsigned char* d_roim = nullptr;
+  size_t roim_cap = 0;
+  unsigned char* h_roim = nullptr;
   int num_cu = 0;
   bool coop = false;               // device supports cooperative launches
   int fused = 2;                   // PFMPE_OPT_FUSED: 2 flat one-launch (k_frame2), 1 tree (k_frame), 0 two launches

@@ -102,6 +102,8 @@ void free_all(pfmpe_ctx* c) {
   if (c->d_detm) (void)hipFree(c->d_detm);
   if (c->h_detm) (void)hipHostFree(c->h_detm);
   if (c->h_detm_out) (void)hipHostFree(c->h_detm_out);
+  if (c->d_roim) (void)hipFree(c->d_roim);
+  if (c->h_roim) (void)hipHostFree(c->h_roim);
   for (auto& e : c->ev_pool) {
     (void)hipEventDestroy(e.a);
     (void)hipEventDestroy(e.b);
@@ -618,56 +620,23 @@ void host_distort(const double* K, const double* D, float xin, float yin, float*
   *xo = (float)(xc * fx + cx);
   *yo = (float)(yc * fy + cy);
 }
-}  // namespace
-
-int pfmpe_predict_roi(pfmpe_ctx* c, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
-  if (!c) return PFMPE_E_ARG;
-  if (!in || !out) return fail(c, PFMPE_E_ARG, "predict_roi: null in/out");
-  if (!c->has_model || !c->has_prior) return fail(c, PFMPE_E_STATE, "predict_roi: set_model and set_prior first");
-  if (in->image_w < 1 || in->image_h < 1) return fail(c, PFMPE_E_ARG, "predict_roi: bad image size");
-  RET(set_device(c));
-  const int N = c->N;
-  const int nblk = (N + kBlock - 1) / kBlock;
-  if (!c->d_roi) HIPCHK(c, hipMalloc((void**)&c->d_roi, ((size_t)c->max_blk + 1) * 4 * sizeof(double)));
-  RoiArgs ra{};
-  std::memcpy(ra.cam, in->cam_move_inv, sizeof(ra.cam));
-  std::memcpy(ra.predm, in->prediction, sizeof(ra.predm));
-  std::memcpy(ra.K, c->K, sizeof(ra.K));
-  std::memcpy(ra.markers, c->markers, sizeof(ra.markers));
-  std::memcpy(ra.anchor, c->anchor[c->prior_idx], sizeof(ra.anchor));
-  ra.N = N;
-  ra.M = c->M;
-  ra.ld = c->ld;
-  ra.owner = prior_owner_ptr(c);
-  double* part = c->d_roi + 4;
-  RET(launch(c, PFMPE_K_ROI, [&] {
-    const void* st = c->d_state[c->prior_idx];
-    if (c->state_dtype == PFMPE_STATE_F64)
-      hipLaunchKernelGGL((k_roi<double, double>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const double*)st, part);
-    else if (c->state_dtype == PFMPE_STATE_F16)
-      hipLaunchKernelGGL((k_roi<float, __half>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const __half*)st, part);
-    else
-      hipLaunchKernelGGL((k_roi<float, float>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const float*)st, part);
-    hipLaunchKernelGGL((k_roi_final<double>), dim3(1), dim3(kBlock), 0, c->stream, part, nblk, c->d_roi);
-  }));
-  double bb[4];
-  HIPCHK(c, hipMemcpyAsync(bb, c->d_roi, sizeof(bb), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  RET(harvest_timing(c));
+// The host end of every ROI entry point: bb = the particles' box {x_min, x_max, y_min, y_max} -> out.
+void roi_epilogue(const double* K, const double* markers, int M, const pfmpe_roi_in* in, double* bb,
+                  pfmpe_roi_out* out) {
   // + the markers at predicted_pose_ (PE:1049-1052)
-  for (int m = 0; m < c->M; ++m) {
+  for (int m = 0; m < M; ++m) {
     double uv[2];
-    host_project(c->K, in->predicted_pose, c->markers + 3 * m, uv);
+    host_project(K, in->predicted_pose, markers + 3 * m, uv);
     if (uv[0] < bb[0]) bb[0] = uv[0];
     if (uv[0] > bb[1]) bb[1] = uv[0];
     if (uv[1] < bb[2]) bb[2] = uv[1];
     if (uv[1] > bb[3]) bb[3] = uv[1];
   }
-  std::memcpy(out->bbox, bb, sizeof(bb));
+  std::memcpy(out->bbox, bb, 4 * sizeof(double));
   // determineROI (led_detector.cpp:317-368): corners as cv::Point2f, distorted, border, clamp, cv::Rect
   float x0f, y0f, x1f, y1f;
-  host_distort(c->K, in->D, (float)bb[0], (float)bb[2], &x0f, &y0f);
-  host_distort(c->K, in->D, (float)bb[1], (float)bb[3], &x1f, &y1f);
+  host_distort(K, in->D, (float)bb[0], (float)bb[2], &x0f, &y0f);
+  host_distort(K, in->D, (float)bb[1], (float)bb[3], &x1f, &y1f);
   const double W = in->image_w, H = in->image_h, b = in->border;
   const double x0 = std::max(0.0, std::min(W, (double)x0f - b));
   const double x1 = std::max(0.0, std::min(W, (double)x1f + b));
@@ -684,6 +653,175 @@ int pfmpe_predict_roi(pfmpe_ctx* c, const pfmpe_roi_in* in, pfmpe_roi_out* out) 
     out->width = (int32_t)(x1 - x0);
     out->height = (int32_t)(y1 - y0);
   }
+}
+// the kernel arguments of context c's current prior for one ROI request
+RoiArgs roi_args(const pfmpe_ctx* c, const pfmpe_roi_in* in) {
+  RoiArgs ra{};
+  std::memcpy(ra.cam, in->cam_move_inv, sizeof(ra.cam));
+  std::memcpy(ra.predm, in->prediction, sizeof(ra.predm));
+  std::memcpy(ra.K, c->K, sizeof(ra.K));
+  std::memcpy(ra.markers, c->markers, sizeof(ra.markers));
+  std::memcpy(ra.anchor, c->anchor[c->prior_idx], sizeof(ra.anchor));
+  ra.N = c->N;
+  ra.M = c->M;
+  ra.ld = c->ld;
+  ra.owner = prior_owner_ptr(c);
+  return ra;
+}
+}  // namespace
+
+int pfmpe_predict_roi(pfmpe_ctx* c, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
+  if (!c) return PFMPE_E_ARG;
+  if (!in || !out) return fail(c, PFMPE_E_ARG, "predict_roi: null in/out");
+  if (!c->has_model || !c->has_prior) return fail(c, PFMPE_E_STATE, "predict_roi: set_model and set_prior first");
+  if (in->image_w < 1 || in->image_h < 1) return fail(c, PFMPE_E_ARG, "predict_roi: bad image size");
+  RET(set_device(c));
+  const int N = c->N;
+  const int nblk = (N + kBlock - 1) / kBlock;
+  if (!c->d_roi) HIPCHK(c, hipMalloc((void**)&c->d_roi, ((size_t)c->max_blk + 1) * 4 * sizeof(double)));
+  const RoiArgs ra = roi_args(c, in);
+  double* part = c->d_roi + 4;
+  c->timing_now = c->timing > 0;  // bracketed like the detector's and the initialisation's launches
+  const int rl = launch(c, PFMPE_K_ROI, [&] {
+    const void* st = c->d_state[c->prior_idx];
+    if (c->state_dtype == PFMPE_STATE_F64)
+      hipLaunchKernelGGL((k_roi<double, double>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const double*)st, part);
+    else if (c->state_dtype == PFMPE_STATE_F16)
+      hipLaunchKernelGGL((k_roi<float, __half>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const __half*)st, part);
+    else
+      hipLaunchKernelGGL((k_roi<float, float>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const float*)st, part);
+    hipLaunchKernelGGL((k_roi_final<double>), dim3(1), dim3(kBlock), 0, c->stream, part, nblk, c->d_roi);
+  });
+  c->timing_now = false;
+  RET(rl);
+  double bb[4];
+  HIPCHK(c, hipMemcpyAsync(bb, c->d_roi, sizeof(bb), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  RET(harvest_timing(c));
+  roi_epilogue(c->K, c->markers, c->M, in, bb, out);
+  return PFMPE_OK;
+}
+
+int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
+  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+  pfmpe_ctx* c0 = ctxs[0];
+  if (!in || !out) return fail(c0, PFMPE_E_ARG, "predict_roi_multi: null in/out");
+  if (S > PFMPE_ROI_MAX_STREAMS)
+    return fail(c0, PFMPE_E_CAP, "predict_roi_multi: S exceeds PFMPE_ROI_MAX_STREAMS");
+  int64_t total = 0;
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = ctxs[s];
+    const std::string who = "predict_roi_multi: stream " + std::to_string(s) + ": ";
+    if (!c) return fail(c0, PFMPE_E_ARG, who + "null context");
+    for (int e = 0; e < s; ++e)
+      if (ctxs[e] == c) return fail(c0, PFMPE_E_ARG, who + "context appears twice");
+    if (c->device != c0->device || c->state_dtype != c0->state_dtype)
+      return fail(c0, PFMPE_E_ARG, who + "device and state type must match ctxs[0]");
+    if (!c->has_model || !c->has_prior) return fail(c0, PFMPE_E_STATE, who + "set_model and set_prior first");
+    if (in[s].image_w < 1 || in[s].image_h < 1) return fail(c0, PFMPE_E_ARG, who + "bad image size");
+    total += (c->N + kBlock - 1) / kBlock;
+  }
+  if (total > INT32_MAX) return fail(c0, PFMPE_E_CAP, "predict_roi_multi: too many blocks in one batch");
+  RET(set_device(c0));
+  // the scratch before any member's ordering state changes: pinned image (head, descriptors, result boxes) once,
+  // device image + partials grown on demand (nothing of an earlier batch is pending: the call is blocking)
+  constexpr size_t kDescOff = (sizeof(RoiBatch) + 255) / 256 * 256;
+  constexpr size_t kBoxOff = kDescOff + kRoiMaxStreams * sizeof(RoiDesc);
+  if (!c0->h_roim)
+    HIPCHK(c0, hipHostMalloc((void**)&c0->h_roim, kBoxOff + kRoiMaxStreams * 4 * sizeof(double),
+                             hipHostMallocMapped | hipHostMallocCoherent));
+  const size_t need = kBoxOff + (size_t)total * 4 * sizeof(double);
+  if (need > c0->roim_cap) {
+    if (c0->d_roim) HIPCHK(c0, hipFree(c0->d_roim));
+    c0->d_roim = nullptr;
+    c0->roim_cap = 0;
+    const size_t cap = kBoxOff + (need - kBoxOff) * 2;
+    HIPCHK(c0, hipMalloc((void**)&c0->d_roim, cap));
+    c0->roim_cap = cap;
+  }
+  unsigned char* hd_img = nullptr;
+  HIPCHK(c0, hipHostGetDevicePointer((void**)&hd_img, c0->h_roim, 0));
+  // every member's work so far is ordered before the batch (multi_m's rule: a later member's failure gives the
+  // earlier ones their ordering state back)
+  std::vector<std::pair<hipStream_t, std::shared_ptr<BatchFence>>> saved(S);
+  for (int s = 0; s < S; ++s) saved[s] = {ctxs[s]->last_stream, ctxs[s]->last_fence};
+  auto restore = [&] {
+    for (int e = 0; e < S; ++e) {
+      ctxs[e]->last_stream = saved[e].first;
+      ctxs[e]->last_fence = saved[e].second;
+    }
+  };
+  for (int s = 1; s < S; ++s)
+    if (const int r = order_after(ctxs[s], c0->stream, c0)) {
+      restore();
+      return r;
+    }
+  RoiBatch* hd = (RoiBatch*)c0->h_roim;
+  RoiDesc* descs = (RoiDesc*)(c0->h_roim + kDescOff);
+  std::memset(hd, 0, sizeof(*hd));
+  hd->S = S;
+  int32_t nb = 0;
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = ctxs[s];
+    RoiDesc& d = descs[s];
+    d.a = roi_args(c, &in[s]);
+    d.prior = c->d_state[c->prior_idx];
+    hd->first[s] = nb;
+    nb += (c->N + kBlock - 1) / kBlock;
+  }
+  hd->first[S] = nb;
+  const int stage_words = (int)((kDescOff + (size_t)S * sizeof(RoiDesc)) / sizeof(uint64_t));
+  const RoiBatch* dhd = (const RoiBatch*)c0->d_roim;
+  const RoiDesc* ddescs = (const RoiDesc*)(c0->d_roim + kDescOff);
+  double* part = (double*)(c0->d_roim + kBoxOff);
+  const double* hbox = (const double*)(c0->h_roim + kBoxOff);
+  double* dbox = (double*)(hd_img + kBoxOff);
+  c0->timing_now = c0->timing > 0;
+  int rc = launch(c0, PFMPE_K_ROI, [&] {
+    hipLaunchKernelGGL((k_roi_stage<uint64_t>), dim3(1), dim3(kBlock), 0, c0->stream, (const uint64_t*)hd_img,
+                       (uint64_t*)c0->d_roim, stage_words);
+    if (c0->state_dtype == PFMPE_STATE_F64)
+      hipLaunchKernelGGL((k_roi_multi<double, double>), dim3(nb), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
+    else if (c0->state_dtype == PFMPE_STATE_F16)
+      hipLaunchKernelGGL((k_roi_multi<float, __half>), dim3(nb), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
+    else
+      hipLaunchKernelGGL((k_roi_multi<float, float>), dim3(nb), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
+    hipLaunchKernelGGL((k_roi_multi_final<double>), dim3(S), dim3(kBlock), 0, c0->stream, dhd, (const double*)part,
+                       dbox);
+  });
+  c0->timing_now = false;
+  if (rc == PFMPE_OK && hipStreamSynchronize(c0->stream) != hipSuccess)
+    rc = fail(c0, PFMPE_E_HIP, "predict_roi_multi: stream synchronise failed");
+  if (rc == PFMPE_OK) rc = harvest_timing(c0);
+  if (rc != PFMPE_OK) {
+    restore();
+    return rc;
+  }
+  // nothing of the batch is pending: no member needs a fence
+  for (int s = 0; s < S; ++s) {
+    double bb[4];
+    std::memcpy(bb, hbox + 4 * (size_t)s, sizeof(bb));
+    roi_epilogue(ctxs[s]->K, ctxs[s]->markers, ctxs[s]->M, &in[s], bb, &out[s]);
+  }
+  return PFMPE_OK;
+}
+
+int pfmpe_host_predict_roi(const double* markers_xyz, int M, const double* K, const double* poses, int64_t N,
+                           const pfmpe_roi_in* in, pfmpe_roi_out* out) {
+  if (!markers_xyz || !K || !in || !out || M < 1 || M > PFMPE_MAX_MARKERS || N < 0 || (N > 0 && !poses) ||
+      in->image_w < 1 || in->image_h < 1)
+    return PFMPE_E_ARG;
+  RoiArgs ra{};
+  std::memcpy(ra.cam, in->cam_move_inv, sizeof(ra.cam));
+  std::memcpy(ra.predm, in->prediction, sizeof(ra.predm));
+  std::memcpy(ra.K, K, sizeof(ra.K));
+  std::memcpy(ra.markers, markers_xyz, (size_t)M * 3 * sizeof(double));
+  ra.N = 1;  // each pose row is a one-particle set: 12 planes of one element
+  ra.M = M;
+  ra.ld = 1;
+  double bb[4] = {INFINITY, 0.0, INFINITY, 0.0};
+  for (int64_t n = 0; n < N; ++n) roi_particle_box<double, double>(ra, poses + 12 * n, 0, bb[0], bb[1], bb[2], bb[3]);
+  roi_epilogue(ra.K, ra.markers, M, in, bb, out);
   return PFMPE_OK;
 }
 

@@ -1,0 +1,273 @@
+"""pfmpe_predict_roi_multi: the ROIs of S contexts in one batch.
+
+Every box of a batch must be the single call's, the host twin's (pfmpe_host_predict_roi on the exported prior) and the
+oracle's: rectangles equal, bbox bit patterns equal, for every state type, particle counts on both sides of every
+block and wave boundary (100,000 particles: 391 partials, a second pass of the per-stream reduction), priors in
+particle order and deferred (owner indices), members whose latest work is on another stream, and every argument
+error."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import pf_monocular_pose_estimator_amd as pf
+from pf_monocular_pose_estimator_amd import _capi
+from pf_monocular_pose_estimator_amd import synthetic as syn
+from oracle import pforacle as orc
+from test_gpu_parity import make_engine
+
+pytestmark = pytest.mark.gpu
+
+STATES = {"f64": pf.STATE_F64, "f32": pf.STATE_F32, "f16": pf.STATE_F16}
+EYE = np.eye(4)[:3].reshape(12)
+SIZES = [(752, 480), (640, 480), (752, 480), (800, 600), (376, 240), (1024, 768)]
+BORDERS = [0, 5, 20, 7, 12, 3]
+
+
+def markers_of(M):
+    if M <= 12:
+        return syn.markers_for(M)
+    rng = np.random.default_rng(16)
+    return np.vstack([syn.markers_12(), rng.uniform(-0.15, 0.3, size=(M - 12, 3))])
+
+
+def cam_moved(i):
+    cam = np.eye(4)
+    cam[:3, :3] = syn.rot_z(0.002 * (i + 1)) @ syn.rot_x(-0.003)
+    cam[:3, 3] = [0.01, -0.004 * (i + 1), 0.002]
+    return cam[:3].reshape(12)
+
+
+class Obj:
+    """One tracked object: an engine with its own model, camera and ROI settings, and the frames that drive it."""
+
+    def __init__(self, i, N, M, state, fused=2, n_frames=3, with_prior=True):
+        self.i, self.N, self.M = i, N, M
+        self.st = syn.make_stream(syn.StreamConfig("t", M=5, B=30, N=N, seed=20 + i), n_frames)  # the motion
+        self.markers = markers_of(M)
+        self.K = syn.K_README.copy()
+        self.K[0, 0] += 3.5 * i
+        self.K[0, 2] -= 2.25 * i
+        self.D = syn.D_README * (0.4 + 0.15 * i)
+        self.size, self.border = SIZES[i % 6], BORDERS[i % 6]
+        self.cam = None if i % 2 == 0 else cam_moved(i)
+        self.eng = make_engine(N, self.markers, self.K, state, pf.RNG_PHILOX, fused=fused)
+        if with_prior:
+            self.eng.set_prior(syn.initial_prior_fast(syn.to44(self.st.frames[0].current_pose), N, seed=7 + i))
+
+    def roi_in(self, f):
+        fr = self.st.frames[f]
+        return pf.Engine.make_roi_in(fr.prediction, fr.predicted_pose, self.D, self.size[0], self.size[1], self.border,
+                                     cam_move_inv=self.cam)
+
+    def single(self, f):
+        fr = self.st.frames[f]
+        return self.eng.predict_roi(fr.prediction, fr.predicted_pose, self.D, self.size[0], self.size[1], self.border,
+                                    cam_move_inv=self.cam)
+
+    def frame(self, f):
+        fr = self.st.frames[f]
+        rng = np.random.default_rng(300 + 31 * self.i + f)
+        blobs = np.vstack([syn.project(self.K, fr.truth, self.markers) + rng.normal(0.0, 0.3, (self.M, 2)),
+                           rng.uniform(0, 480, (10, 2))])
+        return self.eng.make_frame(fr.current_pose, fr.predicted_pose, fr.prediction, blobs=blobs, dt=fr.dt,
+                                   seed=77 + 13 * self.i + f, frame_idx=f)
+
+    def step(self, f):
+        return self.eng.step(self.frame(f))
+
+    def host_and_oracle(self, f):
+        fr = self.st.frames[f]
+        prior = self.eng.get_particles(1)
+        host = pf.host_predict_roi(self.markers, self.K, prior, self.roi_in(f))
+        roi, bbox = orc.predict_roi(self.markers, self.K, self.D, prior, EYE if self.cam is None else self.cam,
+                                    fr.prediction, fr.predicted_pose, self.size[0], self.size[1], self.border)
+        return host, {"roi": roi, "bbox": bbox}
+
+
+def same(a, b, what):
+    assert list(a["roi"]) == list(b["roi"]), (what, a["roi"], b["roi"])
+    assert np.array_equal(np.asarray(a["bbox"]).view(np.uint64), np.asarray(b["bbox"]).view(np.uint64)), \
+        (what, a["bbox"], b["bbox"])
+
+
+def batch(objs, f):
+    return pf.Engine.predict_roi_multi([o.eng for o in objs], [o.roi_in(f) for o in objs])
+
+
+def close(objs):
+    for o in objs:
+        o.eng.close()
+
+
+@pytest.mark.parametrize("state", ["f64", "f32", "f16"])
+def test_batch_equals_single_host_and_oracle(state):
+    """a lone lane, a partial wave, one exact block, a block boundary, the marker cap, and 391 blocks (the smallest of
+    these counts that gives the per-stream reduction a second pass); then the same after one solo step of each
+    (resampled priors, fp16 anchors away from the first prior's)"""
+    specs = [(1, 5), (63, 5), (256, 5), (257, 12), (4099, 16), (100_000, 5)]
+    objs = [Obj(i, N, M, STATES[state]) for i, (N, M) in enumerate(specs)]
+    try:
+        for f in (0, 1):
+            got = batch(objs, f)
+            for o, g in zip(objs, got):
+                host, oracle = o.host_and_oracle(f)
+                same(g, o.single(f), (state, f, o.N, "single"))
+                same(g, host, (state, f, o.N, "host"))
+                same(g, oracle, (state, f, o.N, "oracle"))
+            assert len({tuple(g["roi"]) for g in got}) > 1
+            if f == 0:
+                for o in objs:
+                    o.step(0)
+    finally:
+        close(objs)
+
+
+def test_deferred_priors():
+    """two streams whose prior is stored through owner indices (two-launch frames, deferral on) next to one stored in
+    particle order"""
+    objs = [Obj(0, 5000, 5, pf.STATE_F32, fused=0), Obj(1, 70_001, 5, pf.STATE_F32, fused=0),
+            Obj(2, 3000, 5, pf.STATE_F32, fused=0)]
+    try:
+        objs[2].eng.set_option(pf.OPT_DEFER_RESAMPLE, 0)
+        for o in objs:
+            out = o.step(0)
+            assert out.resampled
+        assert objs[0].eng.info(pf.INFO_LAST_RESAMPLE) == pf.RESAMPLE_OWNERS
+        assert objs[1].eng.info(pf.INFO_LAST_RESAMPLE) == pf.RESAMPLE_OWNERS
+        assert objs[2].eng.info(pf.INFO_LAST_RESAMPLE) == pf.RESAMPLE_BLOCKS
+        got = batch(objs, 1)
+        for o, g in zip(objs, got):
+            host, oracle = o.host_and_oracle(1)
+            same(g, o.single(1), (o.N, "single"))
+            same(g, host, (o.N, "host"))
+            same(g, oracle, (o.N, "oracle"))
+    finally:
+        close(objs)
+
+
+def test_order_and_membership():
+    objs = [Obj(i, N, 5, pf.STATE_F32) for i, N in enumerate((700, 64, 1025))]
+    many = []
+    try:
+        fwd = batch(objs, 0)
+        rev = batch(objs[::-1], 0)
+        for a, b in zip(fwd, rev[::-1]):
+            same(a, b, "reversed")
+        for o, g in zip(objs, fwd):
+            same(batch([o], 0)[0], o.single(0), "S = 1")
+            same(g, o.single(0), "forward")
+        many = [Obj(i, 3 + 5 * i, 5, pf.STATE_F32, n_frames=1) for i in range(pf.ROI_MAX_STREAMS)]  # N = 3 .. 318
+        got = batch(many, 0)
+        assert len(got) == pf.ROI_MAX_STREAMS
+        for o, g in zip(many, got):
+            same(g, o.single(0), ("S = 64", o.i))
+    finally:
+        close(objs + many)
+
+
+def test_members_with_work_on_other_streams():
+    """a batch led by C right after a step batch led by A, a read-back of B right after it, and a batch led by A right
+    after a solo step of B: everything equals a twin set of engines driven by single calls only"""
+    sizes = (20_000, 33_333, 9000)
+    objs = [Obj(i, N, 5, pf.STATE_F32, fused=0) for i, N in enumerate(sizes)]
+    twin = [Obj(i, N, 5, pf.STATE_F32) for i, N in enumerate(sizes)]
+    A, B, Cc = objs
+    try:
+        pf.Engine.step_multi([o.eng for o in objs], [o.frame(0) for o in objs])
+        for t in twin:
+            t.step(0)
+        got = batch([Cc, A, B], 1)
+        pb = B.eng.get_particles(1)
+        for o, g in zip((Cc, A, B), got):
+            same(g, twin[o.i].single(1), ("after step_multi", o.i))
+        assert np.array_equal(pb, twin[1].eng.get_particles(1))
+        B.step(1)
+        got = batch([A, B, Cc], 2)
+        twin[1].step(1)
+        for o, g in zip((A, B, Cc), got):
+            same(g, twin[o.i].single(2), ("after solo step", o.i))
+        assert np.array_equal(B.eng.get_particles(1), twin[1].eng.get_particles(1))
+    finally:
+        close(objs + twin)
+
+
+def test_timing_slot():
+    objs = [Obj(i, N, 5, pf.STATE_F32) for i, N in enumerate((3000, 500))]
+    try:
+        for o in objs:
+            o.eng.set_option(pf.OPT_TIMING, 1 if o.i == 0 else 0)
+            o.eng.reset_kernel_stats()
+        batch(objs, 0)
+        lead, member = (list(o.eng.kernel_stats().values()) for o in objs)
+        assert len(lead) == len(member) == 9 == _capi.K_COUNT
+        assert lead[pf.K_ROI][0] >= 1 and lead[pf.K_ROI][1] > 0.0
+        assert member[pf.K_ROI][0] == 0
+        assert all(n == 0 for k, (n, _) in enumerate(lead) if k != pf.K_ROI)
+    finally:
+        close(objs)
+
+
+def test_errors_leave_out_untouched():
+    lib = pf.load()
+    objs = [Obj(i, 300 + i, 5, pf.STATE_F32, n_frames=1) for i in range(3)]
+    other = Obj(3, 300, 5, pf.STATE_F64, n_frames=1)
+    bare = Obj(4, 300, 5, pf.STATE_F32, n_frames=1, with_prior=False)
+    A, B, Cc = objs
+
+    def call(members, ins=None, S=None, null_in=False, null_out=False, null_ctxs=False):
+        S = len(members) if S is None else S
+        n = max(len(members), 1)
+        ctxs = (C.c_void_p * n)(*[m.eng.ctx.value if m is not None else None for m in members])
+        arr_in = (_capi.RoiIn * n)(*(ins if ins is not None else [m.roi_in(0) if m is not None else A.roi_in(0)
+                                                                  for m in members]))
+        arr_out = (_capi.RoiOut * n)(*[_capi.RoiOut(-7, -7, -7, -7, (C.c_double * 4)(-7.0, -7.0, -7.0, -7.0))
+                                       for _ in range(n)])
+        rc = lib.pfmpe_predict_roi_multi(None if null_ctxs else ctxs, S, None if null_in else arr_in,
+                                         None if null_out else arr_out)
+        untouched = all([o.x, o.y, o.width, o.height] + list(o.bbox) == [-7] * 8 for o in arr_out)
+        return rc, untouched
+
+    try:
+        A.eng.predict_roi_multi([A.eng], [A.roi_in(0)])
+        bad_w = Cc.roi_in(0)
+        bad_w.image_w = 0
+        bad_h = B.roi_in(0)
+        bad_h.image_h = -1
+        cases = [
+            ("twice", call([A, B, A]), pf.E_ARG, "predict_roi_multi: stream 2: "),
+            ("state type", call([A, other, B]), pf.E_ARG, "predict_roi_multi: stream 1: "),
+            ("no prior", call([A, bare]), pf.E_STATE, "predict_roi_multi: stream 1: "),
+            ("image_w", call([A, B, Cc], ins=[A.roi_in(0), B.roi_in(0), bad_w]), pf.E_ARG,
+             "predict_roi_multi: stream 2: "),
+            ("image_h", call([A, B], ins=[A.roi_in(0), bad_h]), pf.E_ARG, "predict_roi_multi: stream 1: "),
+            ("null member", call([A, None]), pf.E_ARG, "predict_roi_multi: stream 1: "),
+            ("S = 65", call([A] * 65), pf.E_CAP, "predict_roi_multi: "),
+            ("null in", call([A, B], null_in=True), pf.E_ARG, "predict_roi_multi: "),
+            ("null out", call([A, B], null_out=True), pf.E_ARG, "predict_roi_multi: "),
+        ]
+        for name, (rc, untouched), code, text in cases:
+            assert rc == code, (name, rc)
+            assert untouched, name
+        # the text of each, on ctxs[0] (read right after the failing call)
+        for members, kw, text in (([A, B, A], {}, "stream 2: context appears twice"),
+                                  ([A, other, B], {}, "stream 1: "),
+                                  ([A, bare], {}, "stream 1: "),
+                                  ([A, B, Cc], {"ins": [A.roi_in(0), B.roi_in(0), bad_w]}, "stream 2: "),
+                                  ([A] * 65, {}, "PFMPE_ROI_MAX_STREAMS")):
+            call(members, **kw)
+            assert A.eng.last_error().startswith("predict_roi_multi: ") and text in A.eng.last_error(), \
+                A.eng.last_error()
+        assert call([A, B], S=0)[0] == pf.E_ARG
+        assert call([A, B], null_ctxs=True)[0] == pf.E_ARG
+        assert call([None, B])[0] == pf.E_ARG
+        with pytest.raises(pf.PFError) as ei:
+            pf.Engine.predict_roi_multi([A.eng, bare.eng], [A.roi_in(0), bare.roi_in(0)])
+        assert ei.value.code == pf.E_STATE
+        with pytest.raises(ValueError):
+            pf.Engine.predict_roi_multi([A.eng, B.eng], [A.roi_in(0)])
+        # a valid batch afterwards
+        for o, g in zip(objs, batch(objs, 0)):
+            same(g, o.single(0), "after the errors")
+    finally:
+        close(objs + [other, bare])
