@@ -9,7 +9,7 @@ namespace {
 template <typename T, typename SP, bool DENSE, int MAXM>
 void assoc_launch_p(pfmpe_ctx* c, const FrameArgsT<T>& fa, const AssocArgs& aa, const unsigned char* table, dim3 grid,
                     size_t lds) {
-  const SP* st = (const SP*)c->d_state[c->prior_idx];
+  const SP* st = (const SP*)c->d_state[c->prior_idx].get();
   if (c->prune)
     hipLaunchKernelGGL((k_assoc_votes<T, SP, DENSE, MAXM, true>), grid, dim3(kBlock), lds, c->stream, fa, aa, table, st);
   else
@@ -56,14 +56,9 @@ int assoc_launch_t(pfmpe_ctx* c, int B, const unsigned char* table, size_t tbyte
 
 int assoc_launch(pfmpe_ctx* c, int B, const unsigned char* table, size_t tbytes, const GridHdr& gh, AssocArgs aa) {
   if (aa.count < 1) return PFMPE_OK;
-  switch (c->state_dtype) {
-    case PFMPE_STATE_F64:
-      return assoc_launch_t<double, double>(c, B, table, tbytes, gh, aa);
-    case PFMPE_STATE_F16:
-      return assoc_launch_t<float, __half>(c, B, table, tbytes, gh, aa);
-    default:
-      return assoc_launch_t<float, float>(c, B, table, tbytes, gh, aa);
-  }
+  return visit_state(c, [&](auto s) {
+    return assoc_launch_t<typename decltype(s)::T, typename decltype(s)::SP>(c, B, table, tbytes, gh, aa);
+  });
 }
 
 }  // namespace pfmpe_impl

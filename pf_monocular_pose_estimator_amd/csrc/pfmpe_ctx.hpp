@@ -56,9 +56,82 @@ struct BatchFence {
   }
 };
 
-struct pfmpe_ctx {
-  int device = 0;
+// ---------------------------------------------------------------------- owned GPU buffers
+// Every block of device or pinned host memory of the engine is owned by a Buf: move-only, freed by its destructor
+// with the call that matches its kind, so nothing is freed by a list somebody has to keep.  A mapped buffer keeps its
+// device address beside the host one (dev()), so a regrown buffer cannot leave a stale alias behind.
+enum class Mem { Device, Pinned, Mapped };  // hipMalloc; hipHostMalloc default; mapped + coherent (device-readable)
+// blocks alive in this process (undocumented info key 115: a deterministic leak check on a shared device)
+inline std::atomic<int64_t>& live_blocks() {
+  static std::atomic<int64_t> n{0};
+  return n;
+}
+template <typename T, Mem K = Mem::Device>
+class Buf {
+ public:
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  Buf(Buf&& o) noexcept { swap(o); }
+  Buf& operator=(Buf&& o) noexcept {
+    Buf t(std::move(o));
+    swap(t);
+    return *this;
+  }
+  ~Buf() { reset(); }
+  void swap(Buf& o) noexcept {
+    std::swap(p_, o.p_);
+    std::swap(dev_, o.dev_);
+    std::swap(cap_, o.cap_);
+  }
+  T* get() const { return p_; }
+  T* dev() const { return dev_; }  // Mem::Mapped: the block's device address
+  size_t bytes() const { return cap_; }
+  explicit operator bool() const { return p_ != nullptr; }
+  // A block of `bytes` in place of the present one (if any); an error leaves the buffer empty.
+  int alloc(pfmpe_ctx* c, size_t bytes);
+  // allocate on first use
+  int ensure(pfmpe_ctx* c, size_t bytes) { return p_ ? PFMPE_OK : alloc(c, bytes); }
+  // Grow on demand: a block of `capacity` bytes when the present one holds fewer than `need` (the growth policy is
+  // the caller's).  The context's stream is drained before the old block is freed: work enqueued on it may still
+  // read it.  Contents are not kept.
+  int grow(pfmpe_ctx* c, size_t need, size_t capacity);
+  void reset() {
+    if (p_) {
+      (void)(K == Mem::Device ? hipFree((void*)p_) : hipHostFree((void*)p_));
+      live_blocks() -= 1;
+    }
+    p_ = dev_ = nullptr;
+    cap_ = 0;
+  }
+
+ private:
+  T* p_ = nullptr;
+  T* dev_ = nullptr;
+  size_t cap_ = 0;
+};
+
+// The stream and the events of a context.  A base of pfmpe_ctx, so its destructor runs after pfmpe_ctx's members are
+// gone: at destroy the buffers go first, then the timing events and own_ev, and the stream last.
+struct CtxQueue {
   hipStream_t stream = nullptr;
+  std::vector<EventPair> ev_pool;  // timing brackets
+  hipEvent_t own_ev = nullptr;     // cross-stream ordering (order_after)
+  CtxQueue() = default;
+  CtxQueue(const CtxQueue&) = delete;
+  CtxQueue& operator=(const CtxQueue&) = delete;
+  ~CtxQueue() {
+    for (auto& e : ev_pool) {
+      (void)hipEventDestroy(e.a);
+      (void)hipEventDestroy(e.b);
+    }
+    if (own_ev) (void)hipEventDestroy(own_ev);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct pfmpe_ctx : CtxQueue {
+  int device = 0;
   int max_particles = 0, max_markers = 0, max_blobs = 0, state_dtype = PFMPE_STATE_F32;
   size_t es = 4;       // bytes per state element (4 fp32, 8 fp64, 2 fp16 deltas)
   size_t ws = 4;       // bytes per weight (compute type)
@@ -66,61 +139,55 @@ struct pfmpe_ctx {
   int64_t ld = 0;      // plane stride (elements)
   int max_blk = 0;
 
-  void* d_state[2] = {nullptr, nullptr};
+  Buf<void> d_state[2];
   int prior_idx = 0;
-  void* d_w[2] = {nullptr, nullptr};
-  void* d_prop[2] = {nullptr, nullptr};  // two-launch path: propagated set per weight slot (keep_prop)
+  Buf<void> d_w[2];
+  Buf<void> d_prop[2];  // two-launch path: propagated set per weight slot (keep_prop)
   // Deferred resampling (PFMPE_OPT_DEFER_RESAMPLE): a two-launch frame with the kept set writes the
   // new prior's owner indices (d_owner[frame_owner_out]) instead of the particles; the frame's kept buffer then
   // becomes the prior's storage (swapped with the unused post buffer at take_step) and prior particle n is stored
   // row d_owner[prior_owner][n].  prior_owner = -1: the prior is stored in particle order.
-  uint32_t* d_owner[2] = {nullptr, nullptr};
+  Buf<uint32_t> d_owner[2];
   int prior_owner = -1;
   int frame_owner_out = -1;  // this frame's owner buffer (-1: materialised resample)
   bool defer = true;
   int max_grp = 0;
-  BlockPart* d_part[2] = {nullptr, nullptr};
-  BlockScan* d_bscan[2] = {nullptr, nullptr};
-  GroupPart* d_gpart[2] = {nullptr, nullptr};
-  GroupScan* d_gscan = nullptr;
-  CountPart* d_cpart = nullptr;
-  unsigned long long* d_winkey = nullptr;  // kWinShards winner keys + the owners finish's arrival shards (kWinBytes), zero between frames
-  CountPart* d_cgroup = nullptr;
-  uint32_t* d_counters = nullptr;  // [prop group x max_grp][prop top][res group x max_grp][res top]
-  uint32_t* d_gen = nullptr;       // k_frame iteration release word (monotonic)
-  Cand* d_cand = nullptr;          // per-block winner candidates
-  double* d_mlpose = nullptr;      // most likely pose (12)
-  double* d_roi = nullptr;         // ROI box [4] + per-block partials
-  double* d_cloud = nullptr;       // cloud statistics: result row + per-block partial rows (pfmpe_cloud_stats)
-  uint32_t* d_assoc = nullptr;     // association votes: M x B bins + the pair-count bins (pfmpe_assoc_stats)
-  uint32_t* d_pairs = nullptr;     // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
-  unsigned char* d_refine = nullptr; // Gauss-Newton refinement scratch (RefineBuf layout, pfmpe_refine_*)
-  unsigned char* d_init = nullptr; // initialisation scratch (pfmpe_init.hip), grown on demand
-  size_t init_cap = 0;
-  unsigned char* d_det = nullptr;  // detector scratch (pfmpe_detect.hip), grown on demand
-  size_t det_cap = 0;
-  uint8_t* d_img = nullptr;        // staged camera image (pfmpe_stage_image)
-  size_t img_cap = 0;
+  Buf<BlockPart> d_part[2];
+  Buf<BlockScan> d_bscan[2];
+  Buf<GroupPart> d_gpart[2];
+  Buf<GroupScan> d_gscan;
+  Buf<CountPart> d_cpart;
+  Buf<unsigned long long> d_winkey;  // kWinShards winner keys + the owners finish's arrival shards (kWinBytes), zero between frames
+  Buf<CountPart> d_cgroup;
+  Buf<uint32_t> d_counters;  // [prop group x max_grp][prop top][res group x max_grp][res top]
+  Buf<uint32_t> d_gen; // k_frame iteration release word (monotonic)
+  Buf<Cand> d_cand; // per-block winner candidates
+  Buf<double> d_mlpose; // most likely pose (12)
+  Buf<double> d_roi;   // ROI box [4] + per-block partials
+  Buf<double> d_cloud; // cloud statistics: result row + per-block partial rows (pfmpe_cloud_stats)
+  Buf<uint32_t> d_assoc; // association votes: M x B bins + the pair-count bins (pfmpe_assoc_stats)
+  Buf<uint32_t> d_pairs; // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
+  Buf<unsigned char> d_refine; // Gauss-Newton refinement scratch (RefineBuf layout, pfmpe_refine_*)
+  Buf<unsigned char> d_init;       // initialisation scratch (pfmpe_init.hip), grown on demand
+  Buf<unsigned char> d_det;        // detector scratch (pfmpe_detect.hip), grown on demand
+  Buf<uint8_t> d_img;              // staged camera image (pfmpe_stage_image), grown on demand
   int img_w = 0, img_h = 0, img_pitch = 0;
-  void* h_det = nullptr;           // detector output record (pinned, host-mapped)
+  Buf<void, Mem::Mapped> h_det;    // detector output record (pinned, host-mapped)
   // pfmpe_find_leds_multi: the batch scratch (counters, batch head + descriptors, work list, then every ROI's
   // regions; grown on demand), the pinned image of the head + descriptors, and R pinned, host-mapped output records
-  unsigned char* d_detm = nullptr;
-  size_t detm_cap = 0;
-  unsigned char* h_detm = nullptr;
-  void* h_detm_out = nullptr;
-  int detm_out_cap = 0;            // records in h_detm_out
+  Buf<unsigned char> d_detm;
+  Buf<unsigned char, Mem::Mapped> h_detm;
+  Buf<void, Mem::Mapped> h_detm_out;  // grown on demand
   // pfmpe_predict_roi_multi (owned by the batch's first context): the batch scratch (head + descriptors, then one
   // partial per block of the batch; grown on demand), and the pinned, host-mapped image of the head + descriptors
   // followed by the result boxes of PFMPE_ROI_MAX_STREAMS streams
-  unsigned char* d_roim = nullptr;
-  size_t roim_cap = 0;
-  unsigned char* h_roim = nullptr;
+  Buf<unsigned char> d_roim;
+  Buf<unsigned char, Mem::Mapped> h_roim;
   int num_cu = 0;
   bool coop = false;               // device supports cooperative launches
   int fused = 2;                   // PFMPE_OPT_FUSED: 2 flat one-launch (k_frame2), 1 tree (k_frame), 0 two launches
-  uint32_t* d_flat = nullptr;      // k_frame2 sharded arrival counters (kFlatWords)
-  unsigned char* d_gran = nullptr; // k_frame2 granule hand-offs (kGranBytes: block partials x 2 parities, counts)
+  Buf<uint32_t> d_flat; // k_frame2 sharded arrival counters (kFlatWords)
+  Buf<unsigned char> d_gran; // k_frame2 granule hand-offs (kGranBytes: block partials x 2 parities, counts)
   uint32_t gframe = 0;             // granule tag frame count (1 .. kGranFrames; the area is zeroed on wrap)
   uint32_t flat_base_w = 0, flat_base_c = 0;  // their running totals (host mirror)
   int64_t fused_fallbacks = 0;     // fused frames redone with two launches
@@ -137,14 +204,13 @@ struct pfmpe_ctx {
   // host-side timing of batches this context leads (undocumented info keys 110-114): entry -> first launch,
   // the launches, last launch -> records, records -> return, batches counted
   int64_t mt_enter = 0, mt_ns[4] = {0, 0, 0, 0}, mt_batches = 0;
-  Ctrl* d_ctrl = nullptr;
-  RecOut* h_rec = nullptr;       // pinned host memory: the record granules, written by the final wave
-  RecOut* d_out = nullptr;       // its device address
-  OutDev* h_out = nullptr;       // the last record, unpacked on the host by wait_frame
+  Buf<Ctrl> d_ctrl;
+  Buf<RecOut, Mem::Mapped> h_rec;  // pinned host memory: the record granules, written by the final wave (dev())
+  std::unique_ptr<OutDev> h_out;   // the last record, unpacked on the host by wait_frame
   int32_t seq = 0;               // frame-record sequence number (publication tag = 2 * seq + finished)
-  unsigned char* d_table = nullptr;  // this frame's blob table (BlobTable<T> layout)
-  unsigned char* h_table = nullptr;  // pinned staging
-  unsigned char* d_bank = nullptr;   // staged tables of a whole stream, back to back
+  Buf<unsigned char> d_table;        // this frame's blob table (BlobTable<T> layout)
+  Buf<unsigned char, Mem::Pinned> h_table;  // pinned staging
+  Buf<unsigned char> d_bank;         // staged tables of a whole stream, back to back
   std::vector<size_t> bank_off;      // byte offset of frame f's table
   std::vector<int32_t> bank_B;
   std::vector<GridHdr> bank_grid;    // frame f's table grid header (host copy, for the kernel arguments)
@@ -152,17 +218,15 @@ struct pfmpe_ctx {
   std::vector<int32_t> bank_offsets; // set_params changes tol_PF (the grid's window depends on it)
   double bank_tol_pf = 0.0;          // the tol_PF the bank's tables were built for
   int last_grid = -1;                // PFMPE_INFO_LAST_GRID
-  double* d_xfer = nullptr;      // N x 12 doubles
-  uint32_t* d_counts = nullptr;
-  uint64_t* d_stamps = nullptr;  // diagnostic stamps (diag & 4)
+  Buf<double> d_xfer;            // N x 12 doubles
+  Buf<uint32_t> d_counts;
+  Buf<uint64_t> d_stamps;        // diagnostic stamps (diag & 4)
   // batch scratch (pfmpe_step_multi, owned by the batch's first context): stream descriptors, the
   // block -> stream map and host-supplied blob tables; the host writes the descriptors and tables into the
   // pinned image, a staging launch (k_stage_multi) moves them to HBM and builds the map
-  unsigned char* d_multi = nullptr;
+  Buf<unsigned char> d_multi;
+  Buf<unsigned char, Mem::Mapped> h_multi;  // as large as d_multi
   hipEvent_t br_a = nullptr, br_b = nullptr;  // the open timing bracket (launch / klaunch)
-  unsigned char* h_multi = nullptr;
-  unsigned char* hd_multi = nullptr;  // device address of h_multi
-  size_t multi_cap = 0;
   uint32_t multi_gen = 0;  // batch generation: one per staging launch this context leads (StreamDesc::gen)
   std::vector<int64_t> map_sig;  // the block map now in d_multi: {boff, total, then (first, nblk) per stream}
   // Cross-stream ordering.  A context's work runs on its own stream (pfmpe_step, read-backs, ...) or, inside a
@@ -171,7 +235,6 @@ struct pfmpe_ctx {
   // leader's fence when the latest work was a batch, else through own_ev recorded then on the own stream.
   hipStream_t last_stream = nullptr;
   std::shared_ptr<BatchFence> last_fence;
-  hipEvent_t own_ev = nullptr;
   std::shared_ptr<BatchFence> lead_fence;  // this context as a batch leader
 
   // model / params
@@ -202,7 +265,6 @@ struct pfmpe_ctx {
   int last_kept_slot = 0, last_kept_iter = 0;
 
   // timing
-  std::vector<EventPair> ev_pool;
   size_t ev_used = 0;
   int64_t k_launches[PFMPE_K_COUNT] = {0};
   double k_ms[PFMPE_K_COUNT] = {0};
@@ -232,6 +294,73 @@ inline int fail(pfmpe_ctx* c, int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                                       \
       return fail((ctx), PFMPE_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
   } while (0)
+
+#define RET(expr)              \
+  do {                         \
+    int r_ = (expr);           \
+    if (r_ != PFMPE_OK) return r_; \
+  } while (0)
+
+}  // namespace pfmpe_impl
+
+template <typename T, Mem K>
+int Buf<T, K>::alloc(pfmpe_ctx* c, size_t bytes) {
+  reset();
+  void* p = nullptr;
+  const hipError_t e = K == Mem::Device   ? hipMalloc(&p, bytes)
+                       : K == Mem::Pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault)
+                                          : hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess)
+    return pfmpe_impl::fail(c, PFMPE_E_HIP, "allocating " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+  live_blocks() += 1;
+  p_ = (T*)p;
+  cap_ = bytes;
+  if (K == Mem::Mapped) {
+    void* d = nullptr;
+    if (const hipError_t g = hipHostGetDevicePointer(&d, p, 0); g != hipSuccess) {
+      reset();
+      return pfmpe_impl::fail(c, PFMPE_E_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(g));
+    }
+    dev_ = (T*)d;
+  }
+  return PFMPE_OK;
+}
+template <typename T, Mem K>
+int Buf<T, K>::grow(pfmpe_ctx* c, size_t need, size_t capacity) {
+  if (need <= cap_) return PFMPE_OK;
+  if (p_)
+    if (const hipError_t e = hipStreamSynchronize(c->stream); e != hipSuccess)
+      return pfmpe_impl::fail(c, PFMPE_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+  return alloc(c, capacity);
+}
+
+// ---------------------------------------------------------------------- state-type dispatch
+// The one place that maps a context's storage type (and RNG mode) to the template arguments of the kernels:
+// f is called with a tag whose T is the compute type and SP the storage type (RNG: kRngReference / kRngPhilox).
+template <typename T_, typename SP_, int RNG_ = 0>
+struct StateTag {
+  using T = T_;
+  using SP = SP_;
+  static constexpr int RNG = RNG_;
+};
+template <typename F>
+auto visit_state(const pfmpe_ctx* c, F&& f) {
+  switch (c->state_dtype) {
+    case PFMPE_STATE_F64: return f(StateTag<double, double>{});
+    case PFMPE_STATE_F16: return f(StateTag<float, __half>{});
+    default: return f(StateTag<float, float>{});
+  }
+}
+template <typename F>
+auto visit_state_rng(const pfmpe_ctx* c, F&& f) {
+  return visit_state(c, [&](auto s) {
+    using S = decltype(s);
+    return c->params.rng_mode == PFMPE_RNG_REFERENCE ? f(StateTag<typename S::T, typename S::SP, kRngReference>{})
+                                                     : f(StateTag<typename S::T, typename S::SP, kRngPhilox>{});
+  });
+}
+
+namespace pfmpe_impl {
 
 // Order work about to be enqueued for context c on stream `to` after c's latest work, when that went to
 // another stream (a batch runs on the leader's stream, unordered with each member's own stream).
@@ -358,14 +487,14 @@ inline int harvest_timing(pfmpe_ctx* c) {
 // every granule carries the tag.  Granule 0 alone with an even tag is an unfinished iteration batch.  The
 // spin is bounded by hipStreamQuery: an idle stream without a record is an error.
 inline bool take_record(pfmpe_ctx* c, int32_t want) {
-  volatile const uint64_t* g = c->h_rec->g;
+  volatile const uint64_t* g = c->h_rec.get()->g;
   const uint32_t t = (uint32_t)(g[0] >> 32);
   if ((int32_t)(t >> 1) != want) return false;
   if (t & 1u) {
     for (int k = kRecWords - 1; k > 0; --k)
       if ((uint32_t)(g[k] >> 32) != t) return false;
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    uint32_t* w = (uint32_t*)c->h_out;
+    uint32_t* w = (uint32_t*)c->h_out.get();
     for (int k = 0; k < kRecWords; ++k) w[k] = (uint32_t)g[k];
   }
   c->h_out->tag = (int32_t)t;
@@ -408,12 +537,6 @@ inline size_t counters_bytes(const pfmpe_ctx* c) { return (size_t)(2 * c->max_gr
 
 inline bool frame_done(const pfmpe_ctx* c) { return (c->h_out->tag & 1) != 0; }
 
-#define RET(expr)              \
-  do {                         \
-    int r_ = (expr);           \
-    if (r_ != PFMPE_OK) return r_; \
-  } while (0)
-
 // ---------------------------------------------------------------------- typed launch sequence
 template <typename T> FrameArgsT<T>& last_args(pfmpe_ctx* c);
 template <> inline FrameArgsT<float>& last_args<float>(pfmpe_ctx* c) { return c->last_fa_f; }
@@ -423,25 +546,18 @@ template <> inline FrameArgsT<double>& last_args<double>(pfmpe_ctx* c) { return 
 // one-launch frames keep the propagated particle in registers and never need them
 inline int ensure_prop(pfmpe_ctx* c) {
   if (!c->keep_prop) return PFMPE_OK;
-  if (!c->d_prop[0]) {
-    const size_t bytes = (size_t)kPlanes * c->ld * c->es;
-    for (int i = 0; i < 2; ++i) HIPCHK(c, hipMalloc(&c->d_prop[i], bytes));
-  }
+  for (int i = 0; i < 2; ++i) RET(c->d_prop[i].ensure(c, (size_t)kPlanes * c->ld * c->es));
   if (c->defer && !c->d_owner[0]) {  // both or neither: deferral is gated on both pointers
-    const size_t bytes = (size_t)c->ld * sizeof(uint32_t);
-    hipError_t e = hipMalloc((void**)&c->d_owner[0], bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_owner[1], bytes);
-    if (e != hipSuccess) {
-      if (c->d_owner[0]) (void)hipFree(c->d_owner[0]);
-      c->d_owner[0] = c->d_owner[1] = nullptr;
-      return fail(c, PFMPE_E_HIP, std::string("owner buffers: ") + hipGetErrorString(e));
-    }
+    Buf<uint32_t> own[2];
+    for (auto& o : own)
+      if (o.alloc(c, (size_t)c->ld * sizeof(uint32_t)) != PFMPE_OK) return fail(c, PFMPE_E_HIP, "owner buffers: " + c->err);
+    for (int i = 0; i < 2; ++i) c->d_owner[i].swap(own[i]);
   }
   return PFMPE_OK;
 }
 // the owner indices of the current prior (null: stored in particle order)
 inline const uint32_t* prior_owner_ptr(const pfmpe_ctx* c) {
-  return c->prior_owner >= 0 ? c->d_owner[c->prior_owner] : nullptr;
+  return c->prior_owner >= 0 ? c->d_owner[c->prior_owner].get() : nullptr;
 }
 
 // k_assoc_votes for the context's state type, marker bucket and pruning option on its stream (pfmpe_assoc.hip, a TU
@@ -478,6 +594,85 @@ static_assert(sizeof(pfmpe_refine_row) == 128 && sizeof(pfmpe_refine_out) <= Ref
 // d_refine (begun anew when `begin`).  d_refine holds the model and the blobs already.
 int refine_launch(pfmpe_ctx* c, const pfmpe_refine_params& prm, const double* poses, const uint32_t* corr, int64_t base,
                   int count, int cap, bool begin);
+
+// ---------------------------------------------------------------------- shared preambles of the entry points
+// the transfer buffer (N x 12 doubles), written and read inside one blocking call by every user
+inline int ensure_xfer(pfmpe_ctx* c) { return c->d_xfer.ensure(c, (size_t)c->max_particles * 12 * sizeof(double)); }
+// the pair rows of one chunk of pairs_cap(c) particles, then their counts (pfmpe_get_pairs, pfmpe_refine_*)
+constexpr size_t kPairRow = 2 * kMaxMarkers;
+inline int pairs_cap(const pfmpe_ctx* c) { return std::min(c->max_particles, kPairsChunk); }
+inline int ensure_pairs(pfmpe_ctx* c) {
+  return c->d_pairs.ensure(c, (size_t)pairs_cap(c) * (kPairRow + 1) * sizeof(uint32_t));
+}
+
+// Which blobs a pfmpe_assoc_in means: the caller's, or a frame of the staged bank (the host copy kept for
+// rebuilds).  Checks the request (texts begin with `who`); *blobs / *B are the resolved list.
+inline int resolve_blobs(pfmpe_ctx* c, const std::string& who, const pfmpe_assoc_in* in, const double** blobs, int* B) {
+  if (in->B < 0) return fail(c, PFMPE_E_ARG, who + ": B < 0");
+  *blobs = in->blobs;
+  *B = in->B;
+  if (in->bank_frame >= 0) {
+    if (c->bank_offsets.empty() || in->bank_frame >= (int)c->bank_offsets.size() - 1)
+      return fail(c, PFMPE_E_ARG, who + ": bank_frame out of range");
+    *B = c->bank_offsets[in->bank_frame + 1] - c->bank_offsets[in->bank_frame];
+    *blobs = c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame];
+  } else if (*B > 0 && !*blobs) {
+    return fail(c, PFMPE_E_ARG, who + ": null blobs");
+  }
+  if (*B > c->max_blobs) return fail(c, PFMPE_E_CAP, who + ": B exceeds max_blobs");
+  return PFMPE_OK;
+}
+
+// The members of a batch (pfmpe_step_multi, pfmpe_predict_roi_multi): none null, none twice, and each agreeing
+// with ctxs[0] as same(c) tells (`what` names the properties); then the entry point's own checks of that stream,
+// each(s, prefix).  Errors are reported on ctxs[0] as "<who>: stream <s>: ...".
+template <typename Same, typename Each>
+int check_members(pfmpe_ctx* const* ctxs, int S, const char* who, const char* what, Same&& same, Each&& each) {
+  pfmpe_ctx* c0 = ctxs[0];
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = ctxs[s];
+    const std::string at = std::string(who) + ": stream " + std::to_string(s) + ": ";
+    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
+    for (int e = 0; e < s; ++e)
+      if (ctxs[e] == c) return fail(c0, PFMPE_E_ARG, at + "context appears twice");
+    if (c->device != c0->device || c->state_dtype != c0->state_dtype || !same(c))
+      return fail(c0, PFMPE_E_ARG, at + what + " must match ctxs[0]");
+    RET(each(s, at));
+  }
+  return PFMPE_OK;
+}
+
+// Orders a batch's members before the batch on the leader's stream `to`.  order_after clears a member's ordering
+// state; whatever happens between that and the batch's fence (an ordering failure of a later member, a failed
+// launch) gives every member its state back, since its pending work is then still unordered with its own stream.
+// So: no path between changing a member's ordering state and either restoring it (the destructor) or setting
+// the state the batch leaves (after commit()).
+class OrderGuard {
+ public:
+  OrderGuard(pfmpe_ctx* const* cs, int S) : cs_(cs), saved_(S) {
+    for (int s = 0; s < S; ++s) saved_[s] = {cs[s]->last_stream, cs[s]->last_fence};
+  }
+  OrderGuard(const OrderGuard&) = delete;
+  OrderGuard& operator=(const OrderGuard&) = delete;
+  // members first .. S - 1 after their latest work; errors are reported on `err`
+  int order(int first, hipStream_t to, pfmpe_ctx* err) {
+    for (int s = first; s < (int)saved_.size(); ++s) RET(order_after(cs_[s], to, err));
+    return PFMPE_OK;
+  }
+  void commit() { committed_ = true; }
+  ~OrderGuard() {
+    if (committed_) return;
+    for (size_t s = 0; s < saved_.size(); ++s) {
+      cs_[s]->last_stream = saved_[s].first;
+      cs_[s]->last_fence = saved_[s].second;
+    }
+  }
+
+ private:
+  pfmpe_ctx* const* cs_;
+  std::vector<std::pair<hipStream_t, std::shared_ptr<BatchFence>>> saved_;
+  bool committed_ = false;
+};
 
 // Batch scratch layout (pfmpe_step_multi), the same in the pinned host image and in HBM: host-supplied blob
 // tables [0, tbytes), then `na` stream descriptors from doff, then the uint16 block -> stream map of `total`
@@ -533,9 +728,9 @@ inline const void* pk_kernel() {
 // early).  Zero them once `on` has drained, as abandoned() does for a one-launch frame; the prior is untouched.
 inline int reset_handoffs(pfmpe_ctx* c, hipStream_t on) {
   HIPCHK(c, hipStreamSynchronize(on));
-  HIPCHK(c, hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_counters, 0, counters_bytes(c), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_winkey, 0, kWinBytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_ctrl.get(), 0, sizeof(Ctrl), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counters.get(), 0, counters_bytes(c), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_winkey.get(), 0, kWinBytes, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PFMPE_OK;
 }
@@ -544,10 +739,10 @@ inline int reset_handoffs(pfmpe_ctx* c, hipStream_t on) {
 // hand-off state, stop fusing on this context; the caller redoes the frame with two launches.
 inline int abandoned(pfmpe_ctx* c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_counters, 0, counters_bytes(c), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_winkey, 0, kWinBytes, c->stream));
-  if (c->d_flat) HIPCHK(c, hipMemsetAsync(c->d_flat, 0, kFlatWords * sizeof(uint32_t), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counters.get(), 0, counters_bytes(c), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_ctrl.get(), 0, sizeof(Ctrl), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_winkey.get(), 0, kWinBytes, c->stream));
+  if (c->d_flat.get()) HIPCHK(c, hipMemsetAsync(c->d_flat.get(), 0, kFlatWords * sizeof(uint32_t), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->flat_base_w = c->flat_base_c = 0;
   c->fused_fallbacks += 1;
@@ -564,7 +759,7 @@ inline int abandoned(pfmpe_ctx* c) {
 constexpr uint32_t kGranFrames = 0xFFFFF;
 inline int next_gtag(pfmpe_ctx* c, uint32_t* gtag) {
   if (c->gframe >= kGranFrames) {
-    HIPCHK(c, hipMemsetAsync(c->d_gran, 0, kGranBytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_gran.get(), 0, kGranBytes, c->stream));
     c->gframe = 0;
   }
   c->gframe += 1;
@@ -572,20 +767,20 @@ inline int next_gtag(pfmpe_ctx* c, uint32_t* gtag) {
   return PFMPE_OK;
 }
 inline BlockPart* gran_part(const pfmpe_ctx* c, int parity) {
-  return (BlockPart*)(c->d_gran + (size_t)parity * kGranPartBytes);
+  return (BlockPart*)(c->d_gran.get() + (size_t)parity * kGranPartBytes);
 }
-inline CountPart* gran_count(const pfmpe_ctx* c) { return (CountPart*)(c->d_gran + kGranCountOff); }
+inline CountPart* gran_count(const pfmpe_ctx* c) { return (CountPart*)(c->d_gran.get() + kGranCountOff); }
 
 template <typename T, int RNG, int MAXM, typename SP>
 struct Seq {
   static int iterate(pfmpe_ctx* c, const FrameArgsT<T>& fa, const unsigned char* table, int iter) {
-    const SP* prior = (const SP*)c->d_state[c->prior_idx];
+    const SP* prior = (const SP*)c->d_state[c->prior_idx].get();
     const size_t lds = BlobTable<T>::lds_bytes(fa.tbytes);
-    uint32_t* gcount = c->d_counters;
-    uint32_t* tcount = c->d_counters + c->max_grp;
+    uint32_t* gcount = c->d_counters.get();
+    uint32_t* tcount = c->d_counters.get() + c->max_grp;
     RET(ensure_prop(c));
-    SP* prop0 = c->keep_prop ? (SP*)c->d_prop[0] : nullptr;
-    SP* prop1 = c->keep_prop ? (SP*)c->d_prop[1] : nullptr;
+    SP* prop0 = c->keep_prop ? (SP*)c->d_prop[0].get() : nullptr;
+    SP* prop1 = c->keep_prop ? (SP*)c->d_prop[1].get() : nullptr;
     // The streaming weighing pass (k_weigh_stream: resident blocks looping over the 256-particle blocks, the
     // next particle's state prefetched) with the group / top hand-off as two small launches.  It wins for
     // every marker bucket: C5 52 -> 31 us weighing (round 2), C4 265 -> 233 us; at 12 markers (C3) it lost while
@@ -615,25 +810,25 @@ struct Seq {
       RET(launch_ext(c, PFMPE_K_PROPAGATE, [&] {
         if constexpr (kPkInstance<T, RNG, MAXM, SP>) {
           if (pk) {
-            klaunch(c, k_weigh_pk<SP>, dim3(grid), dim3(kBlock), lds, fa, table, prior, (float*)c->d_w[0],
-                    (float*)c->d_w[1], c->d_part[0], c->d_part[1], (const Ctrl*)c->d_ctrl, prop0, prop1, iter);
+            klaunch(c, k_weigh_pk<SP>, dim3(grid), dim3(kBlock), lds, fa, table, prior, (float*)c->d_w[0].get(),
+                    (float*)c->d_w[1].get(), c->d_part[0].get(), c->d_part[1].get(), (const Ctrl*)c->d_ctrl.get(), prop0, prop1, iter);
             return;
           }
         }
         if constexpr (kPk12Instance<T, RNG, MAXM, SP>) {
           if (pk) {
-            klaunch(c, k_weigh_pk12<SP>, dim3(grid), dim3(kBlock), lds, fa, table, prior, (float*)c->d_w[0],
-                    (float*)c->d_w[1], c->d_part[0], c->d_part[1], (const Ctrl*)c->d_ctrl, prop0, prop1, iter);
+            klaunch(c, k_weigh_pk12<SP>, dim3(grid), dim3(kBlock), lds, fa, table, prior, (float*)c->d_w[0].get(),
+                    (float*)c->d_w[1].get(), c->d_part[0].get(), c->d_part[1].get(), (const Ctrl*)c->d_ctrl.get(), prop0, prop1, iter);
             return;
           }
         }
         if (c->prune)
           klaunch(c, k_weigh_stream<T, RNG, MAXM, true, SP>, dim3(grid), dim3(kBlock), lds, fa,
-                             table, prior, (T*)c->d_w[0], (T*)c->d_w[1], c->d_part[0], c->d_part[1], c->d_ctrl, prop0,
+                             table, prior, (T*)c->d_w[0].get(), (T*)c->d_w[1].get(), c->d_part[0].get(), c->d_part[1].get(), c->d_ctrl.get(), prop0,
                              prop1, iter);
         else
           klaunch(c, k_weigh_stream<T, RNG, MAXM, false, SP>, dim3(grid), dim3(kBlock), lds, fa,
-                             table, prior, (T*)c->d_w[0], (T*)c->d_w[1], c->d_part[0], c->d_part[1], c->d_ctrl, prop0,
+                             table, prior, (T*)c->d_w[0].get(), (T*)c->d_w[1].get(), c->d_part[0].get(), c->d_part[1].get(), c->d_ctrl.get(), prop0,
                              prop1, iter);
       }));
       // the top's group partials fit LDS up to 1,365 groups (22M particles); beyond, it reads them from L2
@@ -641,47 +836,47 @@ struct Seq {
       const bool staged = glds > 0 && glds <= 64 * 1024;
       if (fa.ngrp <= 64 && !(c->diag & kDiagSerialTop))  // one tile: group scans + top in one launch
         return launch_ext(c, PFMPE_K_AUX, [&] {
-          klaunch(c, k_group_top<T, RNG>, dim3(fa.ngrp), dim3(64), 0, fa, c->d_part[0], c->d_part[1], c->d_bscan[0],
-                  c->d_bscan[1], c->d_gpart[0], c->d_gpart[1], c->d_gscan, c->d_ctrl, tcount, iter);
+          klaunch(c, k_group_top<T, RNG>, dim3(fa.ngrp), dim3(64), 0, fa, c->d_part[0].get(), c->d_part[1].get(), c->d_bscan[0].get(),
+                  c->d_bscan[1].get(), c->d_gpart[0].get(), c->d_gpart[1].get(), c->d_gscan.get(), c->d_ctrl.get(), tcount, iter);
         });
       return launch_ext(c, PFMPE_K_AUX, [&] {
-        klaunch(c, k_group<T>, dim3(fa.ngrp), dim3(64), 0, fa, c->d_part[0], c->d_part[1],
-                           c->d_bscan[0], c->d_bscan[1], c->d_gpart[0], c->d_gpart[1], (const Ctrl*)c->d_ctrl);
+        klaunch(c, k_group<T>, dim3(fa.ngrp), dim3(64), 0, fa, c->d_part[0].get(), c->d_part[1].get(),
+                           c->d_bscan[0].get(), c->d_bscan[1].get(), c->d_gpart[0].get(), c->d_gpart[1].get(), (const Ctrl*)c->d_ctrl.get());
         if (staged && fa.ngrp <= 64 * kTopMaxTiles && !(c->diag & kDiagSerialTop))  // > 1 tile: k_top_wide
-          klaunch(c, k_top_wide<T, RNG>, dim3(1), dim3(64 * kTopWaves), glds, fa, c->d_gpart[0], c->d_gpart[1],
-                  c->d_gscan, c->d_ctrl, iter);
+          klaunch(c, k_top_wide<T, RNG>, dim3(1), dim3(64 * kTopWaves), glds, fa, c->d_gpart[0].get(), c->d_gpart[1].get(),
+                  c->d_gscan.get(), c->d_ctrl.get(), iter);
         else
-          klaunch(c, k_top<T, RNG>, dim3(1), dim3(64), staged ? glds : 0, fa, c->d_gpart[0],
-                             c->d_gpart[1], c->d_gscan, c->d_ctrl, iter, staged ? 1 : 0);
+          klaunch(c, k_top<T, RNG>, dim3(1), dim3(64), staged ? glds : 0, fa, c->d_gpart[0].get(),
+                             c->d_gpart[1].get(), c->d_gscan.get(), c->d_ctrl.get(), iter, staged ? 1 : 0);
       });
     }
     return launch_ext(c, PFMPE_K_PROPAGATE, [&] {
       if (c->prune)
         klaunch(c, k_propagate_weigh<T, RNG, MAXM, true, SP>, dim3(fa.nblk), dim3(kBlock), lds, fa,
-                           table, prior, (T*)c->d_w[0], (T*)c->d_w[1], c->d_part[0], c->d_part[1], c->d_bscan[0],
-                           c->d_bscan[1], c->d_gpart[0], c->d_gpart[1], c->d_gscan, c->d_ctrl, gcount, tcount, prop0,
-                           prop1, iter, c->d_stamps);
+                           table, prior, (T*)c->d_w[0].get(), (T*)c->d_w[1].get(), c->d_part[0].get(), c->d_part[1].get(), c->d_bscan[0].get(),
+                           c->d_bscan[1].get(), c->d_gpart[0].get(), c->d_gpart[1].get(), c->d_gscan.get(), c->d_ctrl.get(), gcount, tcount, prop0,
+                           prop1, iter, c->d_stamps.get());
       else
         klaunch(c, k_propagate_weigh<T, RNG, MAXM, false, SP>, dim3(fa.nblk), dim3(kBlock), lds, fa,
-                           table, prior, (T*)c->d_w[0], (T*)c->d_w[1], c->d_part[0], c->d_part[1], c->d_bscan[0],
-                           c->d_bscan[1], c->d_gpart[0], c->d_gpart[1], c->d_gscan, c->d_ctrl, gcount, tcount, prop0,
-                           prop1, iter, c->d_stamps);
+                           table, prior, (T*)c->d_w[0].get(), (T*)c->d_w[1].get(), c->d_part[0].get(), c->d_part[1].get(), c->d_bscan[0].get(),
+                           c->d_bscan[1].get(), c->d_gpart[0].get(), c->d_gpart[1].get(), c->d_gscan.get(), c->d_ctrl.get(), gcount, tcount, prop0,
+                           prop1, iter, c->d_stamps.get());
     });
   }
   static int finish(pfmpe_ctx* c, const FrameArgsT<T>& fa, const unsigned char* table) {
-    const SP* prior = (const SP*)c->d_state[c->prior_idx];
-    SP* post = (SP*)c->d_state[1 - c->prior_idx];
-    uint32_t* gcount = c->d_counters + c->max_grp + 1;
-    uint32_t* tcount = c->d_counters + 2 * c->max_grp + 1;
+    const SP* prior = (const SP*)c->d_state[c->prior_idx].get();
+    SP* post = (SP*)c->d_state[1 - c->prior_idx].get();
+    uint32_t* gcount = c->d_counters.get() + c->max_grp + 1;
+    uint32_t* tcount = c->d_counters.get() + 2 * c->max_grp + 1;
     c->seq = (c->seq + 1) & 0x3fffffff;
     const int32_t seq = c->seq;
-    const bool kept = c->keep_prop && c->d_prop[0];  // iterate() allocated them
+    const bool kept = c->keep_prop && c->d_prop[0].get();  // iterate() allocated them
     // deferred resampling: the new prior's owner indices go to the owner buffer the current prior does not use
     FrameArgsT<T> far = fa;
     c->frame_owner_out = -1;
-    if (kept && c->defer && c->d_owner[0] && c->d_owner[1] && !(c->diag & kDiagNoDefer)) {
+    if (kept && c->defer && c->d_owner[0].get() && c->d_owner[1].get() && !(c->diag & kDiagNoDefer)) {
       c->frame_owner_out = c->prior_owner == 0 ? 1 : 0;
-      far.owner_out = c->d_owner[c->frame_owner_out];
+      far.owner_out = c->d_owner[c->frame_owner_out].get();
     }
     bool owners = false;
     RET(launch_ext(c, PFMPE_K_RESAMPLE, [&] {
@@ -690,26 +885,26 @@ struct Seq {
       if (far.owner_out && !(c->diag & kDiagBlockResample)) {
         owners = true;
         klaunch(c, k_resample_owners<T, RNG, MAXM, SP>, dim3((unsigned)((fa.nblk + kWaves - 1) / kWaves)),
-                dim3(kBlock), 0, far, c->d_ctrl, prior, (const T*)c->d_w[0], (const T*)c->d_w[1], c->d_bscan[0],
-                c->d_bscan[1], c->d_gscan, c->record_counts ? c->d_counts : nullptr, c->d_mlpose, c->d_winkey,
-                win_arrive(c->d_winkey), table, c->d_out, seq, c->d_stamps);
+                dim3(kBlock), 0, far, c->d_ctrl.get(), prior, (const T*)c->d_w[0].get(), (const T*)c->d_w[1].get(), c->d_bscan[0].get(),
+                c->d_bscan[1].get(), c->d_gscan.get(), c->record_counts ? c->d_counts.get() : nullptr, c->d_mlpose.get(), c->d_winkey.get(),
+                win_arrive(c->d_winkey.get()), table, c->h_rec.dev(), seq, c->d_stamps.get());
         return;
       }
       // the kept-set variant compiles the regeneration path out (its registers spilled in the generic form)
       auto k = kept ? k_resample<T, RNG, MAXM, SP, true> : k_resample<T, RNG, MAXM, SP, false>;
-      klaunch(c, k, dim3(fa.nblk), dim3(kBlock), 0, far, c->d_ctrl, table,
-                         prior, post, (const T*)c->d_w[0], (const T*)c->d_w[1], c->d_bscan[0], c->d_bscan[1],
-                         c->d_gscan, c->d_cpart, c->d_cgroup, gcount, tcount,
-                         c->record_counts ? c->d_counts : nullptr, c->d_cand, c->d_mlpose, c->d_out, seq,
-                         c->d_stamps, kept ? (const SP*)c->d_prop[0] : nullptr,
-                         kept ? (const SP*)c->d_prop[1] : nullptr, c->d_winkey);
+      klaunch(c, k, dim3(fa.nblk), dim3(kBlock), 0, far, c->d_ctrl.get(), table,
+                         prior, post, (const T*)c->d_w[0].get(), (const T*)c->d_w[1].get(), c->d_bscan[0].get(), c->d_bscan[1].get(),
+                         c->d_gscan.get(), c->d_cpart.get(), c->d_cgroup.get(), gcount, tcount,
+                         c->record_counts ? c->d_counts.get() : nullptr, c->d_cand.get(), c->d_mlpose.get(), c->h_rec.dev(), seq,
+                         c->d_stamps.get(), kept ? (const SP*)c->d_prop[0].get() : nullptr,
+                         kept ? (const SP*)c->d_prop[1].get() : nullptr, c->d_winkey.get());
     }));
     c->last_resample = owners ? PFMPE_RESAMPLE_OWNERS : PFMPE_RESAMPLE_BLOCKS;
     if (!owners)
       RET(launch_ext(c, PFMPE_K_FINAL, [&] {
         klaunch(c, k_resample_final<T, RNG, MAXM, SP>, dim3(1), dim3(kFinalBlock), BlobTable<T>::bytes(fa.B), fa,
-                c->d_ctrl, table, prior, c->d_cpart, c->d_cand, c->d_mlpose, c->d_out, seq, c->d_stamps, kept ? 1 : 0,
-                c->d_winkey);
+                c->d_ctrl.get(), table, prior, c->d_cpart.get(), c->d_cand.get(), c->d_mlpose.get(), c->h_rec.dev(), seq, c->d_stamps.get(), kept ? 1 : 0,
+                c->d_winkey.get());
       }));
     if (const int rc = wait_frame(c); rc != PFMPE_OK) {
       const std::string err = c->err;
@@ -723,7 +918,7 @@ struct Seq {
   template <bool PRUNE>
   static int frame_fused(pfmpe_ctx* c, const FrameArgsT<T>& fa_in, const unsigned char* table, bool* launched) {
     *launched = false;
-    const bool flat = c->fused == 2 && fa_in.nblk <= kFlatMaxGroups * kGroup && fa_in.gsz == kGroup && c->d_flat;
+    const bool flat = c->fused == 2 && fa_in.nblk <= kFlatMaxGroups * kGroup && fa_in.gsz == kGroup && c->d_flat.get();
     const void* fn = flat ? (const void*)k_frame2<T, RNG, MAXM, PRUNE, SP> : (const void*)k_frame<T, RNG, MAXM, PRUNE, SP>;
     const size_t lds = BlobTable<T>::lds_bytes(fa_in.tbytes);
     auto key = std::make_pair(fn, lds);
@@ -756,29 +951,29 @@ struct Seq {
     // (the flat count barrier's poll covers <= kFlatMaxGroups * kGroup blocks: at most 2 per CU on 256 CUs)
     const bool tree_count = !flat && ((c->diag & kDiagTreeCount) || a.nblk > kFlatMaxGroups * kGroup);
     if (!tree_count) RET(next_gtag(c, &a.gtag));
-    const SP* prior = (const SP*)c->d_state[c->prior_idx];
-    SP* post = (SP*)c->d_state[1 - c->prior_idx];
-    T* w0 = (T*)c->d_w[0];
-    T* w1 = (T*)c->d_w[1];
-    uint32_t* gcount_w = c->d_counters;
-    uint32_t* tcount_w = c->d_counters + c->max_grp;
-    uint32_t* gcount_r = c->d_counters + c->max_grp + 1;
-    uint32_t* tcount_r = c->d_counters + 2 * c->max_grp + 1;
-    uint32_t* counts = c->record_counts ? c->d_counts : nullptr;
+    const SP* prior = (const SP*)c->d_state[c->prior_idx].get();
+    SP* post = (SP*)c->d_state[1 - c->prior_idx].get();
+    T* w0 = (T*)c->d_w[0].get();
+    T* w1 = (T*)c->d_w[1].get();
+    uint32_t* gcount_w = c->d_counters.get();
+    uint32_t* tcount_w = c->d_counters.get() + c->max_grp;
+    uint32_t* gcount_r = c->d_counters.get() + c->max_grp + 1;
+    uint32_t* tcount_r = c->d_counters.get() + 2 * c->max_grp + 1;
+    uint32_t* counts = c->record_counts ? c->d_counts.get() : nullptr;
     c->seq = (c->seq + 1) & 0x3fffffff;
     int32_t seq = c->seq;
     RET(launch_ext(c, PFMPE_K_FRAME, [&] {
       if (flat)
         klaunch(c, k_frame2<T, RNG, MAXM, PRUNE, SP>, dim3(a.nblk), dim3(kBlock), lds, a, table,
-                           prior, post, w0, w1, gran_part(c, 0), gran_part(c, 1), c->d_ctrl, gran_count(c), c->d_flat,
-                           counts, c->d_cand, c->d_mlpose, c->d_out, seq, c->d_stamps);
+                           prior, post, w0, w1, gran_part(c, 0), gran_part(c, 1), c->d_ctrl.get(), gran_count(c), c->d_flat.get(),
+                           counts, c->d_cand.get(), c->d_mlpose.get(), c->h_rec.dev(), seq, c->d_stamps.get());
       else
         klaunch(c, k_frame<T, RNG, MAXM, PRUNE, SP>, dim3(a.nblk), dim3(kBlock), lds, a, table,
-                           prior, post, w0, w1, c->d_part[0], c->d_part[1], c->d_bscan[0], c->d_bscan[1],
-                           c->d_gpart[0], c->d_gpart[1], c->d_gscan, c->d_ctrl,
-                           tree_count ? c->d_cpart : gran_count(c), c->d_cgroup, gcount_w,
-                           tcount_w, gcount_r, tcount_r, c->d_gen, counts, c->d_cand, c->d_mlpose, c->d_out, seq,
-                           c->d_stamps, tree_count ? nullptr : c->d_flat);
+                           prior, post, w0, w1, c->d_part[0].get(), c->d_part[1].get(), c->d_bscan[0].get(), c->d_bscan[1].get(),
+                           c->d_gpart[0].get(), c->d_gpart[1].get(), c->d_gscan.get(), c->d_ctrl.get(),
+                           tree_count ? c->d_cpart.get() : gran_count(c), c->d_cgroup.get(), gcount_w,
+                           tcount_w, gcount_r, tcount_r, c->d_gen.get(), counts, c->d_cand.get(), c->d_mlpose.get(), c->h_rec.dev(), seq,
+                           c->d_stamps.get(), tree_count ? nullptr : c->d_flat.get());
     }));
     *launched = true;
     if (wait_frame(c) != PFMPE_OK) {
@@ -787,7 +982,7 @@ struct Seq {
       return PFMPE_OK;
     }
     if (flat || !(c->diag & kDiagTreeCount)) {  // the flat counters' new running totals (k_frame: the count set only)
-      const OutDev& o = *(const OutDev*)c->h_out;
+      const OutDev& o = *c->h_out;
       if (flat) c->flat_base_w += (uint32_t)o.iters * (uint32_t)a.nblk;
       if (o.resampled) c->flat_base_c += (uint32_t)a.nblk;
     }
@@ -912,45 +1107,45 @@ struct Seq {
         std::memset((void*)&x, 0, sizeof(Desc));
         x.fa = fa;
         x.table = tables[act[i]];
-        x.prior = (const SP*)c->d_state[c->prior_idx];
-        x.post = (SP*)c->d_state[1 - c->prior_idx];
-        x.w0 = (T*)c->d_w[0];
-        x.w1 = (T*)c->d_w[1];
-        x.part0 = c->d_part[0];
-        x.part1 = c->d_part[1];
-        x.bscan0 = c->d_bscan[0];
-        x.bscan1 = c->d_bscan[1];
-        x.gpart0 = c->d_gpart[0];
-        x.gpart1 = c->d_gpart[1];
-        x.gscan = c->d_gscan;
-        x.ctrl = c->d_ctrl;
-        x.gcount_w = c->d_counters;
-        x.tcount_w = c->d_counters + c->max_grp;
-        x.gcount_r = c->d_counters + c->max_grp + 1;
-        x.tcount_r = c->d_counters + 2 * c->max_grp + 1;
+        x.prior = (const SP*)c->d_state[c->prior_idx].get();
+        x.post = (SP*)c->d_state[1 - c->prior_idx].get();
+        x.w0 = (T*)c->d_w[0].get();
+        x.w1 = (T*)c->d_w[1].get();
+        x.part0 = c->d_part[0].get();
+        x.part1 = c->d_part[1].get();
+        x.bscan0 = c->d_bscan[0].get();
+        x.bscan1 = c->d_bscan[1].get();
+        x.gpart0 = c->d_gpart[0].get();
+        x.gpart1 = c->d_gpart[1].get();
+        x.gscan = c->d_gscan.get();
+        x.ctrl = c->d_ctrl.get();
+        x.gcount_w = c->d_counters.get();
+        x.tcount_w = c->d_counters.get() + c->max_grp;
+        x.gcount_r = c->d_counters.get() + c->max_grp + 1;
+        x.tcount_r = c->d_counters.get() + 2 * c->max_grp + 1;
         // The stored set with deferred resampling (k_resample_multi writes owner indices; the kept buffer becomes the
         // stream's prior at take_step, as in finish()) for every state type; without deferral it pays in batches only
         // for fp16 state (round-3 A/B, DESIGN.md §4.2: 8 x C5 batches 5-8 % faster regenerating).  No choice here
         // changes a result.
-        const bool defer = c->defer && c->d_owner[0] && c->d_owner[1] && !(c->diag & kDiagNoDefer);
-        const bool kept = c->keep_prop && c->d_prop[0] && (defer || std::is_same<SP, __half>::value);
-        x.prop0 = kept ? (SP*)c->d_prop[0] : nullptr;
-        x.prop1 = kept ? (SP*)c->d_prop[1] : nullptr;
+        const bool defer = c->defer && c->d_owner[0].get() && c->d_owner[1].get() && !(c->diag & kDiagNoDefer);
+        const bool kept = c->keep_prop && c->d_prop[0].get() && (defer || std::is_same<SP, __half>::value);
+        x.prop0 = kept ? (SP*)c->d_prop[0].get() : nullptr;
+        x.prop1 = kept ? (SP*)c->d_prop[1].get() : nullptr;
         all_kept = all_kept && kept;
         c->frame_owner_out = -1;
         if (kept && defer) {
           c->frame_owner_out = c->prior_owner == 0 ? 1 : 0;
-          x.fa.owner_out = c->d_owner[c->frame_owner_out];
+          x.fa.owner_out = c->d_owner[c->frame_owner_out].get();
         } else {
           all_owners = false;
         }
-        x.cpart = c->d_cpart;
-        x.cgroup = c->d_cgroup;
-        x.counts = c->record_counts ? c->d_counts : nullptr;
-        x.cand = c->d_cand;
-        x.mlpose = c->d_mlpose;
-        x.out = c->d_out;
-        x.winkey = c->d_winkey;
+        x.cpart = c->d_cpart.get();
+        x.cgroup = c->d_cgroup.get();
+        x.counts = c->record_counts ? c->d_counts.get() : nullptr;
+        x.cand = c->d_cand.get();
+        x.mlpose = c->d_mlpose.get();
+        x.out = c->h_rec.dev();
+        x.winkey = c->d_winkey.get();
         c->seq = (c->seq + 1) & 0x3fffffff;
         x.seq = c->seq;
         x.first_blk = (int32_t)total;
@@ -1173,11 +1368,11 @@ int audit_batch(pfmpe_ctx* const* cs, int S, const FrameArgsT<T>* fas, const pfm
     if (c->state_dtype != PFMPE_STATE_F64 && (int64_t)kPlanes * c->ld * (int64_t)c->es >= ((int64_t)1 << 32))
       return bad(s, "plane buffer resource range");
     if (fa.M != c->M || fa.M < 1 || fa.M > c->max_markers || fa.B < 0 || fa.B > c->max_blobs) return bad(s, "M / B");
-    if (c->keep_prop && (!c->d_prop[0] || !c->d_prop[1])) return bad(s, "kept propagated set not allocated");
-    if (c->record_counts && !c->d_counts) return bad(s, "count buffer not allocated");
+    if (c->keep_prop && (!c->d_prop[0].get() || !c->d_prop[1].get())) return bad(s, "kept propagated set not allocated");
+    if (c->record_counts && !c->d_counts.get()) return bad(s, "count buffer not allocated");
     if (in[s].bank_frame >= 0) {
       const size_t f = (size_t)in[s].bank_frame;
-      if (!c->d_bank || f >= c->bank_B.size() || c->bank_B[f] != fa.B ||
+      if (!c->d_bank.get() || f >= c->bank_B.size() || c->bank_B[f] != fa.B ||
           c->bank_off[f] + (size_t)fa.tbytes != c->bank_off[f + 1] || fa.tbytes < (int)BlobTable<T>::bytes(fa.B))
         return bad(s, "bank table");
     } else if (toff[s] + (size_t)fa.tbytes > tbytes || fa.tbytes < (int)BlobTable<T>::bytes(fa.B)) {
@@ -1236,24 +1431,15 @@ int multi_m(pfmpe_ctx* const* cs, int S, const pfmpe_frame_in* in) {
                                      std::to_string(max_blocks) + " = " + std::to_string(max_blocks * kBlock) +
                                      " particles, PFMPE_OPT_MULTI_MAX_BLOCKS)");
   const size_t need = batch_layout<Desc>(S, total, tbytes).need;
-  if (need > c0->multi_cap) {
-    HIPCHK(c0, hipStreamSynchronize(c0->stream));
-    if (c0->d_multi) HIPCHK(c0, hipFree(c0->d_multi));
-    if (c0->h_multi) HIPCHK(c0, hipHostFree(c0->h_multi));
-    c0->d_multi = nullptr;
-    c0->h_multi = nullptr;
-    c0->hd_multi = nullptr;
-    c0->multi_cap = 0;
+  if (need > std::min(c0->d_multi.bytes(), c0->h_multi.bytes())) {
     c0->map_sig.clear();  // a new scratch holds no map
     const size_t cap = std::max(need * 2, (size_t)1 << 16);
-    HIPCHK(c0, hipMalloc((void**)&c0->d_multi, cap));
+    RET(c0->d_multi.grow(c0, need, cap));
     // read by k_stage_multi over PCIe: mapped, coherent (the host rewrites it between batches)
-    HIPCHK(c0, hipHostMalloc((void**)&c0->h_multi, cap, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(c0, hipHostGetDevicePointer((void**)&c0->hd_multi, c0->h_multi, 0));
-    c0->multi_cap = cap;
+    RET(c0->h_multi.grow(c0, need, cap));
   }
   for (int s = 0; s < S; ++s) RET(ensure_prop(cs[s]));
-  RET((audit_batch<T, SP>(cs, S, fas.data(), in, toff, tbytes, total, c0->multi_cap)));
+  RET((audit_batch<T, SP>(cs, S, fas.data(), in, toff, tbytes, total, c0->d_multi.bytes())));
   if (!c0->lead_fence) {  // created before any member's ordering state changes (no early return after)
     auto f = std::make_shared<BatchFence>();
     HIPCHK(c0, hipEventCreateWithFlags(&f->ev, hipEventDisableTiming));
@@ -1270,36 +1456,29 @@ int multi_m(pfmpe_ctx* const* cs, int S, const pfmpe_frame_in* in) {
   // order_after clears a member's ordering state; if a later member's ordering fails, the earlier ones get their
   // state back (their pending work is still unordered with their own streams)
   {
-    std::vector<std::pair<hipStream_t, std::shared_ptr<BatchFence>>> saved(S);
-    for (int s = 0; s < S; ++s) saved[s] = {cs[s]->last_stream, cs[s]->last_fence};
-    for (int s = 0; s < S; ++s)
-      if (const int r = order_after(cs[s], c0->stream, c0)) {
-        for (int e = 0; e < S; ++e) {
-          cs[e]->last_stream = saved[e].first;
-          cs[e]->last_fence = saved[e].second;
-        }
-        return r;
-      }
+    OrderGuard members(cs, S);
+    RET(members.order(0, c0->stream, c0));
+    members.commit();  // from here to the fence below there is no return
   }
   std::vector<const unsigned char*> tables(S);
   for (int s = 0; s < S; ++s) {
     pfmpe_ctx* c = cs[s];
     if (in[s].bank_frame >= 0) {
-      tables[s] = c->d_bank + c->bank_off[in[s].bank_frame];
+      tables[s] = c->d_bank.get() + c->bank_off[in[s].bank_frame];
     } else {
-      std::memcpy(c0->h_multi + toff[s], hosttab[s].data(), (size_t)fas[s].tbytes);
-      tables[s] = c0->d_multi + toff[s];
+      std::memcpy(c0->h_multi.get() + toff[s], hosttab[s].data(), (size_t)fas[s].tbytes);
+      tables[s] = c0->d_multi.get() + toff[s];
     }
   }
   int rc;
   if (all5)
-    rc = Seq<T, RNG, kExactM, SP>::step_multi(cs, S, fas.data(), tables.data(), c0->h_multi, c0->hd_multi, c0->d_multi, tbytes);
+    rc = Seq<T, RNG, kExactM, SP>::step_multi(cs, S, fas.data(), tables.data(), c0->h_multi.get(), c0->h_multi.dev(), c0->d_multi.get(), tbytes);
   else if (maxM <= 8)
-    rc = Seq<T, RNG, 8, SP>::step_multi(cs, S, fas.data(), tables.data(), c0->h_multi, c0->hd_multi, c0->d_multi, tbytes);
+    rc = Seq<T, RNG, 8, SP>::step_multi(cs, S, fas.data(), tables.data(), c0->h_multi.get(), c0->h_multi.dev(), c0->d_multi.get(), tbytes);
   else if (maxM <= 12)
-    rc = Seq<T, RNG, 12, SP>::step_multi(cs, S, fas.data(), tables.data(), c0->h_multi, c0->hd_multi, c0->d_multi, tbytes);
+    rc = Seq<T, RNG, 12, SP>::step_multi(cs, S, fas.data(), tables.data(), c0->h_multi.get(), c0->h_multi.dev(), c0->d_multi.get(), tbytes);
   else
-    rc = Seq<T, RNG, 16, SP>::step_multi(cs, S, fas.data(), tables.data(), c0->h_multi, c0->hd_multi, c0->d_multi, tbytes);
+    rc = Seq<T, RNG, 16, SP>::step_multi(cs, S, fas.data(), tables.data(), c0->h_multi.get(), c0->h_multi.dev(), c0->d_multi.get(), tbytes);
   // the batch's kernels may still be retiring when the records are in (or when a step failed part-way): each
   // member's next work on its own stream is ordered after the leader's stream through the fence, recorded when
   // that work comes (the leader's own stream is the batch stream).  Set whatever step_multi returned.

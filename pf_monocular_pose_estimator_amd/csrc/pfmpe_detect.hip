@@ -579,17 +579,8 @@ int det_buffers(pfmpe_ctx* c, int64_t npix, DetBuffers& b) {
   const size_t o_mask = 0, o_nbr = o_mask + al(npix), o_label = o_nbr + al(npix);
   const size_t o_count = o_label + al(npix * 4), o_roots = o_count + 256;
   const size_t o_rec = o_roots + al(kDetMaxComponents * 4), total = o_rec + al(kDetMaxComponents * sizeof(DetRecord));
-  if (total > c->det_cap) {
-    if (c->d_det) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipFree(c->d_det));
-      c->d_det = nullptr;
-      c->det_cap = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&c->d_det, total));
-    c->det_cap = total;
-  }
-  unsigned char* d = c->d_det;
+  RET(c->d_det.grow(c, total, total));
+  unsigned char* d = c->d_det.get();
   b = DetBuffers{d + o_mask, d + o_nbr, (int*)(d + o_label), (int*)(d + o_count), (int*)(d + o_roots),
                  (DetRecord*)(d + o_rec)};
   return PFMPE_OK;
@@ -646,19 +637,10 @@ int detm_buffers(pfmpe_ctx* c, int R, DetDesc* descs, size_t* o_work) {
     total += 2 * al256(npix) + al256(npix * 4) + al256(kDetMaxComponents * sizeof(int)) +
              al256(kDetMaxComponents * sizeof(DetRecord));
   }
-  if (total > c->detm_cap) {
-    if (c->d_detm) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipFree(c->d_detm));
-      c->d_detm = nullptr;
-      c->detm_cap = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&c->d_detm, total));
-    c->detm_cap = total;
-  }
+  RET(c->d_detm.grow(c, total, total));
   for (int r = 0; r < R; ++r) {
     const size_t npix = (size_t)descs[r].a.W * descs[r].a.H;
-    unsigned char* p = c->d_detm + base[r];
+    unsigned char* p = c->d_detm.get() + base[r];
     descs[r].mask = p;
     descs[r].nbr = (p += al256(npix));
     descs[r].label = (int*)(p += al256(npix));
@@ -705,17 +687,8 @@ int pfmpe_stage_image(pfmpe_ctx* c, const uint8_t* image, int width, int height,
   if (!image || width < 1 || height < 1 || pitch < width) return fail(c, PFMPE_E_ARG, "stage_image: bad image");
   RET(set_device(c));
   const size_t bytes = (size_t)pitch * height;
-  if (bytes > c->img_cap) {
-    if (c->d_img) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipFree(c->d_img));
-      c->d_img = nullptr;
-      c->img_cap = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&c->d_img, bytes));
-    c->img_cap = bytes;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_img, image, bytes, hipMemcpyHostToDevice, c->stream));
+  RET(c->d_img.grow(c, bytes, bytes));
+  HIPCHK(c, hipMemcpyAsync(c->d_img.get(), image, bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->img_w = width;
   c->img_h = height;
@@ -744,15 +717,12 @@ int pfmpe_find_leds(pfmpe_ctx* c, const uint8_t* image, int width, int height, i
   HIPCHK(c, hipMemsetAsync(b.count, 0, sizeof(int), c->stream));
   const unsigned g1 = (unsigned)((npix + 255) / 256);
   c->timing_now = c->timing > 0;
-  if (!c->h_det) {
-    HIPCHK(c, hipHostMalloc((void**)&c->h_det, sizeof(DetOutHost), hipHostMallocMapped | hipHostMallocCoherent));
-  }
-  DetOutHost* hout = (DetOutHost*)c->h_det;
-  DetOutHost* dout = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&dout, hout, 0));
+  RET(c->h_det.ensure(c, sizeof(DetOutHost)));
+  DetOutHost* hout = (DetOutHost*)c->h_det.get();
+  DetOutHost* dout = (DetOutHost*)c->h_det.dev();
   RET(launch(c, PFMPE_K_DETECT, [&] {
     hipLaunchKernelGGL(k_det_mask, dim3((W + kDetTile - 1) / kDetTile, (H + kDetTile - 1) / kDetTile),
-                       dim3(kDetTile * kDetTile), 0, c->stream, a, c->d_img, b.mask);
+                       dim3(kDetTile * kDetTile), 0, c->stream, a, c->d_img.get(), b.mask);
     hipLaunchKernelGGL(k_det_label, dim3((W + kLT - 1) / kLT, (H + kLT - 1) / kLT), dim3(kLabelBlock), 0, c->stream, a, b.mask,
                        b.nbr, b.label);
     hipLaunchKernelGGL(k_det_merge, dim3(g1), dim3(256), 0, c->stream, a, b.nbr, b.label);
@@ -794,24 +764,11 @@ int pfmpe_find_leds_multi(pfmpe_ctx* c, const uint8_t* image, int width, int hei
       return fail(c, PFMPE_E_ARG, "find_leds_multi: roi " + std::to_string(r) + ": " + why);
   if (image) RET(pfmpe_stage_image(c, image, width, height, pitch));
   RET(set_device(c));
-  if (!c->h_detm) {
-    HIPCHK(c, hipHostMalloc((void**)&c->h_detm, al256(sizeof(DetBatch)) + kDetMaxRois * sizeof(DetDesc),
-                            hipHostMallocMapped | hipHostMallocCoherent));
-  }
-  if (R > c->detm_out_cap) {
-    if (c->h_detm_out) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipHostFree(c->h_detm_out));
-      c->h_detm_out = nullptr;
-      c->detm_out_cap = 0;
-    }
-    HIPCHK(c, hipHostMalloc((void**)&c->h_detm_out, (size_t)R * sizeof(DetOutHost),
-                            hipHostMallocMapped | hipHostMallocCoherent));
-    c->detm_out_cap = R;
-  }
+  RET(c->h_detm.ensure(c, al256(sizeof(DetBatch)) + kDetMaxRois * sizeof(DetDesc)));
+  RET(c->h_detm_out.grow(c, (size_t)R * sizeof(DetOutHost), (size_t)R * sizeof(DetOutHost)));
   // the pinned image of the batch head and the descriptors, then one upload
-  DetBatch* hd = (DetBatch*)c->h_detm;
-  DetDesc* descs = (DetDesc*)(c->h_detm + al256(sizeof(DetBatch)));
+  DetBatch* hd = (DetBatch*)c->h_detm.get();
+  DetDesc* descs = (DetDesc*)(c->h_detm.get() + al256(sizeof(DetBatch)));
   std::memset(hd, 0, sizeof(*hd));
   hd->R = R;
   int n16 = 0, n32 = 0, npb = 0;
@@ -829,22 +786,20 @@ int pfmpe_find_leds_multi(pfmpe_ctx* c, const uint8_t* image, int width, int hei
   }
   size_t o_work = 0;
   RET(detm_buffers(c, R, descs, &o_work));
-  int* counters = (int*)c->d_detm;
-  const DetBatch* dhd = (const DetBatch*)(c->d_detm + kDetmHead);
-  const DetDesc* ddescs = (const DetDesc*)(c->d_detm + kDetmDesc);
-  uint32_t* work = (uint32_t*)(c->d_detm + o_work);
+  int* counters = (int*)c->d_detm.get();
+  const DetBatch* dhd = (const DetBatch*)(c->d_detm.get() + kDetmHead);
+  const DetDesc* ddescs = (const DetDesc*)(c->d_detm.get() + kDetmDesc);
+  uint32_t* work = (uint32_t*)(c->d_detm.get() + o_work);
   static_assert(sizeof(DetDesc) % sizeof(uint64_t) == 0, "k_detm_stage copies 8-byte words");
   const int stage_words = (int)((al256(sizeof(DetBatch)) + (size_t)R * sizeof(DetDesc)) / sizeof(uint64_t));
-  const uint64_t* stage_src = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&stage_src, c->h_detm, 0));
-  DetOutHost* hout = (DetOutHost*)c->h_detm_out;
-  DetOutHost* dout = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer((void**)&dout, hout, 0));
+  const uint64_t* stage_src = (const uint64_t*)c->h_detm.dev();
+  DetOutHost* hout = (DetOutHost*)c->h_detm_out.get();
+  DetOutHost* dout = (DetOutHost*)c->h_detm_out.dev();
   c->timing_now = c->timing > 0;
   RET(launch(c, PFMPE_K_DETECT, [&] {
     hipLaunchKernelGGL(k_detm_stage, dim3(1), dim3(kStageBlock), 0, c->stream, stage_src,
-                       (uint64_t*)(c->d_detm + kDetmHead), stage_words, counters);
-    hipLaunchKernelGGL(k_detm_mask, dim3(n16), dim3(kDetTile * kDetTile), 0, c->stream, dhd, ddescs, c->d_img);
+                       (uint64_t*)(c->d_detm.get() + kDetmHead), stage_words, counters);
+    hipLaunchKernelGGL(k_detm_mask, dim3(n16), dim3(kDetTile * kDetTile), 0, c->stream, dhd, ddescs, c->d_img.get());
     hipLaunchKernelGGL(k_detm_label, dim3(n32), dim3(kLabelBlock), 0, c->stream, dhd, ddescs);
     hipLaunchKernelGGL(k_detm_merge, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs);
     hipLaunchKernelGGL(k_detm_roots, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs, counters, work);

@@ -3,7 +3,7 @@
 // Replaces the PF block of PoseEstimator::estimateBodyPose (pf_mpe_lib/src/pose_estimator.cpp:475-733).
 // The launch sequences live in pfmpe_ctx.hpp (Seq) and are instantiated per (state type, RNG) in the
 // pfmpe_k_*.hip translation units.
-#include "pfmpe_ctx.hpp"
+#include "pfmpe_prior.hpp"
 #include "pf_gn.hpp"
 
 using namespace pfmpe;
@@ -23,94 +23,34 @@ using namespace pfmpe_impl;
 
 int dispatch_step(pfmpe_ctx* c, const pfmpe_frame_in* in, const unsigned char* table, size_t tbytes,
                   const GridHdr& gh) {
-  const bool ref = c->params.rng_mode == PFMPE_RNG_REFERENCE;
-  switch (c->state_dtype) {
-    case PFMPE_STATE_F64:
-      return ref ? dispatch_m<double, kRngReference, double>(c, in, table, tbytes, gh)
-                 : dispatch_m<double, kRngPhilox, double>(c, in, table, tbytes, gh);
-    case PFMPE_STATE_F16:
-      return ref ? dispatch_m<float, kRngReference, __half>(c, in, table, tbytes, gh)
-                 : dispatch_m<float, kRngPhilox, __half>(c, in, table, tbytes, gh);
-    default:
-      return ref ? dispatch_m<float, kRngReference, float>(c, in, table, tbytes, gh)
-                 : dispatch_m<float, kRngPhilox, float>(c, in, table, tbytes, gh);
-  }
+  return visit_state_rng(c, [&](auto s) {
+    using S = decltype(s);
+    return dispatch_m<typename S::T, S::RNG, typename S::SP>(c, in, table, tbytes, gh);
+  });
 }
 
 int dispatch_regen(pfmpe_ctx* c, int kept_iter, const void* prior, double* out) {
-  const bool ref = c->params.rng_mode == PFMPE_RNG_REFERENCE;
-  switch (c->state_dtype) {
-    case PFMPE_STATE_F64:
-      return ref ? regen_m<double, kRngReference, double>(c, kept_iter, prior, out)
-                 : regen_m<double, kRngPhilox, double>(c, kept_iter, prior, out);
-    case PFMPE_STATE_F16:
-      return ref ? regen_m<float, kRngReference, __half>(c, kept_iter, prior, out)
-                 : regen_m<float, kRngPhilox, __half>(c, kept_iter, prior, out);
-    default:
-      return ref ? regen_m<float, kRngReference, float>(c, kept_iter, prior, out)
-                 : regen_m<float, kRngPhilox, float>(c, kept_iter, prior, out);
-  }
+  return visit_state_rng(c, [&](auto s) {
+    using S = decltype(s);
+    return regen_m<typename S::T, S::RNG, typename S::SP>(c, kept_iter, prior, out);
+  });
 }
-
-// state import / export for the three storage types (anchor: fp16 state only)
-template <typename T, typename SP>
-void launch_import(pfmpe_ctx* c, int N, const double* anchor) {
-  Pose12<T> a;
-  for (int q = 0; q < 12; ++q) a.v[q] = (T)anchor[q];
-  hipLaunchKernelGGL((k_import<T, SP>), dim3((N + 255) / 256), dim3(256), 0, c->stream, c->d_xfer,
-                     (SP*)c->d_state[c->prior_idx], N, c->ld, a);
-}
-template <typename T, typename SP>
-void launch_export(pfmpe_ctx* c, int N, const double* anchor) {
-  Pose12<T> a;
-  for (int q = 0; q < 12; ++q) a.v[q] = (T)anchor[q];
-  hipLaunchKernelGGL((k_export<T, SP>), dim3((N + 255) / 256), dim3(256), 0, c->stream,
-                     (const SP*)c->d_state[c->prior_idx], c->d_xfer, N, c->ld, a, prior_owner_ptr(c));
-}
-
 
 // byte offset of a table's GridHdr
 size_t grid_off(const pfmpe_ctx* c, int B) {
-  return c->state_dtype == PFMPE_STATE_F64 ? BlobTable<double>::off_grid(B) : BlobTable<float>::off_grid(B);
+  return visit_state(c, [&](auto s) { return BlobTable<typename decltype(s)::T>::off_grid(B); });
 }
 // largest blob table of this context's type (base part at kMaxBlobs + the largest grid)
 size_t table_max_bytes(const pfmpe_ctx* c) {
-  return c->state_dtype == PFMPE_STATE_F64 ? BlobTable<double>::max_bytes() : BlobTable<float>::max_bytes();
+  return visit_state(c, [&](auto s) { return BlobTable<typename decltype(s)::T>::max_bytes(); });
 }
 // the frame's blob table for the context's current parameters (pruning half-window as build_args computes
 // it); returns its size
 size_t build_table(const pfmpe_ctx* c, const double* blobs, int B, unsigned char* dst) {
-  const double tolq = c->state_dtype == PFMPE_STATE_F64 ? (c->params.tol_pf * (1.0 + 1e-3) + 1e-3)
-                                                        : (double)(float)(c->params.tol_pf * (1.0 + 1e-3) + 1e-3);
-  if (c->state_dtype == PFMPE_STATE_F64) return build_blob_table_host<double>(blobs, B, tolq, dst);
-  return build_blob_table_host<float>(blobs, B, tolq, dst);
-}
-
-
-void free_all(pfmpe_ctx* c) {
-  void* dev[] = {c->d_state[0], c->d_state[1], c->d_w[0], c->d_w[1], c->d_prop[0], c->d_prop[1], c->d_part[0], c->d_part[1],
-                 c->d_bscan[0], c->d_bscan[1], c->d_gpart[0], c->d_gpart[1], c->d_gscan, c->d_cpart, c->d_winkey,
-                 c->d_cgroup, c->d_counters, c->d_ctrl, c->d_gen, c->d_cand, c->d_mlpose, c->d_flat, c->d_roi, c->d_cloud, c->d_assoc, c->d_pairs, c->d_refine, c->d_gran, c->d_init, c->d_det, c->d_img, c->d_table, c->d_bank, c->d_xfer, c->d_counts,
-                 c->d_stamps, c->d_owner[0], c->d_owner[1]};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (c->h_rec) (void)hipHostFree(c->h_rec);
-  delete c->h_out;
-  c->h_out = nullptr;
-  if (c->h_table) (void)hipHostFree(c->h_table);
-  if (c->h_det) (void)hipHostFree(c->h_det);
-  if (c->d_detm) (void)hipFree(c->d_detm);
-  if (c->h_detm) (void)hipHostFree(c->h_detm);
-  if (c->h_detm_out) (void)hipHostFree(c->h_detm_out);
-  if (c->d_roim) (void)hipFree(c->d_roim);
-  if (c->h_roim) (void)hipHostFree(c->h_roim);
-  for (auto& e : c->ev_pool) {
-    (void)hipEventDestroy(e.a);
-    (void)hipEventDestroy(e.b);
-  }
-  if (c->d_multi) (void)hipFree(c->d_multi);
-  if (c->h_multi) (void)hipHostFree(c->h_multi);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  return visit_state(c, [&](auto s) {
+    using T = typename decltype(s)::T;
+    return build_blob_table_host<T>(blobs, B, (double)(T)(c->params.tol_pf * (1.0 + 1e-3) + 1e-3), dst);
+  });
 }
 
 // pfmpe_step's argument and state checks (also per stream of pfmpe_step_multi)
@@ -124,7 +64,7 @@ int check_step(pfmpe_ctx* c, const pfmpe_frame_in* in, const pfmpe_frame_out* ou
   if (in->it_since_init >= 2 && !(in->dt != 0.0))
     return fail(c, PFMPE_E_ARG, "step: dt must be non-zero in steady state");
   if (in->bank_frame >= 0) {
-    if (!c->d_bank || in->bank_frame >= (int)c->bank_B.size())
+    if (!c->d_bank.get() || in->bank_frame >= (int)c->bank_B.size())
       return fail(c, PFMPE_E_ARG, "step: bank_frame out of range");
     if (c->bank_B[in->bank_frame] != in->B) return fail(c, PFMPE_E_ARG, "step: B does not match the staged bank frame");
   } else if (in->B > 0 && !in->blobs) {
@@ -135,7 +75,7 @@ int check_step(pfmpe_ctx* c, const pfmpe_frame_in* in, const pfmpe_frame_out* ou
 
 // the frame record into pfmpe_frame_out, and the context's state after the frame (PE:681, 727)
 void take_step(pfmpe_ctx* c, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
-  const OutDev& o = *(const OutDev*)c->h_out;
+  const OutDev& o = *c->h_out;
   out->iters = o.iters;
   out->kept_iter = o.kept_iter;
   out->most_likely_idx = o.most_likely_idx;
@@ -160,7 +100,7 @@ void take_step(pfmpe_ctx* c, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
         c->d_prop[o.kept_slot]) {
       // deferred resampling: the kept buffer is the new prior's storage (read through the owner indices k_resample
       // wrote); the unused post buffer becomes that weight slot's kept buffer for the next frame
-      std::swap(c->d_prop[o.kept_slot], c->d_state[1 - c->prior_idx]);
+      c->d_prop[o.kept_slot].swap(c->d_state[1 - c->prior_idx]);
       c->prior_owner = c->frame_owner_out;
     } else {
       c->prior_owner = -1;
@@ -221,7 +161,6 @@ int pfmpe_create(pfmpe_ctx** out, int hip_device, int max_particles, int max_mar
   }
   pfmpe_default_params(&c->params);
   auto bad = [&](int code) {
-    free_all(c);
     delete c;
     return code;
   };
@@ -229,53 +168,53 @@ int pfmpe_create(pfmpe_ctx** out, int hip_device, int max_particles, int max_mar
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bad(PFMPE_E_HIP);
   const size_t state_bytes = (size_t)kPlanes * c->ld * c->es;
   bool ok = true;
+  auto got = [&](int rc) { ok = ok && rc == PFMPE_OK; };
   c->max_grp = c->max_blk;  // groups hold ~sqrt(blocks) blocks (build_args): size group buffers per block
   for (int i = 0; i < 2; ++i) {
-    ok &= hipMalloc(&c->d_state[i], state_bytes) == hipSuccess;
-    ok &= hipMalloc(&c->d_w[i], (size_t)c->max_blk * kBlock * c->ws) == hipSuccess;  // whole blocks: k_resample_owners
+    got(c->d_state[i].alloc(c, state_bytes));
+    got(c->d_w[i].alloc(c, (size_t)c->max_blk * kBlock * c->ws));  // whole blocks: k_resample_owners
     // kWaves entries per block: the streaming weighing pass stores wave partials (k_group combines them)
-    ok &= hipMalloc((void**)&c->d_part[i], (size_t)c->max_blk * kWaves * sizeof(BlockPart)) == hipSuccess;
-    ok &= hipMalloc((void**)&c->d_bscan[i], (size_t)c->max_blk * sizeof(BlockScan)) == hipSuccess;
-    ok &= hipMalloc((void**)&c->d_gpart[i], (size_t)c->max_grp * sizeof(GroupPart)) == hipSuccess;
+    got(c->d_part[i].alloc(c, (size_t)c->max_blk * kWaves * sizeof(BlockPart)));
+    got(c->d_bscan[i].alloc(c, (size_t)c->max_blk * sizeof(BlockScan)));
+    got(c->d_gpart[i].alloc(c, (size_t)c->max_grp * sizeof(GroupPart)));
   }
-  ok &= hipMalloc((void**)&c->d_gscan, (size_t)c->max_grp * sizeof(GroupScan)) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_cpart, (size_t)(c->max_blk + 1) * sizeof(CountPart)) == hipSuccess;  // +1: 16-B reads
-  ok &= hipMalloc((void**)&c->d_cgroup, (size_t)c->max_grp * sizeof(CountPart)) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_winkey, kWinBytes) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_counters, counters_bytes(c)) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_ctrl, sizeof(Ctrl)) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_gen, sizeof(uint32_t)) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_cand, (size_t)c->max_blk * sizeof(Cand)) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_mlpose, 12 * sizeof(double)) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_flat, kFlatWords * sizeof(uint32_t)) == hipSuccess;
-  ok &= hipMalloc((void**)&c->d_gran, kGranBytes) == hipSuccess;
+  got(c->d_gscan.alloc(c, (size_t)c->max_grp * sizeof(GroupScan)));
+  got(c->d_cpart.alloc(c, (size_t)(c->max_blk + 1) * sizeof(CountPart)));  // +1: 16-B reads
+  got(c->d_cgroup.alloc(c, (size_t)c->max_grp * sizeof(CountPart)));
+  got(c->d_winkey.alloc(c, kWinBytes));
+  got(c->d_counters.alloc(c, counters_bytes(c)));
+  got(c->d_ctrl.alloc(c, sizeof(Ctrl)));
+  got(c->d_gen.alloc(c, sizeof(uint32_t)));
+  got(c->d_cand.alloc(c, (size_t)c->max_blk * sizeof(Cand)));
+  got(c->d_mlpose.alloc(c, 12 * sizeof(double)));
+  got(c->d_flat.alloc(c, kFlatWords * sizeof(uint32_t)));
+  got(c->d_gran.alloc(c, kGranBytes));
   {
     int coop = 0;
     ok = ok && hipDeviceGetAttribute(&c->num_cu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess;
     ok = ok && hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess;
     c->coop = coop != 0;
   }
-  ok &= hipHostMalloc((void**)&c->h_rec, sizeof(RecOut), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-  ok = ok && hipHostGetDevicePointer((void**)&c->d_out, c->h_rec, 0) == hipSuccess;
+  got(c->h_rec.alloc(c, sizeof(RecOut)));
   if (ok) {
-    memset(c->h_rec, 0, sizeof(RecOut));
-    c->h_out = new OutDev();
+    memset(c->h_rec.get(), 0, sizeof(RecOut));
+    c->h_out.reset(new OutDev());
   }
-  ok &= hipMalloc((void**)&c->d_table, table_max_bytes(c)) == hipSuccess;
-  ok &= hipHostMalloc((void**)&c->h_table, table_max_bytes(c), hipHostMallocDefault) == hipSuccess;
+  got(c->d_table.alloc(c, table_max_bytes(c)));
+  got(c->h_table.alloc(c, table_max_bytes(c)));
   if (!ok) return bad(PFMPE_E_HIP);
   // Zeroed in the context's own stream and waited for: the stream is non-blocking, so a null-stream
   // hipMemset could still be in flight when the first frame's kernels read these words (freed memory of an
   // earlier context: a stale control record, counters or candidate tags).
-  ok = ok && hipMemsetAsync(c->d_gen, 0, sizeof(uint32_t), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(c->d_cand, 0, (size_t)c->max_blk * sizeof(Cand), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(c->d_counters, 0, counters_bytes(c), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(c->d_flat, 0, kFlatWords * sizeof(uint32_t), c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(c->d_gran, 0, kGranBytes, c->stream) == hipSuccess;  // no stale word holds a live tag
-  ok = ok && hipMemsetAsync(c->d_winkey, 0, kWinBytes, c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(c->d_state[0], 0, state_bytes, c->stream) == hipSuccess;
-  ok = ok && hipMemsetAsync(c->d_state[1], 0, state_bytes, c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(c->d_gen.get(), 0, sizeof(uint32_t), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(c->d_ctrl.get(), 0, sizeof(Ctrl), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(c->d_cand.get(), 0, (size_t)c->max_blk * sizeof(Cand), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(c->d_counters.get(), 0, counters_bytes(c), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(c->d_flat.get(), 0, kFlatWords * sizeof(uint32_t), c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(c->d_gran.get(), 0, kGranBytes, c->stream) == hipSuccess;  // no stale word holds a live tag
+  ok = ok && hipMemsetAsync(c->d_winkey.get(), 0, kWinBytes, c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(c->d_state[0].get(), 0, state_bytes, c->stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(c->d_state[1].get(), 0, state_bytes, c->stream) == hipSuccess;
   ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
   if (!ok) return bad(PFMPE_E_HIP);
   *out = c;
@@ -295,9 +234,7 @@ void pfmpe_destroy(pfmpe_ctx* c) {
   c->last_fence.reset();
   if (c->lead_fence) c->lead_fence->stream = nullptr;  // drained above; members find nothing pending
   c->lead_fence.reset();
-  if (c->own_ev) (void)hipEventDestroy(c->own_ev);
-  free_all(c);
-  delete c;
+  delete c;  // the buffers, then the events, the stream last (CtxQueue)
 }
 
 const char* pfmpe_last_error(const pfmpe_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -345,7 +282,7 @@ int pfmpe_set_option(pfmpe_ctx* c, int option, int64_t value) {
       c->record_counts = value != 0;
       if (c->record_counts && !c->d_counts) {
         RET(set_device(c));
-        HIPCHK(c, hipMalloc((void**)&c->d_counts, (size_t)c->max_blk * kBlock * sizeof(uint32_t)));  // whole blocks
+        RET(c->d_counts.alloc(c, (size_t)c->max_blk * kBlock * sizeof(uint32_t)));  // whole blocks
       }
       return PFMPE_OK;
     case PFMPE_OPT_FUSED:
@@ -394,8 +331,8 @@ int pfmpe_set_option(pfmpe_ctx* c, int option, int64_t value) {
       c->diag = (int)value;
       if ((c->diag & kDiagStamps) && !c->d_stamps) {
         RET(set_device(c));
-        HIPCHK(c, hipMalloc((void**)&c->d_stamps, (1 + (size_t)c->max_blk) * kStamps * sizeof(uint64_t)));
-        HIPCHK(c, hipMemsetAsync(c->d_stamps, 0, (1 + (size_t)c->max_blk) * kStamps * sizeof(uint64_t), c->stream));
+        RET(c->d_stamps.alloc(c, (1 + (size_t)c->max_blk) * kStamps * sizeof(uint64_t)));
+        HIPCHK(c, hipMemsetAsync(c->d_stamps.get(), 0, (1 + (size_t)c->max_blk) * kStamps * sizeof(uint64_t), c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
       }
       return PFMPE_OK;
@@ -404,36 +341,15 @@ int pfmpe_set_option(pfmpe_ctx* c, int option, int64_t value) {
   }
 }
 
-static int ensure_xfer(pfmpe_ctx* c) {
-  if (!c->d_xfer) HIPCHK(c, hipMalloc((void**)&c->d_xfer, (size_t)c->max_particles * 12 * sizeof(double)));
-  return PFMPE_OK;
-}
-
 int pfmpe_set_prior(pfmpe_ctx* c, const double* poses, int N) {
   if (!c) return PFMPE_E_ARG;
   if (!poses || N < 1) return fail(c, PFMPE_E_ARG, "set_prior: null poses or N < 1");
   if (N > c->max_particles) return fail(c, PFMPE_E_CAP, "set_prior: N exceeds max_particles");
   RET(set_device(c));
   RET(ensure_xfer(c));
-  HIPCHK(c, hipMemcpyAsync(c->d_xfer, poses, (size_t)N * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_xfer.get(), poses, (size_t)N * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   // fp16 state: the set's anchor is its first particle (deltas of a concentrated set stay small)
-  std::memcpy(c->anchor[c->prior_idx], poses, 12 * sizeof(double));
-  c->prior_owner = -1;  // stored in particle order
-  if (c->state_dtype == PFMPE_STATE_F64)
-    launch_import<double, double>(c, N, c->anchor[c->prior_idx]);
-  else if (c->state_dtype == PFMPE_STATE_F16)
-    launch_import<float, __half>(c, N, c->anchor[c->prior_idx]);
-  else
-    launch_import<float, float>(c, N, c->anchor[c->prior_idx]);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_winkey, 0, kWinBytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_counters, 0, counters_bytes(c), c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->N = N;
-  c->has_prior = true;
-  c->has_last = false;
-  return PFMPE_OK;
+  return import_prior(c, N, poses);
 }
 
 // (Re)builds the device bank from c->bank_blobs / bank_offsets with the parameters current now.  The table of a
@@ -455,16 +371,12 @@ static int build_bank(pfmpe_ctx* c) {
     off[f + 1] = off[f] + n;
     grid[f] = *(const GridHdr*)(one.data() + grid_off(c, nb[f]));
   }
-  unsigned char* d = nullptr;
-  HIPCHK(c, hipMalloc((void**)&d, host.size()));
-  hipError_t e = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, c->stream);
+  Buf<unsigned char> d;
+  RET(d.alloc(c, host.size()));
+  hipError_t e = hipMemcpyAsync(d.get(), host.data(), host.size(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // `host` goes out of scope; frames read in this stream
-  if (e != hipSuccess) {
-    (void)hipFree(d);
-    return fail(c, PFMPE_E_HIP, std::string("build_bank: ") + hipGetErrorString(e));
-  }
-  if (c->d_bank) (void)hipFree(c->d_bank);  // the stream is idle (synchronised above)
-  c->d_bank = d;
+  if (e != hipSuccess) return fail(c, PFMPE_E_HIP, std::string("build_bank: ") + hipGetErrorString(e));
+  c->d_bank.swap(d);  // the old bank is freed with `d`: the stream is idle (synchronised above)
   c->bank_off.swap(off);
   c->bank_B.swap(nb);
   c->bank_grid.swap(grid);
@@ -490,19 +402,19 @@ int pfmpe_stage_blob_bank(pfmpe_ctx* c, const double* blobs, const int32_t* offs
 int pfmpe_step(pfmpe_ctx* c, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
   RET(check_step(c, in, out));
   RET(set_device(c));
-  const unsigned char* table = c->d_table;
+  const unsigned char* table = c->d_table.get();
   const int B = in->B;
   size_t tbytes = 0;
   GridHdr gh{};
   if (in->bank_frame >= 0) {
-    table = c->d_bank + c->bank_off[in->bank_frame];
+    table = c->d_bank.get() + c->bank_off[in->bank_frame];
     tbytes = c->bank_off[in->bank_frame + 1] - c->bank_off[in->bank_frame];
     gh = c->bank_grid[in->bank_frame];
   } else {
     // the x-bucketed table is built here, O(B), and travels in the same copy the blobs would
-    tbytes = build_table(c, in->blobs, B, c->h_table);
-    gh = *(const GridHdr*)(c->h_table + grid_off(c, B));
-    HIPCHK(c, hipMemcpyAsync(c->d_table, c->h_table, tbytes, hipMemcpyHostToDevice, c->stream));
+    tbytes = build_table(c, in->blobs, B, c->h_table.get());
+    gh = *(const GridHdr*)(c->h_table.get() + grid_off(c, B));
+    HIPCHK(c, hipMemcpyAsync(c->d_table.get(), c->h_table.get(), tbytes, hipMemcpyHostToDevice, c->stream));
   }
   c->timing_now = c->timing > 0 && (c->timing_frame++ % c->timing) == 0;
   const size_t ev_mark = c->ev_used;  // brackets of earlier frames still pending (harvested lazily)
@@ -520,34 +432,21 @@ int pfmpe_step_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, pf
   pfmpe_ctx* c0 = ctxs[0];
   if (!in || !out) return fail(c0, PFMPE_E_ARG, "step_multi: null in/out");
   if (S > 65535) return fail(c0, PFMPE_E_CAP, "step_multi: at most 65535 streams per batch");
-  for (int s = 0; s < S; ++s) {
-    pfmpe_ctx* c = ctxs[s];
-    const std::string who = "step_multi: stream " + std::to_string(s) + ": ";
-    if (!c) return fail(c0, PFMPE_E_ARG, who + "null context");
-    if (c->device != c0->device || c->state_dtype != c0->state_dtype ||
-        c->params.rng_mode != c0->params.rng_mode || c->prune != c0->prune)
-      return fail(c0, PFMPE_E_ARG, who + "device, state type, RNG mode and pruning must match ctxs[0]");
-    for (int e = 0; e < s; ++e)
-      if (ctxs[e] == c) return fail(c0, PFMPE_E_ARG, who + "context appears twice");
-    const int rc = check_step(c, &in[s], &out[s]);
-    if (rc != PFMPE_OK) return fail(c0, rc, who + c->err);  // the per-stream code (E_ARG / E_CAP / E_STATE)
-  }
+  RET(check_members(
+      ctxs, S, "step_multi", "device, state type, RNG mode and pruning",
+      [&](const pfmpe_ctx* c) { return c->params.rng_mode == c0->params.rng_mode && c->prune == c0->prune; },
+      [&](int s, const std::string& at) {
+        const int rc = check_step(ctxs[s], &in[s], &out[s]);
+        return rc == PFMPE_OK ? rc : fail(c0, rc, at + ctxs[s]->err);  // the per-stream code (E_ARG / E_CAP / E_STATE)
+      }));
   c0->mt_enter = now_ns();
   RET(set_device(c0));
   c0->timing_now = c0->timing > 0 && (c0->timing_frame++ % c0->timing) == 0;  // batches timed on the leader
-  const bool ref = c0->params.rng_mode == PFMPE_RNG_REFERENCE;
   const size_t ev_mark = c0->ev_used;
-  int rs;
-  switch (c0->state_dtype) {
-    case PFMPE_STATE_F64:
-      rs = ref ? multi_m<double, kRngReference, double>(ctxs, S, in) : multi_m<double, kRngPhilox, double>(ctxs, S, in);
-      break;
-    case PFMPE_STATE_F16:
-      rs = ref ? multi_m<float, kRngReference, __half>(ctxs, S, in) : multi_m<float, kRngPhilox, __half>(ctxs, S, in);
-      break;
-    default:
-      rs = ref ? multi_m<float, kRngReference, float>(ctxs, S, in) : multi_m<float, kRngPhilox, float>(ctxs, S, in);
-  }
+  const int rs = visit_state_rng(c0, [&](auto s) {
+    using S_ = decltype(s);
+    return multi_m<typename S_::T, S_::RNG, typename S_::SP>(ctxs, S, in);
+  });
   c0->timing_now = false;
   if (rs != PFMPE_OK) c0->ev_used = ev_mark;  // only the failed batch's own brackets are dropped
   else if (c0->ev_used >= kHarvestPairs) RET(harvest_timing(c0));
@@ -678,24 +577,22 @@ int pfmpe_predict_roi(pfmpe_ctx* c, const pfmpe_roi_in* in, pfmpe_roi_out* out) 
   RET(set_device(c));
   const int N = c->N;
   const int nblk = (N + kBlock - 1) / kBlock;
-  if (!c->d_roi) HIPCHK(c, hipMalloc((void**)&c->d_roi, ((size_t)c->max_blk + 1) * 4 * sizeof(double)));
+  RET(c->d_roi.ensure(c, ((size_t)c->max_blk + 1) * 4 * sizeof(double)));
   const RoiArgs ra = roi_args(c, in);
-  double* part = c->d_roi + 4;
+  double* part = c->d_roi.get() + 4;
   c->timing_now = c->timing > 0;  // bracketed like the detector's and the initialisation's launches
   const int rl = launch(c, PFMPE_K_ROI, [&] {
-    const void* st = c->d_state[c->prior_idx];
-    if (c->state_dtype == PFMPE_STATE_F64)
-      hipLaunchKernelGGL((k_roi<double, double>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const double*)st, part);
-    else if (c->state_dtype == PFMPE_STATE_F16)
-      hipLaunchKernelGGL((k_roi<float, __half>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const __half*)st, part);
-    else
-      hipLaunchKernelGGL((k_roi<float, float>), dim3(nblk), dim3(kBlock), 0, c->stream, ra, (const float*)st, part);
-    hipLaunchKernelGGL((k_roi_final<double>), dim3(1), dim3(kBlock), 0, c->stream, part, nblk, c->d_roi);
+    visit_state(c, [&](auto s) {
+      using SP = typename decltype(s)::SP;
+      hipLaunchKernelGGL((k_roi<typename decltype(s)::T, SP>), dim3(nblk), dim3(kBlock), 0, c->stream, ra,
+                         (const SP*)c->d_state[c->prior_idx].get(), part);
+    });
+    hipLaunchKernelGGL((k_roi_final<double>), dim3(1), dim3(kBlock), 0, c->stream, part, nblk, c->d_roi.get());
   });
   c->timing_now = false;
   RET(rl);
   double bb[4];
-  HIPCHK(c, hipMemcpyAsync(bb, c->d_roi, sizeof(bb), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bb, c->d_roi.get(), sizeof(bb), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RET(harvest_timing(c));
   roi_epilogue(c->K, c->markers, c->M, in, bb, out);
@@ -709,55 +606,31 @@ int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* i
   if (S > PFMPE_ROI_MAX_STREAMS)
     return fail(c0, PFMPE_E_CAP, "predict_roi_multi: S exceeds PFMPE_ROI_MAX_STREAMS");
   int64_t total = 0;
-  for (int s = 0; s < S; ++s) {
-    const pfmpe_ctx* c = ctxs[s];
-    const std::string who = "predict_roi_multi: stream " + std::to_string(s) + ": ";
-    if (!c) return fail(c0, PFMPE_E_ARG, who + "null context");
-    for (int e = 0; e < s; ++e)
-      if (ctxs[e] == c) return fail(c0, PFMPE_E_ARG, who + "context appears twice");
-    if (c->device != c0->device || c->state_dtype != c0->state_dtype)
-      return fail(c0, PFMPE_E_ARG, who + "device and state type must match ctxs[0]");
-    if (!c->has_model || !c->has_prior) return fail(c0, PFMPE_E_STATE, who + "set_model and set_prior first");
-    if (in[s].image_w < 1 || in[s].image_h < 1) return fail(c0, PFMPE_E_ARG, who + "bad image size");
-    total += (c->N + kBlock - 1) / kBlock;
-  }
+  RET(check_members(
+      ctxs, S, "predict_roi_multi", "device and state type", [](const pfmpe_ctx*) { return true; },
+      [&](int s, const std::string& at) {
+        const pfmpe_ctx* c = ctxs[s];
+        if (!c->has_model || !c->has_prior) return fail(c0, PFMPE_E_STATE, at + "set_model and set_prior first");
+        if (in[s].image_w < 1 || in[s].image_h < 1) return fail(c0, PFMPE_E_ARG, at + "bad image size");
+        total += (c->N + kBlock - 1) / kBlock;
+        return (int)PFMPE_OK;
+      }));
   if (total > INT32_MAX) return fail(c0, PFMPE_E_CAP, "predict_roi_multi: too many blocks in one batch");
   RET(set_device(c0));
   // the scratch before any member's ordering state changes: pinned image (head, descriptors, result boxes) once,
   // device image + partials grown on demand (nothing of an earlier batch is pending: the call is blocking)
   constexpr size_t kDescOff = (sizeof(RoiBatch) + 255) / 256 * 256;
   constexpr size_t kBoxOff = kDescOff + kRoiMaxStreams * sizeof(RoiDesc);
-  if (!c0->h_roim)
-    HIPCHK(c0, hipHostMalloc((void**)&c0->h_roim, kBoxOff + kRoiMaxStreams * 4 * sizeof(double),
-                             hipHostMallocMapped | hipHostMallocCoherent));
+  RET(c0->h_roim.ensure(c0, kBoxOff + kRoiMaxStreams * 4 * sizeof(double)));
   const size_t need = kBoxOff + (size_t)total * 4 * sizeof(double);
-  if (need > c0->roim_cap) {
-    if (c0->d_roim) HIPCHK(c0, hipFree(c0->d_roim));
-    c0->d_roim = nullptr;
-    c0->roim_cap = 0;
-    const size_t cap = kBoxOff + (need - kBoxOff) * 2;
-    HIPCHK(c0, hipMalloc((void**)&c0->d_roim, cap));
-    c0->roim_cap = cap;
-  }
-  unsigned char* hd_img = nullptr;
-  HIPCHK(c0, hipHostGetDevicePointer((void**)&hd_img, c0->h_roim, 0));
-  // every member's work so far is ordered before the batch (multi_m's rule: a later member's failure gives the
-  // earlier ones their ordering state back)
-  std::vector<std::pair<hipStream_t, std::shared_ptr<BatchFence>>> saved(S);
-  for (int s = 0; s < S; ++s) saved[s] = {ctxs[s]->last_stream, ctxs[s]->last_fence};
-  auto restore = [&] {
-    for (int e = 0; e < S; ++e) {
-      ctxs[e]->last_stream = saved[e].first;
-      ctxs[e]->last_fence = saved[e].second;
-    }
-  };
-  for (int s = 1; s < S; ++s)
-    if (const int r = order_after(ctxs[s], c0->stream, c0)) {
-      restore();
-      return r;
-    }
-  RoiBatch* hd = (RoiBatch*)c0->h_roim;
-  RoiDesc* descs = (RoiDesc*)(c0->h_roim + kDescOff);
+  RET(c0->d_roim.grow(c0, need, kBoxOff + (need - kBoxOff) * 2));
+  unsigned char* hd_img = c0->h_roim.dev();
+  // every member's work so far is ordered before the batch; a failure from here on gives the members their
+  // ordering state back (the leader's own was set by set_device)
+  OrderGuard members(ctxs, S);
+  RET(members.order(1, c0->stream, c0));
+  RoiBatch* hd = (RoiBatch*)c0->h_roim.get();
+  RoiDesc* descs = (RoiDesc*)(c0->h_roim.get() + kDescOff);
   std::memset(hd, 0, sizeof(*hd));
   hd->S = S;
   int32_t nb = 0;
@@ -765,27 +638,25 @@ int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* i
     const pfmpe_ctx* c = ctxs[s];
     RoiDesc& d = descs[s];
     d.a = roi_args(c, &in[s]);
-    d.prior = c->d_state[c->prior_idx];
+    d.prior = c->d_state[c->prior_idx].get();
     hd->first[s] = nb;
     nb += (c->N + kBlock - 1) / kBlock;
   }
   hd->first[S] = nb;
   const int stage_words = (int)((kDescOff + (size_t)S * sizeof(RoiDesc)) / sizeof(uint64_t));
-  const RoiBatch* dhd = (const RoiBatch*)c0->d_roim;
-  const RoiDesc* ddescs = (const RoiDesc*)(c0->d_roim + kDescOff);
-  double* part = (double*)(c0->d_roim + kBoxOff);
-  const double* hbox = (const double*)(c0->h_roim + kBoxOff);
+  const RoiBatch* dhd = (const RoiBatch*)c0->d_roim.get();
+  const RoiDesc* ddescs = (const RoiDesc*)(c0->d_roim.get() + kDescOff);
+  double* part = (double*)(c0->d_roim.get() + kBoxOff);
+  const double* hbox = (const double*)(c0->h_roim.get() + kBoxOff);
   double* dbox = (double*)(hd_img + kBoxOff);
   c0->timing_now = c0->timing > 0;
   int rc = launch(c0, PFMPE_K_ROI, [&] {
     hipLaunchKernelGGL((k_roi_stage<uint64_t>), dim3(1), dim3(kBlock), 0, c0->stream, (const uint64_t*)hd_img,
-                       (uint64_t*)c0->d_roim, stage_words);
-    if (c0->state_dtype == PFMPE_STATE_F64)
-      hipLaunchKernelGGL((k_roi_multi<double, double>), dim3(nb), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
-    else if (c0->state_dtype == PFMPE_STATE_F16)
-      hipLaunchKernelGGL((k_roi_multi<float, __half>), dim3(nb), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
-    else
-      hipLaunchKernelGGL((k_roi_multi<float, float>), dim3(nb), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
+                       (uint64_t*)c0->d_roim.get(), stage_words);
+    visit_state(c0, [&](auto s) {
+      hipLaunchKernelGGL((k_roi_multi<typename decltype(s)::T, typename decltype(s)::SP>), dim3(nb), dim3(kBlock), 0,
+                         c0->stream, dhd, ddescs, part);
+    });
     hipLaunchKernelGGL((k_roi_multi_final<double>), dim3(S), dim3(kBlock), 0, c0->stream, dhd, (const double*)part,
                        dbox);
   });
@@ -793,11 +664,8 @@ int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* i
   if (rc == PFMPE_OK && hipStreamSynchronize(c0->stream) != hipSuccess)
     rc = fail(c0, PFMPE_E_HIP, "predict_roi_multi: stream synchronise failed");
   if (rc == PFMPE_OK) rc = harvest_timing(c0);
-  if (rc != PFMPE_OK) {
-    restore();
-    return rc;
-  }
-  // nothing of the batch is pending: no member needs a fence
+  RET(rc);
+  members.commit();  // nothing of the batch is pending: no member needs a fence
   for (int s = 0; s < S; ++s) {
     double bb[4];
     std::memcpy(bb, hbox + 4 * (size_t)s, sizeof(bb));
@@ -833,17 +701,11 @@ int pfmpe_get_particles(pfmpe_ctx* c, int which, double* out) {
   RET(set_device(c));
   RET(ensure_xfer(c));
   const int N = c->N;
-  if (which == 0) {
-    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx], c->d_xfer));
-  } else if (c->state_dtype == PFMPE_STATE_F64) {
-    launch_export<double, double>(c, N, c->anchor[c->prior_idx]);
-  } else if (c->state_dtype == PFMPE_STATE_F16) {
-    launch_export<float, __half>(c, N, c->anchor[c->prior_idx]);
-  } else {
-    launch_export<float, float>(c, N, c->anchor[c->prior_idx]);
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, c->d_xfer, (size_t)N * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (which == 0)
+    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()));
+  else
+    RET(export_prior(c, N));
+  HIPCHK(c, hipMemcpyAsync(out, c->d_xfer.get(), (size_t)N * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RET(harvest_timing(c));
   return PFMPE_OK;
@@ -856,14 +718,13 @@ int pfmpe_get_weights(pfmpe_ctx* c, double* out) {
   RET(set_device(c));
   RET(ensure_xfer(c));
   const int N = c->N;
-  if (c->state_dtype == PFMPE_STATE_F64)
-    hipLaunchKernelGGL((k_weights_export<double>), dim3((N + 255) / 256), dim3(256), 0, c->stream,
-                       (const double*)c->d_w[c->last_kept_slot], c->d_xfer, N);
-  else
-    hipLaunchKernelGGL((k_weights_export<float>), dim3((N + 255) / 256), dim3(256), 0, c->stream,
-                       (const float*)c->d_w[c->last_kept_slot], c->d_xfer, N);
+  visit_state(c, [&](auto s) {
+    using T = typename decltype(s)::T;
+    hipLaunchKernelGGL((k_weights_export<T>), dim3((N + 255) / 256), dim3(256), 0, c->stream,
+                       (const T*)c->d_w[c->last_kept_slot].get(), c->d_xfer.get(), N);
+  });
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, c->d_xfer, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->d_xfer.get(), (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PFMPE_OK;
 }
@@ -871,11 +732,11 @@ int pfmpe_get_weights(pfmpe_ctx* c, double* out) {
 int pfmpe_get_counts(pfmpe_ctx* c, uint32_t* out) {
   if (!c) return PFMPE_E_ARG;
   if (!out) return fail(c, PFMPE_E_ARG, "get_counts: null out");
-  if (!c->record_counts || !c->d_counts) return fail(c, PFMPE_E_STATE, "get_counts: PFMPE_OPT_RECORD_COUNTS off");
+  if (!c->record_counts || !c->d_counts.get()) return fail(c, PFMPE_E_STATE, "get_counts: PFMPE_OPT_RECORD_COUNTS off");
   if (!c->has_last || !c->last_accepted) return fail(c, PFMPE_E_STATE, "get_counts: last step did not resample");
   RET(set_device(c));
   // in the context's stream: the frame's kernel may still be retiring after its record reached the host
-  HIPCHK(c, hipMemcpyAsync(out, c->d_counts, (size_t)c->N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->d_counts.get(), (size_t)c->N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PFMPE_OK;
 }
@@ -917,46 +778,39 @@ int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_ou
   if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_stats(weighted): no step yet");
   RET(set_device(c));
   // scratch of the call's own (nothing a frame reads): the result row, then one partial row per block
-  if (!c->d_cloud)
-    HIPCHK(c, hipMalloc((void**)&c->d_cloud, ((size_t)kCloudMaxBlocks + 1) * kCloudWords * sizeof(double)));
+  RET(c->d_cloud.ensure(c, ((size_t)kCloudMaxBlocks + 1) * kCloudWords * sizeof(double)));
   const int N = c->N;
   const int nblk = cloud_blocks(N);
   CloudArgs ca{};
   std::memcpy(ca.ref, ref, sizeof(ca.ref));
   ca.N = N;
-  double* part = c->d_cloud + kCloudWords;
+  double* part = c->d_cloud.get() + kCloudWords;
   if (which == PFMPE_CLOUD_WEIGHTED) {
     // the kept propagated set as get_particles(0) delivers it (d_xfer is written and read inside one blocking call
     // by every user), weighted by the kept iteration's raw weights
     RET(ensure_xfer(c));
-    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx], c->d_xfer));
-    ca.dense = c->d_xfer;
-    ca.w = c->d_w[c->last_kept_slot];
-    if (c->state_dtype == PFMPE_STATE_F64)
-      hipLaunchKernelGGL((k_cloud_partials<double, double, true>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
-                         (const double*)nullptr, part);
-    else
-      hipLaunchKernelGGL((k_cloud_partials<float, float, true>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
-                         (const float*)nullptr, part);
+    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()));
+    ca.dense = c->d_xfer.get();
+    ca.w = c->d_w[c->last_kept_slot].get();
+    visit_state(c, [&](auto s) {  // the dense set is in the compute type
+      using T = typename decltype(s)::T;
+      hipLaunchKernelGGL((k_cloud_partials<T, T, true>), dim3(nblk), dim3(kBlock), 0, c->stream, ca, (const T*)nullptr,
+                         part);
+    });
   } else {
     std::memcpy(ca.anchor, c->anchor[c->prior_idx], sizeof(ca.anchor));
     ca.ld = c->ld;
     ca.owner = prior_owner_ptr(c);
-    const void* st = c->d_state[c->prior_idx];
-    if (c->state_dtype == PFMPE_STATE_F64)
-      hipLaunchKernelGGL((k_cloud_partials<double, double, false>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
-                         (const double*)st, part);
-    else if (c->state_dtype == PFMPE_STATE_F16)
-      hipLaunchKernelGGL((k_cloud_partials<float, __half, false>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
-                         (const __half*)st, part);
-    else
-      hipLaunchKernelGGL((k_cloud_partials<float, float, false>), dim3(nblk), dim3(kBlock), 0, c->stream, ca,
-                         (const float*)st, part);
+    visit_state(c, [&](auto s) {
+      using SP = typename decltype(s)::SP;
+      hipLaunchKernelGGL((k_cloud_partials<typename decltype(s)::T, SP, false>), dim3(nblk), dim3(kBlock), 0, c->stream,
+                         ca, (const SP*)c->d_state[c->prior_idx].get(), part);
+    });
   }
-  hipLaunchKernelGGL((k_cloud_final<double>), dim3(1), dim3(kCloudSegs * kCloudWords), 0, c->stream, part, nblk, c->d_cloud);
+  hipLaunchKernelGGL((k_cloud_final<double>), dim3(1), dim3(kCloudSegs * kCloudWords), 0, c->stream, part, nblk, c->d_cloud.get());
   HIPCHK(c, hipGetLastError());
   double r[kCloudWords];
-  HIPCHK(c, hipMemcpyAsync(r, c->d_cloud, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(r, c->d_cloud.get(), sizeof(r), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RET(harvest_timing(c));  // (a weighted call's regeneration is bracketed like get_particles(0)'s)
 
@@ -1023,36 +877,29 @@ int pfmpe_host_assoc_summary(const uint32_t* votes, int M, int B, pfmpe_assoc_ou
 namespace {
 // The argument and state checks shared by pfmpe_assoc_stats / pfmpe_get_pairs, then the call's blob table built
 // into d_table (every frame that reads d_table writes it first) and, for the propagated set, the kept set
-// regenerated into d_xfer (written and read inside one blocking call by every user).
-int assoc_prepare(pfmpe_ctx* c, const char* who, int which, const pfmpe_assoc_in* in, int* B_out, size_t* tbytes,
-                  GridHdr* gh, AssocArgs* aa) {
+// regenerated into d_xfer (written and read inside one blocking call by every user).  *blobs_out / *B_out: the
+// blobs the call means (resolve_blobs).
+int assoc_prepare(pfmpe_ctx* c, const char* who, int which, const pfmpe_assoc_in* in, const double** blobs_out,
+                  int* B_out, size_t* tbytes, GridHdr* gh, AssocArgs* aa) {
   const std::string w(who);
   if (!in || (which != PFMPE_ASSOC_PROPAGATED && which != PFMPE_ASSOC_POSTERIOR))
     return fail(c, PFMPE_E_ARG, w + ": bad arguments");
-  if (in->B < 0) return fail(c, PFMPE_E_ARG, w + ": B < 0");
-  const double* blobs = in->blobs;
-  int B = in->B;
-  if (in->bank_frame >= 0) {
-    if (c->bank_offsets.empty() || in->bank_frame >= (int)c->bank_offsets.size() - 1)
-      return fail(c, PFMPE_E_ARG, w + ": bank_frame out of range");
-    B = c->bank_offsets[in->bank_frame + 1] - c->bank_offsets[in->bank_frame];
-    blobs = c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame];
-  } else if (B > 0 && !blobs) {
-    return fail(c, PFMPE_E_ARG, w + ": null blobs");
-  }
-  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, w + ": B exceeds max_blobs");
+  const double* blobs = nullptr;
+  int B = 0;
+  RET(resolve_blobs(c, w, in, &blobs, &B));
   if (!c->has_model || !c->has_prior) return fail(c, PFMPE_E_STATE, w + ": set_model and a particle set first");
   if (which == PFMPE_ASSOC_PROPAGATED && !c->has_last) return fail(c, PFMPE_E_STATE, w + "(propagated): no step yet");
   RET(set_device(c));
-  *tbytes = build_table(c, blobs, B, c->h_table);
-  *gh = *(const GridHdr*)(c->h_table + grid_off(c, B));
-  HIPCHK(c, hipMemcpyAsync(c->d_table, c->h_table, *tbytes, hipMemcpyHostToDevice, c->stream));
+  *tbytes = build_table(c, blobs, B, c->h_table.get());
+  *gh = *(const GridHdr*)(c->h_table.get() + grid_off(c, B));
+  HIPCHK(c, hipMemcpyAsync(c->d_table.get(), c->h_table.get(), *tbytes, hipMemcpyHostToDevice, c->stream));
   *aa = AssocArgs{};
   if (which == PFMPE_ASSOC_PROPAGATED) {
     RET(ensure_xfer(c));
-    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx], c->d_xfer));
-    aa->dense = c->d_xfer;
+    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()));
+    aa->dense = c->d_xfer.get();
   }
+  *blobs_out = blobs;
   *B_out = B;
   return PFMPE_OK;
 }
@@ -1061,23 +908,23 @@ int assoc_prepare(pfmpe_ctx* c, const char* who, int which, const pfmpe_assoc_in
 int pfmpe_assoc_stats(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, pfmpe_assoc_out* out, uint32_t* votes) {
   if (!c) return PFMPE_E_ARG;
   if (!out) return fail(c, PFMPE_E_ARG, "assoc_stats: null out");
+  const double* blobs = nullptr;
   int B = 0;
   size_t tbytes = 0;
   GridHdr gh{};
   AssocArgs aa{};
-  RET(assoc_prepare(c, "assoc_stats", which, in, &B, &tbytes, &gh, &aa));
+  RET(assoc_prepare(c, "assoc_stats", which, in, &blobs, &B, &tbytes, &gh, &aa));
   // scratch of the call's own: the bins of the largest table
-  if (!c->d_assoc)
-    HIPCHK(c, hipMalloc((void**)&c->d_assoc, (size_t)assoc_bins(kMaxMarkers, kMaxBlobs) * sizeof(uint32_t)));
+  RET(c->d_assoc.ensure(c, (size_t)assoc_bins(kMaxMarkers, kMaxBlobs) * sizeof(uint32_t)));
   const int M = c->M, N = c->N;
   const int nbins = assoc_bins(M, B);
-  HIPCHK(c, hipMemsetAsync(c->d_assoc, 0, (size_t)nbins * sizeof(uint32_t), c->stream));
-  aa.votes = c->d_assoc;
+  HIPCHK(c, hipMemsetAsync(c->d_assoc.get(), 0, (size_t)nbins * sizeof(uint32_t), c->stream));
+  aa.votes = c->d_assoc.get();
   aa.first = 0;
   aa.count = N;
-  RET(assoc_launch(c, B, c->d_table, tbytes, gh, aa));
+  RET(assoc_launch(c, B, c->d_table.get(), tbytes, gh, aa));
   std::vector<uint32_t> bins(nbins);
-  HIPCHK(c, hipMemcpyAsync(bins.data(), c->d_assoc, (size_t)nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bins.data(), c->d_assoc.get(), (size_t)nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RET(harvest_timing(c));  // (a propagated call's regeneration is bracketed like the particle read-back's)
 
@@ -1106,21 +953,22 @@ int pfmpe_get_pairs(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, int64_t f
     return fail(c, PFMPE_E_ARG, "get_pairs: bad range or null output");
   if (c->has_prior && first + (int64_t)count > (int64_t)c->N)
     return fail(c, PFMPE_E_ARG, "get_pairs: first + count exceeds the particle count");
+  const double* blobs = nullptr;
   int B = 0;
   size_t tbytes = 0;
   GridHdr gh{};
   AssocArgs aa{};
-  RET(assoc_prepare(c, "get_pairs", which, in, &B, &tbytes, &gh, &aa));
-  constexpr size_t kRow = 2 * kMaxMarkers;
-  const int cap = std::min(c->max_particles, kPairsChunk);
-  if (!c->d_pairs) HIPCHK(c, hipMalloc((void**)&c->d_pairs, (size_t)cap * (kRow + 1) * sizeof(uint32_t)));
-  aa.corr = c->d_pairs;
-  aa.n_corr = (int32_t*)(c->d_pairs + (size_t)cap * kRow);
+  RET(assoc_prepare(c, "get_pairs", which, in, &blobs, &B, &tbytes, &gh, &aa));
+  constexpr size_t kRow = kPairRow;
+  const int cap = pairs_cap(c);
+  RET(ensure_pairs(c));
+  aa.corr = c->d_pairs.get();
+  aa.n_corr = (int32_t*)(c->d_pairs.get() + (size_t)cap * kRow);
   for (int64_t done = 0; done < count; done += cap) {
     const int n = (int)std::min<int64_t>(cap, count - done);
     aa.first = (int32_t)(first + done);
     aa.count = n;
-    RET(assoc_launch(c, B, c->d_table, tbytes, gh, aa));
+    RET(assoc_launch(c, B, c->d_table.get(), tbytes, gh, aa));
     HIPCHK(c, hipMemcpyAsync(corr + (size_t)done * kRow, aa.corr, (size_t)n * kRow * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(n_corr + done, aa.n_corr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1159,20 +1007,20 @@ bool refine_poses_finite(const double* poses, size_t n) {
 
 // the scratch, the model and the call's blobs in fp64 (enqueued on the stream; `stage` must outlive the copy)
 int refine_stage(pfmpe_ctx* c, const double* blobs, int B, int cap, std::vector<double>& stage) {
-  if (!c->d_refine) HIPCHK(c, hipMalloc((void**)&c->d_refine, RefineBuf::bytes(c->max_blobs, cap)));
+  RET(c->d_refine.ensure(c, RefineBuf::bytes(c->max_blobs, cap)));
   const size_t words = (RefineBuf::kBlobs - RefineBuf::kMarkers) / sizeof(double) + 2 * (size_t)B;
   stage.assign(words, 0.0);
   std::memcpy(stage.data(), c->markers, sizeof(c->markers));
   std::memcpy(stage.data() + (RefineBuf::kK - RefineBuf::kMarkers) / sizeof(double), c->K, sizeof(c->K));
   if (B > 0) std::memcpy(stage.data() + (RefineBuf::kBlobs - RefineBuf::kMarkers) / sizeof(double), blobs, 2 * (size_t)B * sizeof(double));
-  HIPCHK(c, hipMemcpyAsync(c->d_refine + RefineBuf::kMarkers, stage.data(), words * sizeof(double), hipMemcpyHostToDevice,
+  HIPCHK(c, hipMemcpyAsync(c->d_refine.get() + RefineBuf::kMarkers, stage.data(), words * sizeof(double), hipMemcpyHostToDevice,
                            c->stream));
   return PFMPE_OK;
 }
 // a chunk's rows and covariances, hypotheses lo .. hi - 1 of the chunk, to the caller's arrays at index `at`
 int refine_fetch(pfmpe_ctx* c, int cap, int lo, int hi, pfmpe_refine_row* rows, double* cov, int64_t at) {
   if (hi <= lo) return PFMPE_OK;
-  const unsigned char* d = c->d_refine;
+  const unsigned char* d = c->d_refine.get();
   if (rows)
     HIPCHK(c, hipMemcpyAsync(rows + at, d + RefineBuf::rows(c->max_blobs) + (size_t)lo * sizeof(pfmpe_refine_row),
                              (size_t)(hi - lo) * sizeof(pfmpe_refine_row), hipMemcpyDeviceToHost, c->stream));
@@ -1182,7 +1030,7 @@ int refine_fetch(pfmpe_ctx* c, int cap, int lo, int hi, pfmpe_refine_row* rows, 
   return PFMPE_OK;
 }
 int refine_finish(pfmpe_ctx* c, int64_t n, pfmpe_refine_out* out) {
-  HIPCHK(c, hipMemcpyAsync(out, c->d_refine + RefineBuf::kOut, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->d_refine.get() + RefineBuf::kOut, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RET(harvest_timing(c));  // (a propagated call's regeneration is bracketed like the particle read-back's)
   out->n = n;
@@ -1198,18 +1046,9 @@ int pfmpe_refine_poses(pfmpe_ctx* c, const pfmpe_assoc_in* in, const pfmpe_refin
   if (params) prm = *params;
   if (!out || !in || K < 0 || (K > 0 && (!poses || !corr))) return fail(c, PFMPE_E_ARG, "refine_poses: bad arguments");
   if (!refine_params_ok(prm)) return fail(c, PFMPE_E_ARG, "refine_poses: bad parameters");
-  if (in->B < 0) return fail(c, PFMPE_E_ARG, "refine_poses: B < 0");
-  const double* blobs = in->blobs;
-  int B = in->B;
-  if (in->bank_frame >= 0) {
-    if (c->bank_offsets.empty() || in->bank_frame >= (int)c->bank_offsets.size() - 1)
-      return fail(c, PFMPE_E_ARG, "refine_poses: bank_frame out of range");
-    B = c->bank_offsets[in->bank_frame + 1] - c->bank_offsets[in->bank_frame];
-    blobs = c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame];
-  } else if (B > 0 && !blobs) {
-    return fail(c, PFMPE_E_ARG, "refine_poses: null blobs");
-  }
-  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, "refine_poses: B exceeds max_blobs");
+  const double* blobs = nullptr;
+  int B = 0;
+  RET(resolve_blobs(c, "refine_poses", in, &blobs, &B));
   if (K > c->max_particles) return fail(c, PFMPE_E_CAP, "refine_poses: K exceeds max_particles");
   if (!c->has_model) return fail(c, PFMPE_E_STATE, "refine_poses: set_model first");
   if (K > 0 && !refine_corr_ok(corr, (size_t)K * kMaxMarkers, c->M, B))
@@ -1217,20 +1056,20 @@ int pfmpe_refine_poses(pfmpe_ctx* c, const pfmpe_assoc_in* in, const pfmpe_refin
   if (K > 0 && !refine_poses_finite(poses, (size_t)K)) return fail(c, PFMPE_E_ARG, "refine_poses: non-finite start pose");
   RET(set_device(c));
   RET(ensure_xfer(c));
-  constexpr size_t kRow = 2 * kMaxMarkers;
-  const int cap = std::min(c->max_particles, kPairsChunk);
-  if (!c->d_pairs) HIPCHK(c, hipMalloc((void**)&c->d_pairs, (size_t)cap * (kRow + 1) * sizeof(uint32_t)));
+  constexpr size_t kRow = kPairRow;
+  const int cap = pairs_cap(c);
+  RET(ensure_pairs(c));
   std::vector<double> stage;
   RET(refine_stage(c, blobs, B, cap, stage));
   // d_xfer is written and read inside one blocking call by every user
-  if (K > 0) HIPCHK(c, hipMemcpyAsync(c->d_xfer, poses, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (K > 0) HIPCHK(c, hipMemcpyAsync(c->d_xfer.get(), poses, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   int64_t done = 0;
   do {  // (K = 0: one empty chunk writes the empty summary)
     const int n = (int)std::min<int64_t>(cap, (int64_t)K - done);
     if (n > 0)
-      HIPCHK(c, hipMemcpyAsync(c->d_pairs, corr + (size_t)done * kRow, (size_t)n * kRow * sizeof(uint32_t),
+      HIPCHK(c, hipMemcpyAsync(c->d_pairs.get(), corr + (size_t)done * kRow, (size_t)n * kRow * sizeof(uint32_t),
                                hipMemcpyHostToDevice, c->stream));
-    RET(refine_launch(c, prm, c->d_xfer + 12 * done, c->d_pairs, done, n, cap, done == 0));
+    RET(refine_launch(c, prm, c->d_xfer.get() + 12 * done, c->d_pairs.get(), done, n, cap, done == 0));
     RET(refine_fetch(c, cap, 0, n, rows, cov, done));
     done += n;
   } while (done < K);
@@ -1247,37 +1086,31 @@ int pfmpe_refine_cloud(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, const 
   if (c->has_prior && first + (int64_t)count > (int64_t)c->N)
     return fail(c, PFMPE_E_ARG, "refine_cloud: first + count exceeds the particle count");
   if (!refine_params_ok(prm)) return fail(c, PFMPE_E_ARG, "refine_cloud: bad parameters");
+  const double* blobs = nullptr;
   int B = 0;
   size_t tbytes = 0;
   GridHdr gh{};
   AssocArgs aa{};
-  RET(assoc_prepare(c, "refine_cloud", which, in, &B, &tbytes, &gh, &aa));
-  const double* blobs = in->bank_frame >= 0 ? c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame] : in->blobs;
+  RET(assoc_prepare(c, "refine_cloud", which, in, &blobs, &B, &tbytes, &gh, &aa));
   const int N = c->N;
   // the start poses as get_particles delivers them: the propagated set is in d_xfer already (assoc_prepare)
   if (which == PFMPE_ASSOC_POSTERIOR) {
     RET(ensure_xfer(c));
-    if (c->state_dtype == PFMPE_STATE_F64)
-      launch_export<double, double>(c, N, c->anchor[c->prior_idx]);
-    else if (c->state_dtype == PFMPE_STATE_F16)
-      launch_export<float, __half>(c, N, c->anchor[c->prior_idx]);
-    else
-      launch_export<float, float>(c, N, c->anchor[c->prior_idx]);
-    HIPCHK(c, hipGetLastError());
+    RET(export_prior(c, N));
   }
-  constexpr size_t kRow = 2 * kMaxMarkers;
-  const int cap = std::min(c->max_particles, kPairsChunk);
-  if (!c->d_pairs) HIPCHK(c, hipMalloc((void**)&c->d_pairs, (size_t)cap * (kRow + 1) * sizeof(uint32_t)));
+  constexpr size_t kRow = kPairRow;
+  const int cap = pairs_cap(c);
+  RET(ensure_pairs(c));
   std::vector<double> stage;
   RET(refine_stage(c, blobs, B, cap, stage));
-  aa.corr = c->d_pairs;
-  aa.n_corr = (int32_t*)(c->d_pairs + (size_t)cap * kRow);
+  aa.corr = c->d_pairs.get();
+  aa.n_corr = (int32_t*)(c->d_pairs.get() + (size_t)cap * kRow);
   for (int64_t done = 0; done < N; done += cap) {
     const int n = (int)std::min<int64_t>(cap, (int64_t)N - done);
     aa.first = (int32_t)done;
     aa.count = n;
-    RET(assoc_launch(c, B, c->d_table, tbytes, gh, aa));
-    RET(refine_launch(c, prm, c->d_xfer + 12 * done, c->d_pairs, done, n, cap, done == 0));
+    RET(assoc_launch(c, B, c->d_table.get(), tbytes, gh, aa));
+    RET(refine_launch(c, prm, c->d_xfer.get() + 12 * done, c->d_pairs.get(), done, n, cap, done == 0));
     const int64_t lo = std::max<int64_t>(first, done), hi = std::min<int64_t>(first + count, done + n);
     RET(refine_fetch(c, cap, (int)(lo - done), (int)(hi - done), rows, cov, lo - first));
   }
@@ -1308,12 +1141,12 @@ int pfmpe_debug_stamps(pfmpe_ctx* c, uint64_t* out) {
   hipStream_t st = c->stream;
   const size_t rows = 1 + (size_t)c->max_blk;
   if (!out) {
-    HIPCHK(c, hipMemsetAsync(c->d_stamps, 0, rows * kStamps * sizeof(uint64_t), st));
+    HIPCHK(c, hipMemsetAsync(c->d_stamps.get(), 0, rows * kStamps * sizeof(uint64_t), st));
     HIPCHK(c, hipStreamSynchronize(st));
     return PFMPE_OK;
   }
   std::vector<uint64_t> h(rows * kStamps);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->d_stamps, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(h.data(), c->d_stamps.get(), h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   for (int i = 0; i < kStamps; ++i) {
     const bool is_min = i == 0 || i == 4 || i == 19;
@@ -1352,6 +1185,7 @@ int pfmpe_get_info(const pfmpe_ctx* c, int key, int64_t* value) {
     case PFMPE_INFO_N: *value = c->N; return PFMPE_OK;
     case 110: case 111: case 112: case 113: *value = c->mt_ns[key - 110]; return PFMPE_OK;  // batch host timing
     case 114: *value = c->mt_batches; return PFMPE_OK;
+    case 115: *value = live_blocks().load(); return PFMPE_OK;  // buffers alive in this process (any context)
     default: return PFMPE_E_ARG;
   }
 }

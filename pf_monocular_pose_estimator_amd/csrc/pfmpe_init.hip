@@ -17,7 +17,7 @@
 // Integer histogram increments are commutative, so the device enumerates combinations in colex order
 // and marker triples in any order; the reference's lexicographic order only matters for
 // checkCorrespondences (particle slot order), which keeps it.
-#include "pfmpe_ctx.hpp"
+#include "pfmpe_prior.hpp"
 #include "pf_p3p.hpp"
 
 using namespace pfmpe;
@@ -352,71 +352,8 @@ struct Arena {
   }
 };
 
-int ensure_init(pfmpe_ctx* c, size_t bytes) {
-  if (bytes <= c->init_cap) return PFMPE_OK;
-  if (c->d_init) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(c->d_init));
-    c->d_init = nullptr;
-    c->init_cap = 0;
-  }
-  HIPCHK(c, hipMalloc((void**)&c->d_init, bytes));
-  c->init_cap = bytes;
-  return PFMPE_OK;
-}
-
-int ensure_xfer(pfmpe_ctx* c) {
-  if (!c->d_xfer) HIPCHK(c, hipMalloc((void**)&c->d_xfer, (size_t)c->max_particles * 12 * sizeof(double)));
-  return PFMPE_OK;
-}
-
-template <typename T, typename SP>
-void export1(pfmpe_ctx* c) {
-  Pose12<T> a;
-  for (int q = 0; q < 12; ++q) a.v[q] = (T)c->anchor[c->prior_idx][q];
-  hipLaunchKernelGGL((k_export<T, SP>), dim3(1), dim3(64), 0, c->stream, (const SP*)c->d_state[c->prior_idx],
-                     c->d_xfer, 1, c->ld, a, prior_owner_ptr(c));
-}
-// slot 0 of the resident set -> d_xfer[0..11]
-int export_slot0(pfmpe_ctx* c) {
-  if (c->state_dtype == PFMPE_STATE_F64)
-    export1<double, double>(c);
-  else if (c->state_dtype == PFMPE_STATE_F16)
-    export1<float, __half>(c);
-  else
-    export1<float, float>(c);
-  HIPCHK(c, hipGetLastError());
-  return PFMPE_OK;
-}
-
-template <typename T, typename SP>
-void import_n(pfmpe_ctx* c, int N, int slot) {
-  Pose12<T> a;
-  for (int q = 0; q < 12; ++q) a.v[q] = (T)c->anchor[slot][q];
-  hipLaunchKernelGGL((k_import<T, SP>), dim3((N + 255) / 256), dim3(256), 0, c->stream, c->d_xfer,
-                     (SP*)c->d_state[slot], N, c->ld, a);
-}
-// d_xfer (N x 12) -> the prior buffer, as pfmpe_set_prior does; anchor = the given pose
-int import_xfer(pfmpe_ctx* c, int N, const double* anchor) {
-  const int slot = c->prior_idx;
-  std::memcpy(c->anchor[slot], anchor, 12 * sizeof(double));
-  c->prior_owner = -1;  // stored in particle order
-  if (c->state_dtype == PFMPE_STATE_F64)
-    import_n<double, double>(c, N, slot);
-  else if (c->state_dtype == PFMPE_STATE_F16)
-    import_n<float, __half>(c, N, slot);
-  else
-    import_n<float, float>(c, N, slot);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_winkey, 0, kWinBytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_counters, 0, counters_bytes(c), c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->N = N;
-  c->has_prior = true;
-  c->has_last = false;
-  return PFMPE_OK;
-}
+// the initialisation scratch, grown to exactly what a stage needs
+int ensure_init(pfmpe_ctx* c, size_t bytes) { return c->d_init.grow(c, bytes, bytes); }
 
 InitArgs make_args(const pfmpe_ctx* c, int B) {
   InitArgs ia{};
@@ -461,7 +398,7 @@ int run_histogram(pfmpe_ctx* c, const double* blobs, int B, uint32_t* hist) {
   const size_t o_sxy = ar.take<double>(2 * (size_t)B), o_sidx = ar.take<int>(B);
   const size_t o_pass = ar.take<uint8_t>((size_t)ia.ncomb), o_hist = ar.take<uint32_t>((size_t)B * c->M);
   RET(ensure_init(c, ar.off));
-  unsigned char* d = c->d_init;
+  unsigned char* d = c->d_init.get();
   double* d_blobs = (double*)(d + o_blobs);
   double* d_iv = (double*)(d + o_iv);
   double* d_sxy = (double*)(d + o_sxy);
@@ -761,7 +698,7 @@ int pfmpe_initialise(pfmpe_ctx* c, const double* blobs, int B, const pfmpe_init_
       c->timing_now = false;
       return rc;
     }
-    unsigned char* d = c->d_init;
+    unsigned char* d = c->d_init.get();
     double* d_blobs = (double*)(d + o_blobs);
     double* d_iv = (double*)(d + o_iv);
     HIPCHK(c, hipMemcpyAsync(d_blobs, blobs, 2 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -853,20 +790,20 @@ int pfmpe_initialise(pfmpe_ctx* c, const double* blobs, int B, const pfmpe_init_
     Arena ar;
     const size_t o_e = ar.take<double>(est.size());
     RET(ensure_init(c, ar.off));
-    HIPCHK(c, hipMemcpyAsync(c->d_init + o_e, est.data(), est.size() * sizeof(double), hipMemcpyHostToDevice,
+    HIPCHK(c, hipMemcpyAsync(c->d_init.get() + o_e, est.data(), est.size() * sizeof(double), hipMemcpyHostToDevice,
                              c->stream));
     if (K < N) {  // slot 0 keeps the resident set's slot 0 (identity when there is none)
       if (c->has_prior) {
-        RET(export_slot0(c));
+        RET(export_prior(c, 1));
       } else {
         static const double I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-        HIPCHK(c, hipMemcpyAsync(c->d_xfer, I12, sizeof(I12), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_xfer.get(), I12, sizeof(I12), hipMemcpyHostToDevice, c->stream));
       }
     }
-    hipLaunchKernelGGL(k_init_seed, dim3((N + 255) / 256), dim3(256), 0, c->stream, (const double*)(c->d_init + o_e),
-                       K, N, c->d_xfer);
+    hipLaunchKernelGGL(k_init_seed, dim3((N + 255) / 256), dim3(256), 0, c->stream, (const double*)(c->d_init.get() + o_e),
+                       K, N, c->d_xfer.get());
     HIPCHK(c, hipGetLastError());
-    RET(import_xfer(c, N, est.data()));  // anchor (fp16 state): the first stored estimate
+    RET(import_prior(c, N, est.data()));  // anchor (fp16 state): the first stored estimate
   }
   return PFMPE_OK;
 }

@@ -1,0 +1,47 @@
+#pragma once
+// pfmpe_prior.hpp — the resident particle set to and from the transfer buffer d_xfer (N x 12 doubles), for the
+// three storage types.  Included only by the translation units that move particle sets (pfmpe_engine.hip,
+// pfmpe_init.hip): each of them instantiates k_import / k_export.
+#include "pfmpe_ctx.hpp"
+
+namespace pfmpe_impl {
+
+// Install d_xfer's first N poses as the prior, stored in particle order: the import launch (anchor: the fp16
+// state's anchor pose), the hand-off state zeroed for the first frame, all waited for.
+inline int import_prior(pfmpe_ctx* c, int N, const double* anchor) {
+  std::memcpy(c->anchor[c->prior_idx], anchor, 12 * sizeof(double));
+  c->prior_owner = -1;
+  visit_state(c, [&](auto s) {
+    using T = typename decltype(s)::T;
+    using SP = typename decltype(s)::SP;
+    Pose12<T> a;
+    for (int q = 0; q < 12; ++q) a.v[q] = (T)anchor[q];
+    hipLaunchKernelGGL((k_import<T, SP>), dim3((N + 255) / 256), dim3(256), 0, c->stream, c->d_xfer.get(),
+                       (SP*)c->d_state[c->prior_idx].get(), N, c->ld, a);
+  });
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemsetAsync(c->d_ctrl.get(), 0, sizeof(Ctrl), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_winkey.get(), 0, kWinBytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counters.get(), 0, counters_bytes(c), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->N = N;
+  c->has_prior = true;
+  c->has_last = false;
+  return PFMPE_OK;
+}
+
+// The prior's first `count` particles -> d_xfer (enqueued; through the owner indices of a deferred prior).
+inline int export_prior(pfmpe_ctx* c, int count) {
+  visit_state(c, [&](auto s) {
+    using T = typename decltype(s)::T;
+    using SP = typename decltype(s)::SP;
+    Pose12<T> a;
+    for (int q = 0; q < 12; ++q) a.v[q] = (T)c->anchor[c->prior_idx][q];
+    hipLaunchKernelGGL((k_export<T, SP>), dim3((count + 255) / 256), dim3(256), 0, c->stream,
+                       (const SP*)c->d_state[c->prior_idx].get(), c->d_xfer.get(), count, c->ld, a, prior_owner_ptr(c));
+  });
+  HIPCHK(c, hipGetLastError());
+  return PFMPE_OK;
+}
+
+}  // namespace pfmpe_impl

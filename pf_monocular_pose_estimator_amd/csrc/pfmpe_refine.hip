@@ -151,7 +151,7 @@ static_assert(sizeof(pfmpe_refine_row) / sizeof(double) + 36 <= kWave, "k_refine
 
 int refine_launch(pfmpe_ctx* c, const pfmpe_refine_params& prm, const double* poses, const uint32_t* corr, int64_t base,
                   int count, int cap, bool begin) {
-  unsigned char* d = c->d_refine;
+  unsigned char* d = c->d_refine.get();
   RefineArgs ra{};
   ra.poses = poses;
   ra.corr = corr;

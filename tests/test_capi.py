@@ -76,3 +76,12 @@ def test_create_without_gpu_fails_cleanly():
         pytest.skip("a GPU driver is present")
     with pytest.raises(pf.PFError):
         pf.Engine(device=0, max_particles=10)
+    # twice through the C-ABI itself: the failure path deletes the half-built context (its destructor frees
+    # whatever was allocated), so a second attempt fails the same way and neither leaves a handle behind
+    lib = pf.load()
+    codes = []
+    for _ in range(2):
+        ctx = ctypes.c_void_p(1)  # a non-null value the call has to clear
+        codes.append(lib.pfmpe_create(ctypes.byref(ctx), 0, 10, _capi.MAX_MARKERS, _capi.MAX_BLOBS, _capi.STATE_F32))
+        assert not ctx.value
+    assert codes[0] == codes[1] and codes[0] != _capi.OK

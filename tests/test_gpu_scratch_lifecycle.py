@@ -1,0 +1,209 @@
+"""Lifecycle of the engine's scratch: every buffer a context allocates lazily or grows on demand is freed with it.
+
+A context B is driven through every entry point that owns lazily allocated scratch, each grow-on-demand owner small
+first and then larger, so the growth path (drain the stream, free, allocate anew) runs.  After each growth the call's
+result must equal the same call on a context whose scratch was allocated at that size straight away: a stale device
+alias of a regrown pinned block, or a block freed while work on it was pending, shows there.  Then everything but a
+keeper context is destroyed and the process-wide count of live blocks (undocumented info key 115, readable through
+any context) must be back where it was: device free-memory readings cannot tell that on a shared machine.
+
+Shapes are the smallest that reach each path: M = 5, B = 8, N = 300 (two blocks, the second partial).
+
+step_multi's batch scratch starts at 64 KiB and holds one descriptor per stream, so it only grows with the stream
+count: the smallest count whose need (batch_layout, csrc/pfmpe_ctx.hpp, mirrored in batch_need below) exceeds 64 KiB
+is 58 one-block streams for fp32 / fp16 state and 38 for fp64, within the 64 streams of 256 particles a test may
+spend, so that growth is driven too (every stream reads a staged bank frame: the need then depends on nothing else).
+
+pfmpe_initialise returns before it touches the device when B < M, so the call at B = 4 is preceded by
+pfmpe_p3p_histogram on the same four blobs, which allocates the initialisation scratch at its small size."""
+import gc
+
+import numpy as np
+import pytest
+
+import pf_monocular_pose_estimator_amd as pf
+from pf_monocular_pose_estimator_amd import synthetic as syn
+
+pytestmark = pytest.mark.gpu
+
+STATES = {"f64": pf.STATE_F64, "f32": pf.STATE_F32, "f16": pf.STATE_F16}
+INFO_LIVE_BLOCKS = 115
+M, B, N, CAP = 5, 8, 300, 2048
+# sizeof(StreamDesc<T, SP>) (csrc/pf_kernels.hpp): the frame arguments in the compute type + the stream's pointers
+DESC_BYTES = {"f64": 1728, "f32": 1136, "f16": 1136}
+D = syn.D_README
+
+
+def al256(x):
+    return (x + 255) // 256 * 256
+
+
+def batch_need(desc, streams, blocks, tbytes=0):
+    boff = tbytes + al256(streams * desc)
+    soff = boff + al256(2 * blocks)
+    return soff + 4 * streams + 256
+
+
+def growth_streams(desc):
+    s = 1
+    while batch_need(desc, s, s) <= 1 << 16:
+        s += 1
+    return s
+
+
+@pytest.fixture(scope="module")
+def stream():
+    return syn.make_stream(syn.StreamConfig("t", M=M, B=B, N=N, seed=3), 4)
+
+
+def engine(state, cap, st, n=None):
+    e = pf.Engine(device=0, max_particles=cap, state_dtype=STATES[state])
+    e.set_model(st.markers, st.K)
+    prm = pf.default_params()
+    prm.rng_mode = pf.RNG_PHILOX
+    e.set_params(prm)
+    if n:
+        e.set_prior(st.prior(n, fast=True))
+    return e
+
+
+def frame(e, st, f, bank=False):
+    fr = st.frames[f]
+    kw = dict(bank_frame=f, B=len(fr.blobs)) if bank else dict(blobs=fr.blobs)
+    return e.make_frame(fr.current_pose, fr.predicted_pose, fr.prediction, dt=fr.dt, seed=11 + f, frame_idx=f, **kw)
+
+
+def roi_in(st, f):
+    fr = st.frames[f]
+    return pf.Engine.make_roi_in(fr.prediction, fr.predicted_pose, D, 752, 480, 5)
+
+
+def led_picture(w, h, seed):
+    """noise below the threshold and four saturated discs of ~35 px"""
+    img = np.random.default_rng(seed).integers(0, 60, size=(h, w)).astype(np.float64)
+    yy, xx = np.mgrid[0:h, 0:w]
+    for cx, cy in [(0.2, 0.25), (0.55, 0.3), (0.35, 0.7), (0.8, 0.75)]:
+        img = np.maximum(img, np.clip(4.2 - np.hypot(xx - cx * w, yy - cy * h), 0.0, 1.0) * 255.0)
+    return np.rint(img).astype(np.uint8)
+
+
+def same_detections(got, want):
+    assert len(got) == len(want)
+    for (u, d, info), (u2, d2, info2) in zip(got, want):
+        assert info == info2 and np.array_equal(u, u2) and np.array_equal(d, d2)
+
+
+def same_dict(got, want):
+    assert got.keys() == want.keys()
+    for k in got:
+        assert np.array_equal(np.asarray(got[k]), np.asarray(want[k])), k
+
+
+def same_records(got, want):
+    for a, b in zip(got, want):
+        assert bytes(a) == bytes(b)
+
+
+def close(engines):
+    for e in engines:
+        e.close()
+
+
+@pytest.mark.parametrize("state", ["f64", "f32", "f16"])
+def test_every_scratch_owner_is_freed_with_its_context(state, stream):
+    st = stream
+    gc.collect()  # engines other tests left to the collector are gone before the count is read
+    keeper = engine(state, 256, st)
+    base = keeper.info(INFO_LIVE_BLOCKS)
+    e = engine(state, CAP, st, N)
+    assert keeper.info(INFO_LIVE_BLOCKS) > base
+    blobs = st.frames[0].blobs
+
+    # ---- allocate on first use: the transfer buffer, the kept sets, counts, the bank and its rebuild, ROI, cloud,
+    # association, pairs, refinement
+    e.step(frame(e, st, 0))
+    assert e.get_particles(0).shape == e.get_particles(1).shape == (N, 12)
+    assert e.get_weights().shape == (N,)
+    e.set_option(pf.OPT_RECORD_COUNTS, 1)
+    if e.step(frame(e, st, 1)).resampled:
+        assert e.get_counts().shape == (N,)
+    e.stage_blob_bank([f.blobs for f in st.frames])
+    prm = pf.default_params()
+    prm.rng_mode = pf.RNG_PHILOX
+    prm.tol_pf = 3.0  # the bank's grids depend on it: rebuilt aside and swapped in
+    e.set_params(prm)
+    e.step(frame(e, st, 2, bank=True))
+    e.predict_roi(st.frames[3].prediction, st.frames[3].predicted_pose, D, 752, 480, 5)
+    ref = st.frames[2].current_pose
+    assert e.cloud_stats(pf.CLOUD_POSTERIOR, ref)["n"] == e.cloud_stats(pf.CLOUD_WEIGHTED, ref)["n"] == N
+    assert e.assoc_stats(pf.ASSOC_POSTERIOR, blobs)["n"] == e.assoc_stats(pf.ASSOC_PROPAGATED, bank_frame=2)["n"] == N
+    pairs, _ = e.get_pairs(pf.ASSOC_POSTERIOR, blobs, count=4)
+    assert e.refine_poses(e.get_particles(1)[:4], pairs, blobs)["n"] == 4
+    assert e.refine_cloud(pf.ASSOC_POSTERIOR, blobs, count=4)["n"] == N
+
+    # ---- grow on demand, each compared with a context that allocates the larger size at once
+    fresh = engine(state, CAP, st, N)
+    b4, _ = syn.init_blobs(M, 0, seed=1)
+    b12, _ = syn.init_blobs(M, 7, seed=1)
+    e.p3p_histogram(b4[:4])
+    assert e.initialise(b4[:4], n_particles=N)[0]["flag_fail"] == 10
+    got, want = e.initialise(b12, n_particles=N), fresh.initialise(b12, n_particles=N)
+    same_dict(got[0], want[0])
+    assert got[0]["hist_total"] > 0 and np.array_equal(got[1], want[1])
+
+    small, large = led_picture(64, 48, 1), led_picture(128, 96, 2)
+    e.stage_image(small)
+    assert e.find_leds(D=D)[2]["n"] >= 1
+    e.stage_image(large)
+    fresh.stage_image(large)
+    got, want = e.find_leds(D=D), fresh.find_leds(D=D)
+    assert got[2]["n"] >= 1
+    same_detections([got], [want])
+    rois = [(0, 0, 64, 48), (64, 0, 64, 48), (0, 48, 64, 48), None]
+    e.find_leds_multi(rois=rois[:1], D=D)
+    same_detections(e.find_leds_multi(rois=rois, D=D), fresh.find_leds_multi(rois=rois, D=D))
+
+    third, extra = engine(state, CAP, st), engine(state, CAP, st)
+    for x in (e, third):
+        x.set_prior(st.prior(256, fast=True))
+    pf.Engine.predict_roi_multi([e, third], [roi_in(st, 0)] * 2)
+    for x in (e, third, extra, fresh):
+        x.set_prior(st.prior(CAP, fast=True))
+    for got, want in zip(pf.Engine.predict_roi_multi([e, third, extra], [roi_in(st, 0)] * 3),
+                         pf.Engine.predict_roi_multi([fresh, third, extra], [roi_in(st, 0)] * 3)):
+        same_dict(got, want)
+
+    S = growth_streams(DESC_BYTES[state])
+    assert S <= 64 and batch_need(DESC_BYTES[state], 2, 2) <= 1 << 16
+    members = [third, extra] + [engine(state, 256, st) for _ in range(S - 3)]
+    for x in [fresh] + members:
+        x.stage_blob_bank([f.blobs for f in st.frames])
+        x.set_params(prm)
+
+    def batch(leader, group):
+        for x in group:
+            x.set_prior(st.prior(256, fast=True))
+        return pf.Engine.step_multi(group, [frame(x, st, 0, bank=True) for x in group]), leader.get_particles(1)
+
+    batch(e, [e, third])
+    got, want = batch(e, [e] + members), batch(fresh, [fresh] + members)
+    same_records(got[0], want[0])
+    assert np.array_equal(got[1], want[1])
+
+    close([e, fresh] + members)
+    assert keeper.info(INFO_LIVE_BLOCKS) == base
+    keeper.close()
+
+
+@pytest.mark.parametrize("state", ["f64", "f32", "f16"])
+def test_leader_destroyed_while_a_member_holds_its_fence(state, stream):
+    st = stream
+    gc.collect()
+    keeper = engine(state, 256, st)
+    base = keeper.info(INFO_LIVE_BLOCKS)
+    leader, member = engine(state, 256, st, 256), engine(state, 256, st, 256)
+    pf.Engine.step_multi([leader, member], [frame(leader, st, 0), frame(member, st, 0)])
+    leader.close()  # the member's latest work is the batch on the leader's stream
+    member.close()
+    assert keeper.info(INFO_LIVE_BLOCKS) == base
+    keeper.close()
