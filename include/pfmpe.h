@@ -301,6 +301,58 @@ int pfmpe_find_leds_multi(pfmpe_ctx* ctx, const uint8_t* image, int width, int h
                           const pfmpe_detect_params* params, int R, double* blobs, float* distorted,
                           int max_out, pfmpe_detect_out* out);
 
+#define PFMPE_DETECT_MAX_IMAGES 64
+
+/* R detector entries over the images of up to PFMPE_DETECT_MAX_IMAGES cameras, one launch sequence, one
+ * synchronise: the detector stage of a multi-camera frame, between the batched ROI prediction and the batched PF
+ * step.  Entry r detects in images[image_of[r]] with params[r] (a complete record, as for the one-image batch) and
+ * with K of that image's context; blobs / distorted / out are laid out as for the one-image batch (R x max_out x 2,
+ * out[r]).  Entry r's rows and out[r] are the bits the single-ROI call on images[image_of[r]].ctx returns for that
+ * image and params[r] while overflow is 0; min(n, max_out, PFMPE_MAX_BLOBS) rows are written and nothing else of the
+ * arrays is touched.  Of a host image only the pixels of its entries' ROIs cross the host link (the upload plan
+ * below); image = NULL reads the context's staged image in place.  Contexts of any state types may be mixed and a
+ * context may appear under several images; all must be on one device.  images[0].ctx leads: the batch runs on its
+ * stream, in its batch scratch, fills its last-error text and is one PFMPE_K_DETECT bracket of its timing (nothing
+ * is added to another context's statistics).  Blocking.  No context's staged image, model or particle state changes.
+ * Everything is checked before anything is packed, staged or launched and out is untouched on an error:
+ * PFMPE_E_ARG (a NULL pointer or a NULL ctx; I < 1, R < 1, max_out < 0, an image_of[r] outside 0 .. I - 1; an image
+ * with width or height < 1 or pitch < width; contexts on different devices; an ROI outside its image or
+ * gaussian_sigma outside (0, 5]: "find_leds_streams: roi <r>: ..."), PFMPE_E_CAP (R > PFMPE_DETECT_MAX_ROIS or
+ * I > PFMPE_DETECT_MAX_IMAGES), PFMPE_E_STATE (a context without a model, or image = NULL on a context with no staged
+ * image of that width, height and pitch).  With images = NULL or images[0].ctx = NULL: PFMPE_E_ARG, no error text. */
+typedef struct {
+  pfmpe_ctx* ctx;        /* the camera's context: K of its model; its staged image when image == NULL   */
+  const uint8_t* image;  /* host, 8-bit grey; NULL = ctx's staged image                                 */
+  int32_t width, height, pitch, pad;
+} pfmpe_detect_image;    /* 32 bytes */
+int pfmpe_find_leds_streams(const pfmpe_detect_image* images, int I, const int32_t* image_of,
+                            const pfmpe_detect_params* params, int R, double* blobs, float* distorted, int max_out,
+                            pfmpe_detect_out* out);
+
+/* host-only (no GPU, no context: the ctx fields may be NULL): the upload plan of the call above, and its pack.
+ * An entry's rectangle is its ROI in its image (roi_w < 0: the whole width, roi_h < 0: the whole height).  An entry
+ * on a staged image gets offset -1, the image's pitch and shared_with -1.  An entry r on a host image is served by
+ * its owner: of the entries of the same image index whose rectangle contains r's (r included), the one of the
+ * largest area, the lowest index on a tie.  An entry that owns itself has its own crop: pitch = its width rounded
+ * up to a multiple of 16, start 256-byte aligned, own crops in ascending entry index with no other gaps.  An entry
+ * owned by q has shared_with = q, q's pitch and offset = crops[q].offset + (y_r - y_q) * pitch + (x_r - x_q): the
+ * retry on an enlarged ROI (PE:452-463) uploads nothing extra.  upload_bytes: the end of the last own crop rounded
+ * up to 256 (0 without an own crop).  The pack copies every own crop's rows out of the caller's images (pageable,
+ * any pitch >= width) to the planned offsets and writes every other byte of buffer[0 .. upload_bytes) as 0; crops
+ * must be the plan of the same batch.  Errors leave the outputs untouched: the geometric checks and codes of the
+ * call above, PFMPE_E_ARG for crops that are not the batch's plan, PFMPE_E_CAP for buffer_bytes < upload_bytes. */
+typedef struct {
+  int64_t offset;        /* byte offset of the entry's top-left ROI pixel in the upload buffer; -1: staged image */
+  int32_t pitch;         /* row pitch at that offset                                                    */
+  int32_t shared_with;   /* -1: own crop (or staged); else the entry whose crop holds this entry's pixels */
+} pfmpe_detect_crop;     /* 16 bytes */
+int pfmpe_host_detect_plan(const pfmpe_detect_image* images, int I, const int32_t* image_of,
+                           const pfmpe_detect_params* params, int R, pfmpe_detect_crop* crops,
+                           int64_t* upload_bytes);
+int pfmpe_host_detect_pack(const pfmpe_detect_image* images, int I, const int32_t* image_of,
+                           const pfmpe_detect_params* params, int R, const pfmpe_detect_crop* crops,
+                           uint8_t* buffer, int64_t buffer_bytes);
+
 /* host-only: the reference's ROI enlargement (PE:429-432 with margin = ROI_distVal, PE:454-457 with margin = 20):
  *   x' = max(x - margin, 0), y' = max(y - margin, 0),
  *   w' = min(w + 2 margin, image_w - x'), h' = min(h + 2 margin, image_h - y')   (note: x', y', as the reference)

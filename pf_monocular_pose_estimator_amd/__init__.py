@@ -19,6 +19,7 @@ from ._capi import (  # noqa: F401
     RefineOut, default_refine_params, host_optimise_pose,
     DETECT_MAX_ROIS, DetectParams, DetectOut, host_grow_roi,
     ROI_MAX_STREAMS, RoiIn, RoiOut, host_predict_roi,
+    DETECT_MAX_IMAGES, DIAG_DET_COPY, DetectImage, DetectCrop, host_detect_plan, host_detect_pack,
 )
 
 __all__ = [

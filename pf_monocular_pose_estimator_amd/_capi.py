@@ -26,6 +26,7 @@ OPT_DIAG = 99  # undocumented diagnostic switches (csrc/pf_kernels.hpp kDiag*)
 DIAG_LAG_LOADS, DIAG_ABANDON, DIAG_NO_STREAM, DIAG_FORCE_STREAM, DIAG_SERIAL_TOP = 64, 128, 512, 1024, 2048
 DIAG_NO_PK, DIAG_CORRUPT_DESC, DIAG_NO_DEFER, DIAG_BLOCK_RESAMPLE, DIAG_MIN_SIDE = 4096, 8192, 16384, 32768, 65536
 DIAG_ABANDON_FINISH = 131072
+DIAG_DET_COPY = 524288  # find_leds_streams: the crops go up by one async copy command instead of the pull kernel (A/B)
 DIAG_ASSOC_DIRECT = 262144  # assoc_stats: every vote straight into the device table (the path of tables too large for LDS)
 OPT_DEFER_RESAMPLE = 9
 SHAPE_TWO_LAUNCH, SHAPE_FRAME, SHAPE_FRAME2 = 0, 1, 2
@@ -54,8 +55,10 @@ EXPORTED_SYMBOLS = (
     "pfmpe_default_refine_params", "pfmpe_refine_poses", "pfmpe_refine_cloud", "pfmpe_host_optimise_pose",
     "pfmpe_find_leds_multi", "pfmpe_host_grow_roi",
     "pfmpe_predict_roi_multi", "pfmpe_host_predict_roi",
+    "pfmpe_find_leds_streams", "pfmpe_host_detect_plan", "pfmpe_host_detect_pack",
 )
 DETECT_MAX_ROIS = 64
+DETECT_MAX_IMAGES = 64
 ROI_MAX_STREAMS = 64
 
 
@@ -121,6 +124,15 @@ class DetectParams(C.Structure):
 
 class DetectOut(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_components", C.c_int32), ("overflow", C.c_int32), ("pad", C.c_int32)]
+
+
+class DetectImage(C.Structure):
+    _fields_ = [("ctx", C.c_void_p), ("image", C.POINTER(C.c_uint8)), ("width", C.c_int32), ("height", C.c_int32),
+                ("pitch", C.c_int32), ("pad", C.c_int32)]
+
+
+class DetectCrop(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("pitch", C.c_int32), ("shared_with", C.c_int32)]
 
 
 class LaunchConfig(C.Structure):
@@ -284,6 +296,12 @@ def load() -> C.CDLL:
         "pfmpe_find_leds_multi": (I, [P, C.POINTER(C.c_uint8), I, I, I, C.POINTER(DetectParams), I, dp,
                                       C.POINTER(C.c_float), I, C.POINTER(DetectOut)]),
         "pfmpe_host_grow_roi": (I, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+        "pfmpe_find_leds_streams": (I, [C.POINTER(DetectImage), I, C.POINTER(C.c_int32), C.POINTER(DetectParams), I, dp,
+                                        C.POINTER(C.c_float), I, C.POINTER(DetectOut)]),
+        "pfmpe_host_detect_plan": (I, [C.POINTER(DetectImage), I, C.POINTER(C.c_int32), C.POINTER(DetectParams), I,
+                                       C.POINTER(DetectCrop), C.POINTER(I64)]),
+        "pfmpe_host_detect_pack": (I, [C.POINTER(DetectImage), I, C.POINTER(C.c_int32), C.POINTER(DetectParams), I,
+                                       C.POINTER(DetectCrop), C.POINTER(C.c_uint8), I64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -570,6 +588,41 @@ class Engine:
         # the C arrays' ROI stride is 2 * max_out; the numpy rows are max(max_out, 1) wide, the same unless max_out = 0
         self._chk(self.lib.pfmpe_find_leds_multi(self.ctx, ip, w, h, pitch, ps, R, _dptr(blobs),
                                                  dist.ctypes.data_as(C.POINTER(C.c_float)), max_out, outs))
+        res = []
+        for r in range(R):
+            n = min(outs[r].n, max_out)
+            res.append((blobs[r, :n].copy(), dist[r, :n].copy(),
+                        {"n": outs[r].n, "n_components": outs[r].n_components, "overflow": outs[r].overflow}))
+        return res
+
+    @staticmethod
+    def find_leds_streams(images, image_of, rois, D=None, params=None, max_out=MAX_BLOBS) -> list:
+        """pfmpe_find_leds_streams: R detector entries over the images of several cameras in one launch sequence.
+        images: a list of (engine, ndarray or None); None is that engine's staged image, and an array's rows may be
+        non-contiguous (they are passed with their pitch).  Entry r is the ROI rois[r] ((x, y, w, h), or None for the
+        whole image) of images[image_of[r]], with that engine's K.  D: one distortion vector for every entry, or a
+        list with one per entry; params: a dict of DetectParams fields for every entry, or a list with one dict per
+        entry.  images[0]'s engine leads the batch.  Returns one (undistorted, distorted, info) per entry, each as
+        find_leds returns it."""
+        R = len(rois)
+        if len(images) == 0 or R == 0 or len(image_of) != R:
+            raise ValueError("find_leds_streams: at least one image, and one image index per ROI")
+        per_roi = params if isinstance(params, (list, tuple)) else [params or {}] * R
+        if len(per_roi) != R:
+            raise ValueError("find_leds_streams: one params dict per ROI")
+        per_d = [D] * R if D is None or np.ndim(D) == 1 else list(D)
+        if len(per_d) != R:
+            raise ValueError("find_leds_streams: one D per ROI")
+        lead = images[0][0]
+        ims, keep = make_detect_images([(e.ctx, img, getattr(e, "_img_shape", None)) for e, img in images])
+        ps = make_detect_params(rois, per_d, per_roi)
+        idx = (C.c_int32 * R)(*[int(i) for i in image_of])
+        blobs = np.zeros((R, max(max_out, 1), 2))
+        dist = np.zeros((R, max(max_out, 1), 2), dtype=np.float32)
+        outs = (DetectOut * R)()
+        lead._chk(lead.lib.pfmpe_find_leds_streams(ims, len(images), idx, ps, R, _dptr(blobs),
+                                                   dist.ctypes.data_as(C.POINTER(C.c_float)), max_out, outs))
+        del keep
         res = []
         for r in range(R):
             n = min(outs[r].n, max_out)
@@ -866,6 +919,80 @@ def host_assoc_summary(votes) -> dict:
     d = out.as_dict()
     del d["n_any"], d["npairs_hist"]
     return d
+
+
+def make_detect_images(images):
+    """A DetectImage array from (ctx or None, ndarray or None, staged (h, w) or None) triples -> (array, the arrays
+    it points into).  An ndarray needs unit stride along a row; its row stride is passed as the pitch."""
+    ims = (DetectImage * max(len(images), 1))()
+    keep = []
+    for im, (ctx, img, staged) in zip(ims, images):
+        im.ctx = ctx
+        if img is not None:
+            a = np.asarray(img)
+            if a.dtype != np.uint8 or a.ndim != 2 or (a.shape[1] > 1 and a.strides[1] != 1) or a.strides[0] < a.shape[1]:
+                a = np.ascontiguousarray(a, dtype=np.uint8)
+            keep.append(a)
+            im.image = a.ctypes.data_as(C.POINTER(C.c_uint8))
+            im.height, im.width, im.pitch = a.shape[0], a.shape[1], a.strides[0]
+        else:
+            h, w = staged or (0, 0)
+            im.height, im.width, im.pitch = h, w, w
+    return ims, keep
+
+
+def make_detect_params(rois, per_d, per_roi):
+    """A DetectParams array: the defaults, then entry r's D (or None), ROI ((x, y, w, h) or None) and fields."""
+    ps = (DetectParams * max(len(rois), 1))()
+    for p, roi, d, kw in zip(ps, rois, per_d, per_roi):
+        load().pfmpe_default_detect_params(C.byref(p))
+        if d is not None:
+            p.D[:] = list(np.asarray(d, np.float64).reshape(5))
+        if roi is not None:
+            p.roi_x, p.roi_y, p.roi_w, p.roi_h = [int(v) for v in roi]
+        for k, v in (kw or {}).items():
+            setattr(p, k, v)
+    return ps
+
+
+def _host_detect_batch(images, image_of, rois):
+    """The C arrays of a host-only plan / pack call: images are ndarrays, or (h, w) shapes for staged images."""
+    trip = [(None, None, tuple(im)) if isinstance(im, tuple) else (None, im, None) for im in images]
+    ims, keep = make_detect_images(trip)
+    R = len(rois)
+    ps = make_detect_params(rois, [None] * R, [None] * R)
+    idx = (C.c_int32 * max(R, 1))(*[int(i) for i in image_of])
+    return ims, keep, ps, idx, R
+
+
+def host_detect_plan(images, image_of, rois) -> tuple:
+    """pfmpe_host_detect_plan: where the ROI pixels of a find_leds_streams batch land in its upload buffer.  images:
+    ndarrays (host images), or (h, w) tuples for staged images; rois[r]: (x, y, w, h) or None in images[image_of[r]].
+    Returns ([(offset, pitch, shared_with)] per entry, upload_bytes)."""
+    ims, keep, ps, idx, R = _host_detect_batch(images, image_of, rois)
+    crops = (DetectCrop * max(R, 1))()
+    nbytes = C.c_int64()
+    rc = load().pfmpe_host_detect_plan(ims, len(images), idx, ps, R, crops, C.byref(nbytes))
+    if rc != OK:
+        raise PFError(rc, "host_detect_plan: bad batch")
+    return [(c.offset, c.pitch, c.shared_with) for c in crops[:R]], nbytes.value
+
+
+def host_detect_pack(images, image_of, rois, crops=None, buffer_bytes=None) -> np.ndarray:
+    """pfmpe_host_detect_pack: the upload buffer of a find_leds_streams batch (uint8): every own crop's rows at the
+    planned offsets, every other byte 0.  crops / buffer_bytes default to the batch's plan."""
+    ims, keep, ps, idx, R = _host_detect_batch(images, image_of, rois)
+    if crops is None or buffer_bytes is None:
+        plan, nbytes = host_detect_plan(images, image_of, rois)
+        crops = plan if crops is None else crops
+        buffer_bytes = nbytes if buffer_bytes is None else buffer_bytes
+    cs = (DetectCrop * max(R, 1))(*[DetectCrop(*[int(v) for v in c]) for c in crops])
+    buf = np.zeros(max(int(buffer_bytes), 1), dtype=np.uint8)
+    rc = load().pfmpe_host_detect_pack(ims, len(images), idx, ps, R, cs, buf.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                       int(buffer_bytes))
+    if rc != OK:
+        raise PFError(rc, "host_detect_pack: bad batch, crops that are not its plan, or a buffer too small")
+    return buf[: int(buffer_bytes)]
 
 
 def host_grow_roi(roi, margin: int, image_w: int, image_h: int) -> tuple:

@@ -1655,8 +1655,10 @@ enum : int {
                                 // (the two-launch recovery tests)
   kDiagBlockResample = 32768, // deferred two-launch frames resample with the block-per-256 k_resample instead of
                               // k_resample_owners' wave per 256 (A/B, identity tests)
-  kDiagAssocDirect = 262144   // pfmpe_assoc_stats: every vote straight into the device table even when the bins fit
+  kDiagAssocDirect = 262144,  // pfmpe_assoc_stats: every vote straight into the device table even when the bins fit
                               // in LDS (tests: both voting paths on one input)
+  kDiagDetCopy = 524288       // pfmpe_find_leds_streams: the crops go up by one async copy command instead of the
+                              // pull kernel k_detm_pull (A/B)
 };
 __device__ __forceinline__ uint64_t rt_now() { return __builtin_amdgcn_s_memrealtime(); }
 // per-block stamps go to the block's own row (plain stores, no contended atomics); the host reduces rows

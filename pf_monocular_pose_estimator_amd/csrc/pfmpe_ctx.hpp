@@ -178,6 +178,9 @@ struct pfmpe_ctx : CtxQueue {
   Buf<unsigned char> d_detm;
   Buf<unsigned char, Mem::Mapped> h_detm;
   Buf<void, Mem::Mapped> h_detm_out;  // grown on demand
+  // pfmpe_find_leds_streams (owned by the batch's first context): the pinned, host-mapped pack of the ROI crops of the
+  // batch's host images, grown on demand; on the device they land in a region of d_detm
+  Buf<uint8_t, Mem::Mapped> h_detm_pix;
   // pfmpe_predict_roi_multi (owned by the batch's first context): the batch scratch (head + descriptors, then one
   // partial per block of the batch; grown on demand), and the pinned, host-mapped image of the head + descriptors
   // followed by the result boxes of PFMPE_ROI_MAX_STREAMS streams

@@ -22,7 +22,11 @@
 //
 // pfmpe_find_leds_multi runs the same stages over R ROIs of one image in one launch sequence (k_detm_*: flat
 // grids over all ROIs' tiles, pixels and components, one descriptor per ROI); the stage bodies are shared.
+// pfmpe_find_leds_streams runs that sequence over the images of several cameras: a descriptor carries its own K and
+// the address of its ROI's top-left pixel, in its context's staged image or in the crops the batch uploads
+// (pfmpe_detect_plan.hpp: only the ROIs' pixels of a host image cross the host link; k_detm_pull).
 #include "pfmpe_ctx.hpp"
+#include "pfmpe_detect_plan.hpp"
 
 using namespace pfmpe;
 using namespace pfmpe_impl;
@@ -63,8 +67,9 @@ __device__ __forceinline__ int refl101(int p, int len) {
 // The stage bodies below are shared by the single-ROI kernels (k_det_*: `a` is the kernel argument) and their
 // batched forms (k_detm_*: `a` is the ROI's descriptor in device memory, the buffers are that ROI's); `a` is
 // wave-uniform either way.
-// one 16 x 16 tile at (x0, y0) of the ROI; the whole block
-__device__ __forceinline__ void det_mask_tile(const DetArgs& a, const uint8_t* __restrict__ img,
+// one 16 x 16 tile at (x0, y0) of the ROI; the whole block.  pix: the ROI's top-left pixel, rows `pitch` apart (in the
+// image, or in a crop of it: a.rx / a.ry are only the offset added to the centres)
+__device__ __forceinline__ void det_mask_tile(const DetArgs& a, const uint8_t* __restrict__ pix, const int pitch,
                                               uint8_t* __restrict__ mask, const int x0, const int y0) {
   constexpr int T = kDetTile, HW = T + 2 * kDetMaxRadius;
   __shared__ int tb[HW][HW];    // thresholded tile + halo (rows, cols)
@@ -73,7 +78,7 @@ __device__ __forceinline__ void det_mask_tile(const DetArgs& a, const uint8_t* _
   for (int i = threadIdx.x; i < span * span; i += blockDim.x) {
     const int ty = i / span, tx = i - ty * span;
     const int gy = refl101(y0 + ty - r, a.H), gx = refl101(x0 + tx - r, a.W);
-    const int v = img[(int64_t)(a.ry + gy) * a.pitch + a.rx + gx];
+    const int v = pix[(int64_t)gy * pitch + gx];
     tb[ty][tx] = a.active ? (v > a.thr ? v : 0) : (v > a.thr ? 0 : 255);
   }
   __syncthreads();
@@ -95,7 +100,7 @@ __device__ __forceinline__ void det_mask_tile(const DetArgs& a, const uint8_t* _
 }
 __global__ __launch_bounds__(kDetTile* kDetTile) void k_det_mask(const DetArgs a, const uint8_t* __restrict__ img,
                                                                   uint8_t* __restrict__ mask) {
-  det_mask_tile(a, img, mask, blockIdx.x * kDetTile, blockIdx.y * kDetTile);
+  det_mask_tile(a, img + (int64_t)a.ry * a.pitch + a.rx, a.pitch, mask, blockIdx.x * kDetTile, blockIdx.y * kDetTile);
 }
 
 // Labelling, tile-local first: a 32 x 32 tile (+1 halo) of the mask in LDS gives each pixel its 8-neighbour
@@ -451,7 +456,10 @@ struct DetDesc {
   int* label;
   int* roots;
   DetRecord* rec;
+  const uint8_t* pix;        // the ROI's top-left pixel: in a staged image, or in the batch's uploaded crops
+  int pix_pitch;             // row pitch there
   int tiles16_x, tiles32_x;  // tiles per tile row
+  int pad;
 };
 // counters, zeroed per call: components per ROI, then the work list's length
 constexpr int kDetWorkCount = kDetMaxRois;
@@ -473,14 +481,24 @@ __global__ __launch_bounds__(kStageBlock) void k_detm_stage(const uint64_t* __re
   if (threadIdx.x <= kDetWorkCount) counters[threadIdx.x] = 0;
 }
 
+// The streams batch's crops (pfmpe_find_leds_streams) from the leader's host-mapped pinned buffer into the scratch:
+// n 16-byte words, one load per lane, consecutive lanes consecutive words, blocks grid-striding (the grid is sized
+// by n up to kPullMaxGrid).  The alternative, one async copy command, is kept behind kDiagDetCopy for the A/B.
+constexpr int kPullBlock = 256;
+constexpr int kPullMaxGrid = 2048;
+__global__ __launch_bounds__(kPullBlock) void k_detm_pull(const uint4* __restrict__ src, uint4* __restrict__ dst,
+                                                          const int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * kPullBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kPullBlock)
+    dst[i] = src[i];
+}
+
 __global__ __launch_bounds__(kDetTile* kDetTile) void k_detm_mask(const DetBatch* __restrict__ hd,
-                                                                   const DetDesc* __restrict__ descs,
-                                                                   const uint8_t* __restrict__ img) {
+                                                                   const DetDesc* __restrict__ descs) {
   const int roi = det_roi_of_block(hd->first16, hd->R, blockIdx.x);
   const DetDesc& d = descs[roi];
   const int t = blockIdx.x - hd->first16[roi];
   const int ty = t / d.tiles16_x, tx = t - ty * d.tiles16_x;
-  det_mask_tile(d.a, img, d.mask, tx * kDetTile, ty * kDetTile);
+  det_mask_tile(d.a, d.pix, d.pix_pitch, d.mask, tx * kDetTile, ty * kDetTile);
 }
 
 __global__ __launch_bounds__(kLabelBlock) void k_detm_label(const DetBatch* __restrict__ hd,
@@ -588,10 +606,7 @@ int det_buffers(pfmpe_ctx* c, int64_t npix, DetBuffers& b) {
 
 // what is wrong with one ROI's parameters for a width x height image (nullptr: nothing)
 const char* det_check(const pfmpe_detect_params* prm, int width, int height) {
-  const int rx = prm->roi_w < 0 ? 0 : prm->roi_x, ry = prm->roi_h < 0 ? 0 : prm->roi_y;
-  const int W = prm->roi_w < 0 ? width : prm->roi_w, H = prm->roi_h < 0 ? height : prm->roi_h;
-  if (rx < 0 || ry < 0 || W < 1 || H < 1 || (int64_t)rx + W > width || (int64_t)ry + H > height)
-    return "ROI outside the image";
+  if (const char* why = pfmpe_plan::roi_geometry(prm, width, height)) return why;
   if (!(prm->gaussian_sigma > 0) || prm->gaussian_sigma > 5.0) return "gaussian_sigma must be in (0, 5]";
   return nullptr;
 }
@@ -608,10 +623,11 @@ DetArgs det_args(const pfmpe_ctx* c, const pfmpe_detect_params* prm, int width, 
   a.img_w = width;
   a.img_h = height;
   a.pitch = pitch;
-  a.rx = prm->roi_w < 0 ? 0 : prm->roi_x;
-  a.ry = prm->roi_h < 0 ? 0 : prm->roi_y;
-  a.W = prm->roi_w < 0 ? width : prm->roi_w;
-  a.H = prm->roi_h < 0 ? height : prm->roi_h;
+  const pfmpe_plan::Rect roi = pfmpe_plan::rect_of(prm, width, height);
+  a.rx = roi.x;
+  a.ry = roi.y;
+  a.W = roi.w;
+  a.H = roi.h;
   std::memcpy(a.K, c->K, sizeof(a.K));
   std::memcpy(a.D, prm->D, sizeof(a.D));
   a.min_area = prm->min_blob_area;
@@ -621,15 +637,16 @@ DetArgs det_args(const pfmpe_ctx* c, const pfmpe_detect_params* prm, int width, 
   return a;
 }
 
-// Batch scratch (pfmpe_find_leds_multi), one allocation: the counters, the batch head + R descriptors (the pinned
-// image h_detm is uploaded there), the work list, then per ROI mask | nbr | label | roots | rec, each 256-byte
-// aligned.  Fills the descriptors' pointers.
+// Batch scratch (pfmpe_find_leds_multi, pfmpe_find_leds_streams), one allocation: the counters, the batch head + R
+// descriptors (the pinned image h_detm is uploaded there), the work list, the uploaded crops (crop_bytes), then per ROI
+// mask | nbr | label | roots | rec, each 256-byte aligned.  Fills the descriptors' pointers.
 constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 constexpr size_t kDetmHead = al256(kDetCounterBytes);
 constexpr size_t kDetmDesc = kDetmHead + al256(sizeof(DetBatch));
-int detm_buffers(pfmpe_ctx* c, int R, DetDesc* descs, size_t* o_work) {
+int detm_buffers(pfmpe_ctx* c, int R, DetDesc* descs, size_t crop_bytes, size_t* o_work, size_t* o_crop) {
   *o_work = kDetmDesc + al256((size_t)R * sizeof(DetDesc));
-  size_t total = *o_work + al256((size_t)R * kDetMaxComponents * sizeof(uint32_t));
+  *o_crop = *o_work + al256((size_t)R * kDetMaxComponents * sizeof(uint32_t));  // the uploaded crops (streams batch)
+  size_t total = *o_crop + al256(crop_bytes);
   std::vector<size_t> base(R);
   for (int r = 0; r < R; ++r) {
     const size_t npix = (size_t)descs[r].a.W * descs[r].a.H;
@@ -646,6 +663,99 @@ int detm_buffers(pfmpe_ctx* c, int R, DetDesc* descs, size_t* o_work) {
     descs[r].label = (int*)(p += al256(npix));
     descs[r].roots = (int*)(p += al256(npix * 4));
     descs[r].rec = (DetRecord*)(p += al256(kDetMaxComponents * sizeof(int)));
+  }
+  return PFMPE_OK;
+}
+
+// A batch on its leader c (pfmpe_find_leds_multi, pfmpe_find_leds_streams), after every check: the pinned image of the
+// batch head and the descriptors, the scratch, the launch sequence, one synchronise, the results.  fill(r, d) sets
+// entry r's d.a and, for an entry that reads an image where it is, d.pix / d.pix_pitch.  An entry with
+// crops[r].offset >= 0 (crops null: none) reads the batch's uploaded crops: pack(p) writes their upload_bytes into the
+// leader's pinned buffer, which one more launch then moves into the scratch.
+template <typename Fill, typename Pack>
+int detm_run(pfmpe_ctx* c, int R, Fill&& fill, const pfmpe_detect_crop* crops, int64_t upload_bytes, Pack&& pack,
+             double* blobs, float* distorted, int max_out, pfmpe_detect_out* out) {
+  RET(c->h_detm.ensure(c, al256(sizeof(DetBatch)) + kDetMaxRois * sizeof(DetDesc)));
+  RET(c->h_detm_out.grow(c, (size_t)R * sizeof(DetOutHost), (size_t)R * sizeof(DetOutHost)));
+  if (upload_bytes > 0) RET(c->h_detm_pix.grow(c, (size_t)upload_bytes, (size_t)upload_bytes * 2));
+  // the pinned image of the batch head and the descriptors, then one upload
+  DetBatch* hd = (DetBatch*)c->h_detm.get();
+  DetDesc* descs = (DetDesc*)(c->h_detm.get() + al256(sizeof(DetBatch)));
+  std::memset(hd, 0, sizeof(*hd));
+  hd->R = R;
+  int n16 = 0, n32 = 0, npb = 0;
+  for (int r = 0; r < R; ++r) {
+    DetDesc& d = descs[r];
+    fill(r, d);
+    d.tiles16_x = (d.a.W + kDetTile - 1) / kDetTile;
+    d.tiles32_x = (d.a.W + kLT - 1) / kLT;
+    hd->first16[r] = n16;
+    hd->first32[r] = n32;
+    hd->firstpix[r] = npb;
+    n16 += d.tiles16_x * ((d.a.H + kDetTile - 1) / kDetTile);
+    n32 += d.tiles32_x * ((d.a.H + kLT - 1) / kLT);
+    npb += (int)(((int64_t)d.a.W * d.a.H + kPixBlock - 1) / kPixBlock);
+  }
+  size_t o_work = 0, o_crop = 0;
+  RET(detm_buffers(c, R, descs, (size_t)upload_bytes, &o_work, &o_crop));
+  for (int r = 0; crops && r < R; ++r)
+    if (crops[r].offset >= 0) {
+      descs[r].pix = c->d_detm.get() + o_crop + crops[r].offset;
+      descs[r].pix_pitch = crops[r].pitch;
+    }
+  if (upload_bytes > 0) pack(c->h_detm_pix.get());
+  int* counters = (int*)c->d_detm.get();
+  const DetBatch* dhd = (const DetBatch*)(c->d_detm.get() + kDetmHead);
+  const DetDesc* ddescs = (const DetDesc*)(c->d_detm.get() + kDetmDesc);
+  uint32_t* work = (uint32_t*)(c->d_detm.get() + o_work);
+  static_assert(sizeof(DetDesc) % sizeof(uint64_t) == 0, "k_detm_stage copies 8-byte words");
+  const int stage_words = (int)((al256(sizeof(DetBatch)) + (size_t)R * sizeof(DetDesc)) / sizeof(uint64_t));
+  const uint64_t* stage_src = (const uint64_t*)c->h_detm.dev();
+  DetOutHost* hout = (DetOutHost*)c->h_detm_out.get();
+  DetOutHost* dout = (DetOutHost*)c->h_detm_out.dev();
+  const int64_t pull_n = upload_bytes / (int64_t)sizeof(uint4);  // upload_bytes is a multiple of 256
+  const unsigned pull_grid = (unsigned)std::min<int64_t>((pull_n + kPullBlock - 1) / kPullBlock, kPullMaxGrid);
+  hipError_t copy_err = hipSuccess;
+  c->timing_now = c->timing > 0;
+  const int rl = launch(c, PFMPE_K_DETECT, [&] {
+    hipLaunchKernelGGL(k_detm_stage, dim3(1), dim3(kStageBlock), 0, c->stream, stage_src,
+                       (uint64_t*)(c->d_detm.get() + kDetmHead), stage_words, counters);
+    if (pull_n > 0) {
+      if (c->diag & kDiagDetCopy)
+        copy_err = hipMemcpyAsync(c->d_detm.get() + o_crop, c->h_detm_pix.get(), (size_t)upload_bytes,
+                                  hipMemcpyHostToDevice, c->stream);
+      else
+        hipLaunchKernelGGL(k_detm_pull, dim3(pull_grid), dim3(kPullBlock), 0, c->stream,
+                           (const uint4*)c->h_detm_pix.dev(), (uint4*)(c->d_detm.get() + o_crop), pull_n);
+    }
+    hipLaunchKernelGGL(k_detm_mask, dim3(n16), dim3(kDetTile * kDetTile), 0, c->stream, dhd, ddescs);
+    hipLaunchKernelGGL(k_detm_label, dim3(n32), dim3(kLabelBlock), 0, c->stream, dhd, ddescs);
+    hipLaunchKernelGGL(k_detm_merge, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs);
+    hipLaunchKernelGGL(k_detm_roots, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs, counters, work);
+    hipLaunchKernelGGL(k_detm_trace, dim3(512), dim3(64), 0, c->stream, ddescs, (const int*)counters,
+                       (const uint32_t*)work);
+    hipLaunchKernelGGL(k_detm_emit, dim3(R), dim3(kEmitBlock), 0, c->stream, ddescs, (const int*)counters, dout);
+  });
+  // whatever was enqueued is drained before returning, so a failure leaves nothing of the batch pending
+  const hipError_t se = hipStreamSynchronize(c->stream);
+  int rc = rl;
+  if (rc == PFMPE_OK && copy_err != hipSuccess)
+    rc = fail(c, PFMPE_E_HIP, std::string("crop upload: ") + hipGetErrorString(copy_err));
+  if (rc == PFMPE_OK && se != hipSuccess)
+    rc = fail(c, PFMPE_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
+  if (rc == PFMPE_OK && c->timing_now) rc = harvest_timing(c);
+  c->timing_now = false;
+  RET(rc);
+  for (int r = 0; r < R; ++r) {
+    const DetOutHost& h = hout[r];
+    const int nw = std::min(std::min(h.n, max_out), kMaxBlobs);
+    if (nw > 0) {
+      std::memcpy(blobs + (size_t)r * 2 * max_out, h.und, 2 * (size_t)nw * sizeof(double));
+      if (distorted) std::memcpy(distorted + (size_t)r * 2 * max_out, h.dist, 2 * (size_t)nw * sizeof(float));
+    }
+    out[r].n = h.n;
+    out[r].n_components = h.n_components;
+    out[r].overflow = h.overflow;
   }
   return PFMPE_OK;
 }
@@ -764,63 +874,59 @@ int pfmpe_find_leds_multi(pfmpe_ctx* c, const uint8_t* image, int width, int hei
       return fail(c, PFMPE_E_ARG, "find_leds_multi: roi " + std::to_string(r) + ": " + why);
   if (image) RET(pfmpe_stage_image(c, image, width, height, pitch));
   RET(set_device(c));
-  RET(c->h_detm.ensure(c, al256(sizeof(DetBatch)) + kDetMaxRois * sizeof(DetDesc)));
-  RET(c->h_detm_out.grow(c, (size_t)R * sizeof(DetOutHost), (size_t)R * sizeof(DetOutHost)));
-  // the pinned image of the batch head and the descriptors, then one upload
-  DetBatch* hd = (DetBatch*)c->h_detm.get();
-  DetDesc* descs = (DetDesc*)(c->h_detm.get() + al256(sizeof(DetBatch)));
-  std::memset(hd, 0, sizeof(*hd));
-  hd->R = R;
-  int n16 = 0, n32 = 0, npb = 0;
-  for (int r = 0; r < R; ++r) {
-    DetDesc& d = descs[r];
-    d.a = det_args(c, prm + r, width, height, pitch);
-    d.tiles16_x = (d.a.W + kDetTile - 1) / kDetTile;
-    d.tiles32_x = (d.a.W + kLT - 1) / kLT;
-    hd->first16[r] = n16;
-    hd->first32[r] = n32;
-    hd->firstpix[r] = npb;
-    n16 += d.tiles16_x * ((d.a.H + kDetTile - 1) / kDetTile);
-    n32 += d.tiles32_x * ((d.a.H + kLT - 1) / kLT);
-    npb += (int)(((int64_t)d.a.W * d.a.H + kPixBlock - 1) / kPixBlock);
+  return detm_run(
+      c, R,
+      [&](int r, DetDesc& d) {
+        d.a = det_args(c, prm + r, width, height, pitch);
+        d.pix = c->d_img.get() + (int64_t)d.a.ry * pitch + d.a.rx;
+        d.pix_pitch = pitch;
+      },
+      nullptr, 0, [](uint8_t*) {}, blobs, distorted, max_out, out);
+}
+
+int pfmpe_find_leds_streams(const pfmpe_detect_image* images, int I, const int32_t* image_of,
+                            const pfmpe_detect_params* prm, int R, double* blobs, float* distorted, int max_out,
+                            pfmpe_detect_out* out) {
+  if (!images || I < 1 || !images[0].ctx) return PFMPE_E_ARG;
+  pfmpe_ctx* c0 = images[0].ctx;
+  const std::string who = "find_leds_streams: ";
+  if (!out || max_out < 0 || (max_out > 0 && !blobs)) return fail(c0, PFMPE_E_ARG, who + "bad arguments");
+  std::string why;
+  if (const int rc = pfmpe_plan::check(images, I, image_of, prm, R, det_check, &why)) return fail(c0, rc, who + why);
+  std::vector<pfmpe_ctx*> ctxs{c0};  // the batch's contexts, each once, the leader first
+  for (int i = 0; i < I; ++i) {
+    const pfmpe_detect_image& im = images[i];
+    pfmpe_ctx* c = im.ctx;
+    const std::string at = who + "image " + std::to_string(i) + ": ";
+    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
+    if (c->device != c0->device) return fail(c0, PFMPE_E_ARG, at + "device must match images[0].ctx");
+    if (!c->has_model) return fail(c0, PFMPE_E_STATE, at + "set_model first (K)");
+    if (!im.image && (!c->d_img || c->img_w != im.width || c->img_h != im.height || c->img_pitch != im.pitch))
+      return fail(c0, PFMPE_E_STATE, at + "no staged image of this size (pfmpe_stage_image)");
+    if (std::find(ctxs.begin(), ctxs.end(), c) == ctxs.end()) ctxs.push_back(c);
   }
-  size_t o_work = 0;
-  RET(detm_buffers(c, R, descs, &o_work));
-  int* counters = (int*)c->d_detm.get();
-  const DetBatch* dhd = (const DetBatch*)(c->d_detm.get() + kDetmHead);
-  const DetDesc* ddescs = (const DetDesc*)(c->d_detm.get() + kDetmDesc);
-  uint32_t* work = (uint32_t*)(c->d_detm.get() + o_work);
-  static_assert(sizeof(DetDesc) % sizeof(uint64_t) == 0, "k_detm_stage copies 8-byte words");
-  const int stage_words = (int)((al256(sizeof(DetBatch)) + (size_t)R * sizeof(DetDesc)) / sizeof(uint64_t));
-  const uint64_t* stage_src = (const uint64_t*)c->h_detm.dev();
-  DetOutHost* hout = (DetOutHost*)c->h_detm_out.get();
-  DetOutHost* dout = (DetOutHost*)c->h_detm_out.dev();
-  c->timing_now = c->timing > 0;
-  RET(launch(c, PFMPE_K_DETECT, [&] {
-    hipLaunchKernelGGL(k_detm_stage, dim3(1), dim3(kStageBlock), 0, c->stream, stage_src,
-                       (uint64_t*)(c->d_detm.get() + kDetmHead), stage_words, counters);
-    hipLaunchKernelGGL(k_detm_mask, dim3(n16), dim3(kDetTile * kDetTile), 0, c->stream, dhd, ddescs, c->d_img.get());
-    hipLaunchKernelGGL(k_detm_label, dim3(n32), dim3(kLabelBlock), 0, c->stream, dhd, ddescs);
-    hipLaunchKernelGGL(k_detm_merge, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs);
-    hipLaunchKernelGGL(k_detm_roots, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs, counters, work);
-    hipLaunchKernelGGL(k_detm_trace, dim3(512), dim3(64), 0, c->stream, ddescs, (const int*)counters,
-                       (const uint32_t*)work);
-    hipLaunchKernelGGL(k_detm_emit, dim3(R), dim3(kEmitBlock), 0, c->stream, ddescs, (const int*)counters, dout);
-  }));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->timing_now) RET(harvest_timing(c));
-  c->timing_now = false;
-  for (int r = 0; r < R; ++r) {
-    const DetOutHost& h = hout[r];
-    const int nw = std::min(std::min(h.n, max_out), kMaxBlobs);
-    if (nw > 0) {
-      std::memcpy(blobs + (size_t)r * 2 * max_out, h.und, 2 * (size_t)nw * sizeof(double));
-      if (distorted) std::memcpy(distorted + (size_t)r * 2 * max_out, h.dist, 2 * (size_t)nw * sizeof(float));
-    }
-    out[r].n = h.n;
-    out[r].n_components = h.n_components;
-    out[r].overflow = h.overflow;
-  }
+  pfmpe_detect_crop crops[PFMPE_DETECT_MAX_ROIS];
+  int64_t upload_bytes = 0;
+  if (const int rc = pfmpe_plan::build(images, image_of, prm, R, crops, &upload_bytes))
+    return fail(c0, rc, who + "the ROIs' pixels exceed the upload limit");
+  RET(set_device(c0));
+  // every member's work so far (the staging of its image, on its own stream) is ordered before the batch; a failure
+  // from here on gives the members their ordering state back (the leader's own was set by set_device)
+  OrderGuard members(ctxs.data(), (int)ctxs.size());
+  RET(members.order(1, c0->stream, c0));
+  RET(detm_run(
+      c0, R,
+      [&](int r, DetDesc& d) {
+        const pfmpe_detect_image& im = images[image_of[r]];
+        d.a = det_args(im.ctx, prm + r, im.width, im.height, im.pitch);
+        if (!im.image) {
+          d.pix = im.ctx->d_img.get() + (int64_t)d.a.ry * im.pitch + d.a.rx;
+          d.pix_pitch = im.pitch;
+        }
+      },
+      crops, upload_bytes, [&](uint8_t* p) { pfmpe_plan::pack(images, image_of, prm, R, crops, p, upload_bytes); },
+      blobs, distorted, max_out, out));
+  members.commit();  // nothing of the batch is pending: no member needs a fence
   return PFMPE_OK;
 }
 
