@@ -1,0 +1,181 @@
+// pf_cloud.hpp — read-backs of the cloud: the weights (pfmpe_get_weights) and the cloud statistics
+// (pfmpe_cloud_stats).
+#pragma once
+#include "pf_state.hpp"
+#include "pf_wave.hpp"
+
+namespace pfmpe {
+
+template <typename T>
+__global__ void k_weights_export(const T* __restrict__ w, double* __restrict__ out, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  out[n] = (double)w[n];
+}
+
+// ---- cloud statistics (pfmpe_cloud_stats; the definition is in include/pfmpe.h): weighted sums of the particles'
+// twists about a reference pose.  fp64 throughout, for every state type.
+// Twist xi = [upsilon; omega] of D = T * ref^-1 (left perturbation T = exp(xi) * ref), logarithmMap's order
+// (PE:2228-2296).  The stored matrices are used as they are (no re-orthonormalisation).  1 - cos(phi) is formed as
+// 2 sin^2(phi / 2): the same number without the cancellation at small phi.  A pose bit-equal to the reference has
+// twist exactly 0 (R R^T of a stored R is the identity only up to rounding).  Shared by the kernel and the host
+// helper (pfmpe_host_pose_twist), built with -ffp-contract=off on both sides.
+__host__ __device__ inline void pose_twist(const double* T, const double* ref, double* xi) {
+  bool same = true;
+#pragma unroll
+  for (int q = 0; q < 12; ++q) same = same && (T[q] == ref[q]);
+  double DR[9], d[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {  // D_R = R_i R_r^T
+      double s = T[i * 4 + 0] * ref[j * 4 + 0];
+      s = s + T[i * 4 + 1] * ref[j * 4 + 1];
+      s = s + T[i * 4 + 2] * ref[j * 4 + 2];
+      DR[i * 3 + j] = s;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {  // d = t_i - D_R t_r
+    double s = DR[i * 3 + 0] * ref[3];
+    s = s + DR[i * 3 + 1] * ref[7];
+    s = s + DR[i * 3 + 2] * ref[11];
+    d[i] = T[i * 4 + 3] - s;
+  }
+  const double a0 = 0.5 * (DR[7] - DR[5]), a1 = 0.5 * (DR[2] - DR[6]), a2 = 0.5 * (DR[3] - DR[1]);
+  const double s = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
+  const double c = 0.5 * (((DR[0] + DR[4]) + DR[8]) - 1.0);
+  const double phi = atan2(s, c);
+  const double f = s > 1e-8 ? phi / s : 1.0 + (s * s) / 6.0;
+  const double w0 = f * a0, w1 = f * a1, w2 = f * a2;
+  const double sh = sin(0.5 * phi), p2 = phi * phi;
+  const double k = phi >= 1e-4 ? (1.0 - (phi * sin(phi)) / (2.0 * ((2.0 * sh) * sh))) / p2 : 1.0 / 12.0 + p2 / 720.0;
+  // upsilon = (I - 1/2 w^ + k w^ w^) d
+  const double c10 = w1 * d[2] - w2 * d[1], c11 = w2 * d[0] - w0 * d[2], c12 = w0 * d[1] - w1 * d[0];
+  const double c20 = w1 * c12 - w2 * c11, c21 = w2 * c10 - w0 * c12, c22 = w0 * c11 - w1 * c10;
+  xi[0] = same ? 0.0 : (d[0] - 0.5 * c10) + k * c20;
+  xi[1] = same ? 0.0 : (d[1] - 0.5 * c11) + k * c21;
+  xi[2] = same ? 0.0 : (d[2] - 0.5 * c12) + k * c22;
+  xi[3] = same ? 0.0 : w0;
+  xi[4] = same ? 0.0 : w1;
+  xi[5] = same ? 0.0 : w2;
+}
+
+// One partial row per block, kCloudWords doubles: sum w, sum w^2, sum w xi (6), the upper triangle of sum w xi xi^T
+// (21, row by row), max |upsilon|^2 and max |omega|^2 over particles with w > 0, one unused word.
+constexpr int kCloudWords = 32;
+constexpr int kCloudSums = 29;
+// The grid is a function of N alone (one N, one reduction tree): a block per 256 particles up to 1024 blocks (two
+// rounds of the resident grid: 256 CUs x 2 blocks at the kernel's ~210 VGPRs), grid-stride beyond.
+constexpr int kCloudMaxBlocks = 1024;
+inline int cloud_blocks(int N) {
+  const int b = (N + kBlock - 1) / kBlock;
+  return b < kCloudMaxBlocks ? b : kCloudMaxBlocks;
+}
+struct CloudArgs {
+  double ref[12], anchor[12];
+  int32_t N, pad;
+  int64_t ld;
+  const uint32_t* owner;  // a deferred prior's owner indices (FrameArgsT::owner), or null
+  const double* dense;    // DENSE: N x 12 poses (the regenerated kept set)
+  const void* w;          // DENSE: its raw weights (compute type T)
+};
+// DENSE = false: the resident prior through StateIO / the owner indices, exactly the rows k_export writes, unit
+// weights.  DENSE = true: N x 12 doubles with weights widened as k_weights_export widens them.  Each lane sums its
+// particles in index order; one DPP reduction per wave after the stride loop; the block's waves are added in wave
+// order through LDS.  No atomics, no waits on other blocks: k_cloud_final is a second launch.
+template <typename T, typename SP, bool DENSE>
+__global__ __launch_bounds__(kBlock) void k_cloud_partials(const CloudArgs ca, const SP* __restrict__ st,
+                                                          double* __restrict__ part) {
+  __shared__ double sh[kWaves][kCloudWords];
+  double acc[kCloudSums];
+#pragma unroll
+  for (int q = 0; q < kCloudSums; ++q) acc[q] = 0.0;
+  double mt = 0.0, mr = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t n = (int64_t)blockIdx.x * kBlock + threadIdx.x; n < ca.N; n += stride) {
+    double P[12], w = 1.0;
+    if constexpr (DENSE) {
+#pragma unroll
+      for (int q = 0; q < 12; ++q) P[q] = ca.dense[12 * n + q];
+      w = (double)((const T*)ca.w)[n];
+    } else {
+      const int64_t r = ca.owner ? (int64_t)ca.owner[n] : n;
+#pragma unroll
+      for (int q = 0; q < 12; ++q)
+        P[q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ca.ld)], (T)ca.anchor[q]);
+    }
+    double xi[6], wx[6];
+    pose_twist(P, ca.ref, xi);
+    acc[0] = acc[0] + w;
+    acc[1] = acc[1] + w * w;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      wx[q] = w * xi[q];
+      acc[2 + q] = acc[2 + q] + wx[q];
+    }
+    int k = 8;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j, ++k) acc[k] = acc[k] + wx[i] * xi[j];
+    const double t2 = (xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2];
+    const double r2 = (xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5];
+    mt = (w > 0.0 && t2 > mt) ? t2 : mt;
+    mr = (w > 0.0 && r2 > mr) ? r2 : mr;
+  }
+#pragma unroll
+  for (int q = 0; q < kCloudSums; ++q) acc[q] = lane_value(wave_incl_sum(acc[q]), 63);
+  mt = wave_max(mt);
+  mr = wave_max(mr);
+  const int wv = wave_id();
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int q = 0; q < kCloudSums; ++q) sh[wv][q] = acc[q];
+    sh[wv][kCloudSums] = mt;
+    sh[wv][kCloudSums + 1] = mr;
+    sh[wv][kCloudSums + 2] = 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x < kCloudWords) {
+    const int q = threadIdx.x;
+    double v = sh[0][q];
+    for (int x = 1; x < kWaves; ++x) v = q < kCloudSums ? v + sh[x][q] : (sh[x][q] > v ? sh[x][q] : v);
+    part[(size_t)blockIdx.x * kCloudWords + q] = v;
+  }
+}
+// One block: word q of the result = the partial rows' word q combined in block order.  The rows are cut into
+// kCloudSegs runs of consecutive rows; 32 lanes per run add its rows in index order (16 loads in flight: one lane
+// walking all 1024 rows, a load's latency per row, took 50 us), then the runs are added in run order.  The tree
+// depends on nblk alone.  (0 is the identity of the sums and of the maxima, which are of squares.)
+constexpr int kCloudSegs = 8;
+template <typename V>  // (a template from when the header was in several TUs; its symbol is kept)
+__global__ __launch_bounds__(kCloudSegs* kCloudWords) void k_cloud_final(const V* __restrict__ part, int nblk,
+                                                                        V* __restrict__ out) {
+  __shared__ V sh[kCloudSegs][kCloudWords];
+  const int q = threadIdx.x % kCloudWords, sg = threadIdx.x / kCloudWords;
+  const int per = (nblk + kCloudSegs - 1) / kCloudSegs;
+  const int b0 = sg * per, b1 = b0 + per < nblk ? b0 + per : nblk;
+  const bool sum = q < kCloudSums;
+  V v = 0;
+  int b = b0;
+  for (; b + 16 <= b1; b += 16) {
+    V x[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x[i] = part[(size_t)(b + i) * kCloudWords + q];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v = sum ? v + x[i] : (x[i] > v ? x[i] : v);
+  }
+  for (; b < b1; ++b) {
+    const V x = part[(size_t)b * kCloudWords + q];
+    v = sum ? v + x : (x > v ? x : v);
+  }
+  sh[sg][q] = v;
+  __syncthreads();
+  if (sg == 0) {
+    for (int s = 1; s < kCloudSegs; ++s) v = sum ? v + sh[s][q] : (sh[s][q] > v ? sh[s][q] : v);
+    out[q] = v;
+  }
+}
+
+}  // namespace pfmpe

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define PF_TAG_HD __host__ __device__ __forceinline__
 #else
 #define PF_TAG_HD inline

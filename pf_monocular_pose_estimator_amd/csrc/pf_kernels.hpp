@@ -1,4 +1,6 @@
-// pf_kernels.hpp — HIP kernels of the PF step for gfx950 (MI355X, CDNA4, wave64).
+// pf_kernels.hpp — HIP kernels of the PF step for gfx950 (MI355X, CDNA4, wave64): the hand-off, the weighing
+// launches, resampling, the one-launch frames and the batched step.  Constants and records are in pf_types.hpp,
+// the helpers below them in pf_state.hpp, pf_wave.hpp and pf_likelihood.hpp; the side calls have their own headers.
 //
 // One frame (reference PE:475-733) is two launches:
 //
@@ -29,1430 +31,17 @@
 // block boundary is composed EXACTLY (max has no rounding) from group-local max-scans: the slot ranges
 // of all particles tile [0, N) with no gap and no overlap.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <float.h>
-#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <type_traits>
-#include <vector>
 
-#include <hip/hip_fp16.h>
-
-#include "pf_rng.hpp"
 #include "pf_desc_tag.hpp"
+#include "pf_likelihood.hpp"
 
 namespace pfmpe {
-
-constexpr int kBlock = 256;            // particles per block (4 waves)
-constexpr int kWaves = kBlock / 64;
-// Blocks per reduction group: ~sqrt(blocks), at most kGroup (one per lane of the group wave).  Arrival
-// counters are agent-scope atomics that execute at the memory side and serialise per address (~25 ns
-// each), so sqrt balances the group counters against the top counter (a single 391-way counter cost
-// ~10 us at C2).  A grid of one group skips the top counter: its group wave is the top wave.
-constexpr int kGroup = 64;
-constexpr int kMaxMarkers = 16;
-constexpr int kMaxBlobs = 1024;
-constexpr int kMaxBuckets = 512;       // x-buckets of the blob table (see bucket_count)
-constexpr int kMaxIter = 4096;         // PF iterations per frame (reference: 80); < 2^16 for k_frame's release tags
-constexpr int kPlanes = 12;            // r00 r01 r02 t0 r10 r11 r12 t1 r20 r21 r22 t2
-
-enum : int { kRngReference = 0, kRngPhilox = 1 };
-
-// Marker-count buckets (pfmpe_ctx.hpp dispatch_m / multi_m): the per-particle loops are unrolled to MAXM slots.
-// The 5-slot bucket serves exactly M == 5 (the README object: C1, C2, C4, C5), so its "slot j holds a marker"
-// tests are compile-time true: no per-marker lane masks live across the streaming loops (they held SGPR pairs
-// spilled to VGPR lanes, a v_readlane pair per use).  The other buckets test j < M.
-constexpr int kExactM = 5;
-template <int MAXM>
-__host__ __device__ __forceinline__ bool marker_live(int j, int M) {
-  return MAXM == kExactM ? j < kExactM : j < M;
-}
-
-// ----------------------------------------------------------------------------- kernel arguments
-// Passed by value (kernarg segment -> scalar loads), pre-converted to the compute type T on the host.
-// The frame's 2D blob grid as kernel arguments (scalar registers, reloadable from the kernarg segment /
-// stream descriptor instead of held in VGPRs): build_blob_table_host's GridHdr plus the byte offsets of the
-// grid's parts in the table; on = 0 when the table has no grid or one built for a narrower window.
-// one 2D-grid list entry of a blob table (build_blob_table_host): position and original index, one ds_read_b128
-struct alignas(16) GridEnt {
-  float x, y;
-  int32_t orig, pad;
-};
-struct GridArgs {
-  float inv_c, ox, oy, pad0;       // cell of (u, v): (fma(u, inv_c, ox), fma(v, inv_c, oy)), clamped, truncated;
-                                   // ox = -gx0 * inv_c (square cells)
-  float fmaxx, fmaxy;              // ncx - 1, ncy - 1
-  int32_t ncx4, on;               // 4 * ncx: the cell row pitch in bytes
-  int32_t cell_off, ent_off;      // table offsets: uint32 cell[], GridEnt ent[]
-  int32_t b0fin;                  // blob 0 of the table is finite (set whether or not the grid is on)
-  int32_t pad2;
-};
-
-template <typename T>
-struct FrameArgsT {
-  T cur[12], pred[12], predm[12], cam[12];  // 3x4 row-major
-  T markers[kMaxMarkers * 3];
-  T K[9];
-  T lo[6], hi[6];           // draw ranges angX angY angZ tX tY tZ (scaled by fac*), Philox stream
-  T rgs[6];                 // (hi - lo) * 2^-21: hi - lo rounded once on the host, then scaled exactly (Philox draw
-                            // lo + u21 * (hi - lo) with u21 = v * 2^-21, computed as v * rgs: the same product)
-  double dlo[6], dhi[6];    // the same in double, reference stream (draws are computed in double)
-  double growth;            // 0.025
-  T tol, tol_pf, tolq;      // score normaliser / acceptance gate / pruning half-window
-  double exit_thr, accept_thr;
-  uint32_t key0, key1, flo, fhi;  // philox key / frame counter
-  uint32_t lcg_x0;                // reference engine state after seeding
-  uint32_t downgrade;             // bit j: marker j downgraded
-  int32_t N, M, B, it;            // particles, markers, blobs, it_since_initialized_
-  int32_t cam_identity, max_iter, force_iters, nblk;
-  int32_t ngrp, gsz;              // reduction groups and blocks per group (~sqrt(nblk), <= kGroup)
-  int32_t diag;                   // diagnostic switches (0 in production; pfmpe_ctx.hpp kDiag*)
-  int32_t small_angles;           // every angle draw of the frame has |x| <= kSmallAngle (host bound, fp32)
-  int32_t k_upper;                // K = [k0 k1 k2; 0 k4 k5; 0 0 1] (host check; fp32 skips the zero terms)
-  uint32_t wait_ticks;            // bound of every in-launch wait, s_memrealtime ticks (100 MHz)
-  uint32_t flat_base_w, flat_base_c;  // k_frame2: running totals of the flat counter sets at frame start
-  int32_t tbytes;                 // this frame's blob table, bytes (base + grid: build_blob_table_host)
-  uint32_t gtag;                  // k_frame2: this frame's granule tag base (frame << 12; the iteration in the low
-                                  // 12 bits), never 0 (pfmpe_ctx.hpp next_gtag)
-  GridArgs grid;                  // the table's 2D grid (fp32 pruned column minima)
-  int64_t ld;                     // SoA plane stride in elements
-  T anc_in[12], anc_out[12];      // fp16 state only: anchors of the prior / of the new prior
-  // Deferred resampling: the prior may be stored as an earlier frame's kept propagated set plus
-  // owner indices, prior particle n = stored particle owner[n] (null: stored in particle order).  owner_out
-  // (two-launch frames with the kept set): k_resample writes the new prior's owner indices there instead of
-  // gathering and scattering the particles (null: the new prior is materialised in the post buffer).
-  const uint32_t* owner;
-  uint32_t* owner_out;
-};
-
-// The frame-constant arrays, staged once per block into LDS and read from there (broadcast reads):
-// kept in SGPRs they would spill into VGPR lanes and cap residency (MI355X_MICROARCH.md "Residency").
-template <typename T>
-struct LdsConst {
-  T cur[12], pred[12], predm[12], cam[12];
-  T markers[kMaxMarkers * 3];
-  T K[9];
-  T lo[6], hi[6];
-  T rgs[6];
-};
-
-// Per-frame control record.  All-zero is the valid "start of frame" state (zeroed at create, set_prior
-// and by the final wave of every frame).
-struct Ctrl {
-  double best_max;   // highestProb
-  double S;          // probPartSum of the kept iteration
-  double invS;       // fl(1 / S): k_resample's divisions by S as a product and two fma corrections (div_by_S)
-  int32_t done, has_best, best_idx, best_iter, best_slot, cur_slot;
-  int32_t iters, kept_slot, kept_iter, accepted, most_likely_idx, pad0;
-  int64_t K_total;   // number of stratified targets that find a particle
-};
-
-// per block, per weight slot (written and read write-through)
-struct alignas(16) BlockPart {
-  double sum;             // block total (in-block scan order)
-  double maxrel, minrel;  // extrema of the in-block inclusive prefix sums
-  double maxw, minw;      // max / min weight
-  int32_t argmax, argmin;
-};
-// per group, per weight slot (write-through)
-struct alignas(16) GroupPart {
-  double sum;          // group total
-  double zmax, zmin;   // max / min over the group of fl(E_b + incl_i)
-  double maxw, minw;
-  int32_t argmax, argmin;
-};
-// per block, per weight slot: in-group exclusive prefix E_b and exclusive max/min of z (for k_resample)
-struct alignas(16) BlockScan {
-  double E, zin_max, zin_min, pad;
-};
-// per group, kept slot only: group prefix G_g and running max of c at the group start
-struct alignas(16) GroupScan {
-  double G, Gin;
-};
-struct alignas(8) CountPart {
-  int32_t maxcount, idx;
-};
-// winner keys of the one-stream two-launch frame (k_resample -> k_resample_final): unsigned max of
-// count << 32 | (2^31 - 1 - index) is the max count at its lowest index; 0 (count 0 at no index) is the identity
-constexpr int kWinShards = 64;
-constexpr int kWinStride = 16;  // keys one 128-B line apart: ~39k block atomics at C4 spread over 64 lines
-// the key area: the key shards, then as many arrival shards of the fused finish (k_resample_owners), each counter at
-// the start of its own 128-B line (one memory-side atomic unit serialises ~25 ns per arrival on one address: one
-// counter for C4's 39k blocks took 400 us)
-constexpr size_t kWinBytes = (size_t)(2 * kWinShards) * kWinStride * sizeof(unsigned long long);
-__host__ __device__ __forceinline__ uint32_t* win_arrive(unsigned long long* winkey) {
-  return (uint32_t*)(winkey + kWinShards * kWinStride);
-}
-constexpr int kArriveStride = 2 * kWinStride;  // uint32 words between arrival shards (128 B)
-__host__ __device__ __forceinline__ unsigned long long win_key(int count, int idx) {
-  return ((unsigned long long)(uint32_t)count << 32) | (uint32_t)(0x7fffffff - idx);
-}
-
-// frame record written by the final wave into pinned host memory: the pfmpe_frame_out layout, then the
-// kept slot and the publication tag (2 * frame sequence + finished)
-struct OutDev {
-  int32_t iters, kept_iter, most_likely_idx, accepted, resampled, winner_idx, n_corr, flag_fail;
-  double highest_prob, prob_sum;
-  double winner_pose[12], most_likely_pose[12];
-  uint32_t corr[2 * kMaxMarkers];
-  int32_t kept_slot;
-  int32_t tag;
-};
-// The record as the kernel publishes it: data-tagged granules (MI355X_MICROARCH.md "handoff-1to1"), 8-byte
-// words {OutDev word k (low 32 bits), tag (high 32)}, each ONE relaxed system-scope store, so the host has
-// the whole record once every granule carries the current tag, and the final wave needs no release (no
-// wait for the PCIe write acknowledgements).  An unfinished iteration batch (two-launch path) writes
-// granule 0 alone, with tag 2 * seq.
-constexpr int kRecWords = (int)(offsetof(OutDev, tag) / 4);
-constexpr int kRecGran = 128;
-static_assert(offsetof(OutDev, tag) % 4 == 0 && kRecWords <= kRecGran && kRecWords > 64, "record granules");
-struct RecOut {
-  uint64_t g[kRecGran];
-};
-
-// ----------------------------------------------------------------------------- scalar helpers
-__host__ __device__ __forceinline__ float fmadd(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-// fp64: deliberately UNFUSED (TU built with -ffp-contract=off): a*b rounded, then +c rounded, the
-// reference's x86-64 arithmetic.
-__host__ __device__ __forceinline__ double fmadd(double a, double b, double c) { return a * b + c; }
-// fp32: the motion noise angles are tiny (|x| <= 0.015 * 1.x rad with README parameters), so a short
-// Taylor polynomial is accurate to float rounding there; larger angles take sincosf.
-__device__ __forceinline__ void sincos_t(float x, float* s, float* c) {
-  if (fabsf(x) <= 0.25f) {
-    const float x2 = x * x;
-    *s = x * fmadd(x2, fmadd(x2, fmadd(x2, fmadd(x2, 1.0f / 362880.0f, -1.0f / 5040.0f), 1.0f / 120.0f),
-                             -1.0f / 6.0f), 1.0f);
-    *c = fmadd(x2, fmadd(x2, fmadd(x2, fmadd(x2, 1.0f / 40320.0f, -1.0f / 720.0f), 1.0f / 24.0f), -0.5f), 1.0f);
-  } else {
-    sincosf(x, s, c);
-  }
-}
-// |x| <= kSmallAngle (the host proves it for every angle draw of a frame: FrameArgsT::small_angles): the
-// next Taylor terms are below half an fp32 ulp there (x^5/120 / x <= 6.8e-9, x^6/720 <= 1e-12)
-constexpr float kSmallAngle = 0.03f;
-__device__ __forceinline__ void sincos_small(float x, float* s, float* c) {
-  const float x2 = x * x;
-  *s = x * fmadd(x2, -1.0f / 6.0f, 1.0f);
-  *c = fmadd(x2, fmadd(x2, 1.0f / 24.0f, -0.5f), 1.0f);
-}
-__device__ __forceinline__ void sincos_t(double x, double* s, double* c) {
-  *s = sin(x);
-  *c = cos(x);
-}
-__device__ __forceinline__ void sincos_small(double x, double* s, double* c) { sincos_t(x, s, c); }  // fp64: exact path
-// fp32: the hardware square root (v_sqrt_f32, 1 ulp) instead of sqrtf's correctly rounded 14-instruction
-// sequence (tolerance path, like div_t); fp64 stays IEEE
-// max / min for the wave extrema (operands are never NaN: weights are finite, identities are +-inf)
-__device__ __forceinline__ float fmax_t(float a, float b) { return __builtin_fmaxf(a, b); }
-__device__ __forceinline__ double fmax_t(double a, double b) { return __builtin_fmax(a, b); }
-__device__ __forceinline__ float fmin_t(float a, float b) { return __builtin_fminf(a, b); }
-__device__ __forceinline__ double fmin_t(double a, double b) { return __builtin_fmin(a, b); }
-__device__ __forceinline__ float sqrt_t(float x) { return __builtin_amdgcn_sqrtf(x); }
-__device__ __forceinline__ double sqrt_t(double x) { return sqrt(x); }
-// fp32 quotient a/b through the hardware reciprocal (v_rcp_f32, 1 ulp): one instruction instead of the
-// ~10-instruction IEEE division sequence; the fp32 path is a tolerance path, fp64 divides
-// exactly
-__device__ __forceinline__ float rcp_t(float b) { return __builtin_amdgcn_rcpf(b); }
-__device__ __forceinline__ float div_t(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-__device__ __forceinline__ double div_t(double a, double b) { return a / b; }
-// perspective division: fp32 uses one hardware reciprocal, fp64 the exact IEEE quotient (PE:1032)
-__device__ __forceinline__ void persp(float p0, float p1, float p2, float* u, float* v) {
-  const float r = rcp_t(p2);
-  *u = p0 * r;
-  *v = p1 * r;
-}
-__device__ __forceinline__ void persp(double p0, double p1, double p2, double* u, double* v) {
-  *u = p0 / p2;
-  *v = p1 / p2;
-}
-template <typename T>
-__device__ __forceinline__ T inf_t() {
-  return (T)INFINITY;
-}
-
-// The frame-constant arrays lead FrameArgsT in exactly LdsConst's layout, and FrameArgsT is every
-// kernel's first argument, so the block copies them from the kernarg segment with one vector load per
-// lane (no SGPR round trip: kept in SGPRs they spill into VGPR lanes).  Callers barrier afterwards.
-template <typename T>
-__device__ __forceinline__ void stage_consts_from(const uint32_t* src, LdsConst<T>& sc) {
-  static_assert(offsetof(FrameArgsT<T>, cur) == 0 && offsetof(FrameArgsT<T>, hi) == offsetof(LdsConst<T>, hi) &&
-                    offsetof(FrameArgsT<T>, rgs) == offsetof(LdsConst<T>, rgs),
-                "LdsConst must mirror the head of FrameArgsT");
-  static_assert(sizeof(LdsConst<T>) % 4 == 0, "dword copy");
-  uint32_t* dst = (uint32_t*)&sc;
-  constexpr int kWordsC = (int)(sizeof(LdsConst<T>) / 4);
-  for (int i = threadIdx.x; i < kWordsC; i += kBlock) dst[i] = src[i];
-}
-template <typename T>
-__device__ __forceinline__ void stage_consts(const FrameArgsT<T>& fa, LdsConst<T>& sc) {
-  (void)fa;
-  stage_consts_from<T>((const uint32_t*)__builtin_amdgcn_kernarg_segment_ptr(), sc);
-}
-
-// ----------------------------------------------------------------------------- pose algebra
-// 3x4 affine compose C = A*B with the reference's full-4x4 summation order (k = 0..3 sequential; the
-// zero bottom-row terms add +0 and are skipped without changing any non-zero value).
-template <typename T>
-__host__ __device__ __forceinline__ void compose(const T* A, const T* B, T* C) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      T s = A[i * 4 + 0] * B[0 * 4 + j];
-      s = fmadd(A[i * 4 + 1], B[1 * 4 + j], s);
-      s = fmadd(A[i * 4 + 2], B[2 * 4 + j], s);
-      if (j == 3) s = s + A[i * 4 + 3];
-      C[i * 4 + j] = s;
-    }
-  }
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));  // packed fp32 pairs (v_pk_* forms)
-
-// Particle state storage S for compute type T: S == T (fp32 / fp64 planes), or fp16 planes holding
-// deltas to the set's anchor pose (PFMPE_STATE_F16, fp32 compute): 24 B per particle.
-template <typename T, typename SP>
-struct StateIO {
-  static __host__ __device__ __forceinline__ T load(SP v, T) { return (T)v; }
-  static __host__ __device__ __forceinline__ SP store(T v, T) { return (SP)v; }
-};
-template <>
-struct StateIO<float, __half> {
-  static __device__ __forceinline__ float load(__half v, float anchor) { return __half2float(v) + anchor; }
-  static __device__ __forceinline__ __half store(float v, float anchor) { return __float2half(v - anchor); }
-};
-
-// SoA plane access through a buffer resource (cdna_hip_programming.md T8) for the fp32 / fp16 planes: every
-// plane of particle n is at byte n*sizeof(SP) (one 32-bit VGPR offset shared by all 12 planes) plus the
-// wave-uniform plane offset q*ld*sizeof(SP) in the SGPR soffset, so no plane costs a 64-bit VALU address
-// (a flat access costs two v_mad_u64_u32 and moves per plane).  The resource covers the 12 planes
-// (pfmpe_create caps 12*ld*sizeof(SP) below 4 GiB).  fp64 (the parity mode) keeps flat accesses.
-template <typename SP>
-struct BufPlanes : std::false_type {};
-template <>
-struct BufPlanes<float> : std::true_type {};
-template <>
-struct BufPlanes<__half> : std::true_type {};
-
-template <typename SP>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const SP* base, int64_t ld) {
-  const uint32_t bytes = (uint32_t)(12 * ld * (int64_t)sizeof(SP));
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
-}
-template <typename SP, int POL = 0>
-__device__ __forceinline__ SP buf_ld(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-  if constexpr (std::is_same<SP, float>::value)
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, POL));
-  else
-    return __ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, POL));
-}
-// cache policy of a vector memory access: 16 = sc1 (a store writes through and drops the line from the XCD's L2)
-constexpr int kPolSc1 = 16;
-template <int POL = 0>
-__device__ __forceinline__ void buf_st(float v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, POL);
-}
-template <int POL = 0>
-__device__ __forceinline__ void buf_st(__half v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-  __builtin_amdgcn_raw_buffer_store_b16(__half_as_ushort(v), r, voff, soff, POL);
-}
-
-// fp16 state layout (PFMPE_F16_PAIRS, default 1): planes 2j and 2j + 1 interleaved as ONE plane of 32-bit pairs,
-// element (q, n) at half index (q >> 1) * 2 ld + 2 n + (q & 1).  Every fp16 state access is then a 4-byte
-// access per lane (6 instead of 12 VMEM instructions per particle, 256 B per wave instruction), and the pair is
-// the register layout the kernels already use (RawState<__half>, store_state_words_f16).  0 keeps 12 planes of
-// halves (A/B).  fp32 / fp64 planes are unchanged.
-// fp32 state keeps 12 plain planes.  Round 3 also tried 6 planes of 64-bit pairs (PFMPE_F32_PAIRS): -2 us on C5's
-// k_resample, +1..5 us on C3's weighing; round 4 removed it: deferred resampling (k_resample writes owner indices,
-// no state planes) took away the only kernel it helped.
-#ifndef PFMPE_F16_PAIRS
-#define PFMPE_F16_PAIRS 1
-#endif
-template <typename SP>
-__host__ __device__ __forceinline__ constexpr bool f16_pairs() {
-  return std::is_same<SP, __half>::value && PFMPE_F16_PAIRS != 0;
-}
-template <typename SP>
-__host__ __device__ __forceinline__ int64_t plane_index(int q, int64_t n, int64_t ld) {
-  if constexpr (f16_pairs<SP>())
-    return (int64_t)(q >> 1) * 2 * ld + 2 * n + (q & 1);
-  else
-    return (int64_t)q * ld + n;
-}
-
-// the 12 state values of particle n of a state buffer (raw SP values, no anchor / conversion).  POL kPolSc1: the
-// loads bypass L1
-template <typename SP, int POL = 0>
-__device__ __forceinline__ void load_state_raw(const SP* __restrict__ base, int64_t ld, int n, SP* v) {
-  if constexpr (f16_pairs<SP>()) {
-    const __amdgpu_buffer_rsrc_t r = plane_rsrc(base, ld);
-    const uint32_t pps = (uint32_t)(ld * 4);
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-      const uint32_t w = __builtin_amdgcn_raw_buffer_load_b32(r, (uint32_t)n * 4u, (uint32_t)p * pps, POL);
-      v[2 * p] = __ushort_as_half((unsigned short)(w & 0xffffu));
-      v[2 * p + 1] = __ushort_as_half((unsigned short)(w >> 16));
-    }
-  } else if constexpr (BufPlanes<SP>::value) {
-    const __amdgpu_buffer_rsrc_t r = plane_rsrc(base, ld);
-    const uint32_t ps = (uint32_t)(ld * (int64_t)sizeof(SP));
-#pragma unroll
-    for (int q = 0; q < 12; ++q) v[q] = buf_ld<SP, POL>(r, (uint32_t)n * (uint32_t)sizeof(SP), (uint32_t)q * ps);
-  } else if constexpr (POL != 0) {
-#pragma unroll
-    for (int q = 0; q < 12; ++q)
-      v[q] = __hip_atomic_load((const __attribute__((address_space(1))) SP*)(base + (int64_t)q * ld + n),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-#pragma unroll
-    for (int q = 0; q < 12; ++q) v[q] = base[(int64_t)q * ld + n];
-  }
-}
-// store 12 raw state values as particle k
-template <typename SP>
-__device__ __forceinline__ void store_state_raw(SP* __restrict__ base, int64_t ld, int k, const SP* v) {
-  constexpr int pol = 0;
-  if constexpr (f16_pairs<SP>()) {
-    const __amdgpu_buffer_rsrc_t r = plane_rsrc((const SP*)base, ld);
-    const uint32_t pps = (uint32_t)(ld * 4);
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-      const uint32_t w = (uint32_t)__half_as_ushort(v[2 * p]) | ((uint32_t)__half_as_ushort(v[2 * p + 1]) << 16);
-      __builtin_amdgcn_raw_buffer_store_b32(w, r, (uint32_t)k * 4u, (uint32_t)p * pps, pol);
-    }
-  } else if constexpr (BufPlanes<SP>::value) {
-    const __amdgpu_buffer_rsrc_t r = plane_rsrc((const SP*)base, ld);
-    const uint32_t ps = (uint32_t)(ld * (int64_t)sizeof(SP));
-#pragma unroll
-    for (int q = 0; q < 12; ++q) buf_st<pol>(v[q], r, (uint32_t)k * (uint32_t)sizeof(SP), (uint32_t)q * ps);
-  } else {
-#pragma unroll
-    for (int q = 0; q < 12; ++q) base[(int64_t)q * ld + k] = v[q];
-  }
-}
-
-// fp16 planes, particle k from six words holding planes (2j, 2j + 1) in their (low, high) halves: the high half
-// goes out through buffer_store_short_d16_hi, so no word is shifted first (the compiler does not select the
-// _d16_hi form for a store of x >> 16).  A vector store; the "memory" clobber keeps it ordered with the
-// compiler's own memory operations, and it carries its own VALU-SGPR-write -> VMEM wait states (below).
-__device__ __forceinline__ void store_state_words_f16(__half* __restrict__ base, int64_t ld, int k, const uint32_t* w) {
-  const __amdgpu_buffer_rsrc_t r = plane_rsrc((const __half*)base, ld);
-  if constexpr (f16_pairs<__half>()) {  // the words are the layout: one dword store each
-    const uint32_t pps = (uint32_t)(ld * 4);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) __builtin_amdgcn_raw_buffer_store_b32(w[j], r, (uint32_t)k * 4u, (uint32_t)j * pps, 0);
-    return;
-  }
-  const uint32_t ps = (uint32_t)(ld * (int64_t)sizeof(__half));
-  const uint32_t voff = (uint32_t)k * 2u;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)w[j], r, voff, (uint32_t)(2 * j) * ps, 0);
-    // s_nop 4 first: the compiler's hazard recognizer does not look inside inline asm, and the soffset /
-    // resource SGPRs may have just been written by a VALU (v_readlane of a spilled SGPR), which a VMEM
-    // instruction may read only 5 wait states later; without it the store used the stale offset
-    asm volatile("s_nop 4\n\tbuffer_store_short_d16_hi %0, %1, %2, %3 offen" ::"v"(w[j]), "v"(voff), "s"(r),
-                 "s"((uint32_t)(2 * j + 1) * ps)
-                 : "memory");
-  }
-}
-
-// Prefetch form (k_weigh_stream): the 12 raw plane words of particle n as 32-bit registers (fp16 values
-// zero-extended), loaded by every lane without a branch.  The caller clamps the particle index into [0, N) for
-// lanes past N (in_planes): the buffer resource's range check covers the VGPR offset only, not the plane offset
-// in soffset, so an unclamped lane past ld read past the end of the allocation (up to a plane beyond it for the
-// streaming pass's last prefetch); the loaded values of such lanes are never used.  Raw halves kept as halves were packed in pairs by the compiler right after the loads
-// (v_perm), which waited for the prefetch at once; a branch around the loads made the next wait vmcnt(0).
-// fp64 planes (flat accesses) keep the guarded load.
-// fp16 planes: planes 2k and 2k + 1 share one register: one dword load from the pair plane (PFMPE_F16_PAIRS),
-// or buffer_load_short_d16 / _d16_hi into its two halves (12 half planes), so the pair needs no packing.
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-template <typename SP>
-struct RawState {
-  SP v[12];
-};
-template <>
-struct RawState<__half> {
-  u16x2 p[6];
-};
-template <>
-struct RawState<float> {
-  uint32_t v[12];
-};
-// a particle index every plane access may use: n for n < N, else N - 1 (one v_min; see load_state_prefetch)
-__device__ __forceinline__ int in_planes(int n, int N) { return (int)min((unsigned)n, (unsigned)(N - 1)); }
-template <typename SP>
-__device__ __forceinline__ void load_state_prefetch(const SP* __restrict__ base, int64_t ld, int n, bool want,
-                                                    RawState<SP>& R) {
-  if constexpr (BufPlanes<SP>::value) {
-    const __amdgpu_buffer_rsrc_t r = plane_rsrc(base, ld);
-    const uint32_t ps = (uint32_t)(ld * (int64_t)sizeof(SP));
-    if constexpr (f16_pairs<SP>()) {  // one dword per pair plane
-#pragma unroll
-      for (int k = 0; k < 6; ++k)
-        R.p[k] = __builtin_bit_cast(u16x2, __builtin_amdgcn_raw_buffer_load_b32(r, (uint32_t)n * 4u, (uint32_t)k * (uint32_t)(ld * 4), 0));
-    } else if constexpr (sizeof(SP) == 2) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        u16x2 x = R.p[k];
-        x.x = __builtin_amdgcn_raw_buffer_load_b16(r, (uint32_t)n * 2u, (uint32_t)(2 * k) * ps, 0);
-        x.y = __builtin_amdgcn_raw_buffer_load_b16(r, (uint32_t)n * 2u, (uint32_t)(2 * k + 1) * ps, 0);
-        R.p[k] = x;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 12; ++q) R.v[q] = __builtin_amdgcn_raw_buffer_load_b32(r, (uint32_t)n * 4u, (uint32_t)q * ps, 0);
-    }
-  } else {
-    if (want) load_state_raw<SP>(base, ld, n, R.v);
-  }
-}
-// StateIO::load of prefetched plane q
-template <typename T, typename SP>
-__device__ __forceinline__ T state_from_raw(const RawState<SP>& R, int q, T anchor) {
-  if constexpr (std::is_same<SP, __half>::value)
-    return StateIO<T, SP>::load(__ushort_as_half((q & 1) ? R.p[q >> 1].y : R.p[q >> 1].x), anchor);
-  else if constexpr (std::is_same<SP, float>::value)
-    return StateIO<T, SP>::load(__uint_as_float(R.v[q]), anchor);
-  else
-    return StateIO<T, SP>::load(R.v[q], anchor);
-}
-
-// prior particle n (SoA planes), loaded ahead of use so the loads overlap other work
-// the stored row of prior particle n (deferred prior: its owner index)
-template <typename T>
-__device__ __forceinline__ int prior_row(const FrameArgsT<T>& fa, int n) {
-  return fa.owner ? (int)fa.owner[n] : n;
-}
-template <typename T, typename SP, int POL = 0>
-__device__ __forceinline__ void load_prior(const FrameArgsT<T>& fa, const SP* __restrict__ prior, int n, T* A) {
-  SP v[12];
-  load_state_raw<SP, POL>(prior, fa.ld, prior_row(fa, n), v);
-#pragma unroll
-  for (int q = 0; q < 12; ++q) A[q] = StateIO<T, SP>::load(v[q], fa.anc_in[q]);
-}
-// particle k of a state buffer from its pose P (quantised against the anchor `anc` for fp16 state)
-template <typename T, typename SP>
-__device__ __forceinline__ void store_pose(SP* __restrict__ dst, int64_t ld, int k, const T* P, const T* anc) {
-  if constexpr (std::is_same<SP, __half>::value && std::is_same<T, float>::value) {
-    // fp16 deltas two planes at a time: one v_pk_add_f32 (the same fp32 subtractions) and one v_cvt_pk_f16_f32
-    // (round to nearest even, as __float2half) per pair, then the pair's halves as planes 2j / 2j + 1
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-    uint32_t w[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const f32x2 d = f32x2{P[2 * j], P[2 * j + 1]} - f32x2{anc[2 * j], anc[2 * j + 1]};
-      w[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(d, f16x2));
-    }
-    store_state_words_f16(dst, ld, k, w);
-    return;
-  }
-  SP v[12];
-#pragma unroll
-  for (int q = 0; q < 12; ++q) v[q] = StateIO<T, SP>::store(P[q], anc[q]);
-  store_state_raw<SP>(dst, ld, k, v);
-}
-
-// The motion model (PE:543-588) for particle n in PF iteration `iter` from its prior pose A (loaded by
-// load_prior; unused for n < 2); P receives the 3x4 pose.
-template <typename T>
-__device__ __forceinline__ T u21_t(uint32_t v);
-template <>
-__device__ __forceinline__ float u21_t<float>(uint32_t v) { return u21f(v); }
-template <>
-__device__ __forceinline__ double u21_t<double>(uint32_t v) { return u21d(v); }
-
-template <typename T, int RNG>
-__device__ __forceinline__ void propagate(const FrameArgsT<T>& fa, const LdsConst<T>& sc, const T* A_in, int n,
-                                          int iter, T* P) {
-  if (n == 0) {  // current_pose_ (PE:547)
-#pragma unroll
-    for (int q = 0; q < 12; ++q) P[q] = sc.cur[q];
-    return;
-  }
-  if (n == 1) {  // predicted_pose_ (PE:551)
-#pragma unroll
-    for (int q = 0; q < 12; ++q) P[q] = sc.pred[q];
-    return;
-  }
-  T A[12];
-#pragma unroll
-  for (int q = 0; q < 12; ++q) A[q] = A_in[q];
-  if (fa.it > 1) {
-    if (!fa.cam_identity) {  // camMoveInv * prior (PE:556-558)
-      T X[12];
-      compose(sc.cam, A, X);
-#pragma unroll
-      for (int q = 0; q < 12; ++q) A[q] = X[q];
-    }
-    if ((iter % 10) != 0) {  // ... * predictionMatrix (PE:556)
-      T X[12];
-      compose(A, sc.predm, X);
-#pragma unroll
-      for (int q = 0; q < 12; ++q) A[q] = X[q];
-    }
-  }
-  // draws in reference order: angX, angY, angZ, tX, tY, tZ (PE:563-587)
-  const double gd = 1.0 + fa.growth * (double)(iter / 10);
-  T d[6];
-  if (RNG == kRngReference) {
-    const uint64_t before = 12u * ((uint64_t)(fa.N - 2) * (uint64_t)iter + (uint64_t)(n - 2));
-    uint32_t g = lcg_output(fa.lcg_x0, before + 1u);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      const uint32_t g1 = g;
-      const uint32_t g2 = lcg_next(g1);
-      g = lcg_next(g2);
-      d[q] = (T)(ref_uniform(ref_canonical(g1, g2), fa.dlo[q], fa.dhi[q]) * gd);
-    }
-  } else {
-    const Draws6 r = philox_motion6((uint32_t)n, (uint32_t)iter, fa.flo, fa.fhi, fa.key0, fa.key1);
-    // draw = u21 * (hi - lo) + lo, u21 = v * 2^-21 (exact): v * rgs is the same product rounded once, so the
-    // conversion's scaling multiply is folded into the host constant
-#pragma unroll
-    for (int q = 0; q < 6; ++q) d[q] = (T)r.v[q] * sc.rgs[q] + sc.lo[q];
-    if (iter >= 10) {  // wave-uniform: the growth factor 1 + growth * (iter / 10) is exactly 1 before iteration 10
-      // (the empty asm keeps this a scalar branch: if-converted, every frame paid the six products and six
-      // v_cndmask selects)
-      asm volatile("");
-      const T g = (T)gd;
-#pragma unroll
-      for (int q = 0; q < 6; ++q) d[q] = d[q] * g;
-    }
-  }
-  T sa, ca, sb, cb, sz, cz;
-  if (fa.small_angles) {  // wave-uniform (fp32 only: the host never sets it for fp64)
-    sincos_small(d[0], &sa, &ca);
-    sincos_small(d[1], &sb, &cb);
-    sincos_small(d[2], &sz, &cz);
-  } else {
-    sincos_t(d[0], &sa, &ca);
-    sincos_t(d[1], &sb, &cb);
-    sincos_t(d[2], &sz, &cz);
-  }
-  // R = ((R_A * Rz(c)) * Ry(b)) * Rx(a)   (PE:582)
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const T a0 = A[i * 4 + 0], a1 = A[i * 4 + 1], a2 = A[i * 4 + 2];
-    const T z0 = fmadd(a1, sz, a0 * cz);      // A*Rz col 0
-    const T z1 = fmadd(a1, cz, a0 * (-sz));   // A*Rz col 1
-    const T y0 = fmadd(a2, (-sb), z0 * cb);   // *Ry col 0
-    const T y2 = fmadd(a2, cb, z0 * sb);      // *Ry col 2
-    const T x1 = fmadd(y2, sa, z1 * ca);      // *Rx col 1
-    const T x2 = fmadd(y2, ca, z1 * (-sa));   // *Rx col 2
-    P[i * 4 + 0] = y0;
-    P[i * 4 + 1] = x1;
-    P[i * 4 + 2] = x2;
-    P[i * 4 + 3] = A[i * 4 + 3] + d[3 + i];   // translation added unrotated (PE:585-587)
-  }
-}
-
-template <typename T, int RNG, typename SP>
-__device__ __forceinline__ void make_particle(const FrameArgsT<T>& fa, const LdsConst<T>& sc,
-                                              const SP* __restrict__ prior, int n, int iter, T* P) {
-  T A[12];
-  if (n >= 2) load_prior(fa, prior, n, A);
-  propagate<T, RNG>(fa, sc, A, n, iter, P);
-}
-
-// Q = K * P (3x4).  fp32 with an upper-triangular K whose last row is (0 0 1) (every pinhole CameraInfo,
-// README.md:95-143; the host checks, FrameArgsT::k_upper): the zero terms are skipped, 16 instead of 36
-// operations.  A skipped term is an exact +-0 added before the first rounding, so the sums are the same
-// except for the sign of an exact zero.  fp64 (the parity mode) keeps the literal form.
-// fp32 pairs for the packed VALU forms (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: two fp32 operations per
-// instruction).  Each lane of a pair sees exactly the scalar operation sequence (mul, fma, add rounded the
-// same way; the TUs are built with -ffp-contract=off, so nothing else fuses), so packed and scalar forms
-// give the same bits.
-// a * b + c for 0 <= a, b < 2^24: one full-rate v_mad_u32_u24 (v_mul_lo_u32 is quarter rate)
-__device__ __forceinline__ int mad24(int a, int b, int c) {
-  return (int)(((unsigned)a & 0xffffffu) * ((unsigned)b & 0xffffffu)) + c;
-}
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x2 pk2(float a, float b) { return f32x2{a, b}; }
-
-template <typename T>
-__device__ __forceinline__ void k_times_pose(const LdsConst<T>& sc, const T* P, bool k_upper, T* Q) {
-  if (std::is_same<T, float>::value && k_upper) {
-#pragma unroll
-    for (int j = 0; j < 4; j += 2) {  // columns j, j + 1 as one pair
-      const f32x2 p0 = pk2(P[0 * 4 + j], P[0 * 4 + j + 1]);
-      const f32x2 p1 = pk2(P[1 * 4 + j], P[1 * 4 + j + 1]);
-      const f32x2 p2 = pk2(P[2 * 4 + j], P[2 * 4 + j + 1]);
-      f32x2 s = p0 * sc.K[0];
-      s = pk_fma(pk2(sc.K[1], sc.K[1]), p1, s);
-      s = pk_fma(pk2(sc.K[2], sc.K[2]), p2, s);
-      const f32x2 s1 = pk_fma(pk2(sc.K[5], sc.K[5]), p2, p1 * sc.K[4]);
-      Q[0 * 4 + j] = s.x;
-      Q[0 * 4 + j + 1] = s.y;
-      Q[1 * 4 + j] = s1.x;
-      Q[1 * 4 + j + 1] = s1.y;
-      Q[2 * 4 + j] = P[2 * 4 + j];
-      Q[2 * 4 + j + 1] = P[2 * 4 + j + 1];
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      T s = sc.K[i * 3 + 0] * P[0 * 4 + j];
-      s = fmadd(sc.K[i * 3 + 1], P[1 * 4 + j], s);
-      s = fmadd(sc.K[i * 3 + 2], P[2 * 4 + j], s);
-      Q[i * 4 + j] = s;
-    }
-  }
-}
-
-// project2d (PE:1017-1034): p = (K34*T) * [X;1], u = p/p.z — full K, no distortion, no z>0 test
-template <typename T, int MAXM>
-__device__ __forceinline__ void project_markers(const FrameArgsT<T>& fa, const LdsConst<T>& sc, const T* P, T* u,
-                                                T* v) {
-  T Q[12];
-  k_times_pose<T>(sc, P, fa.k_upper != 0, Q);
-  if constexpr (std::is_same<T, float>::value) {  // rows 0 and 1 as one packed pair, same operations
-    // every slot up to MAXM is projected (markers past M are zeros, their u / v never read): no branch, so the
-    // u / v arrays stay in registers (a conditional store per slot had put them in scratch)
-    const f32x2 q0 = pk2(Q[0], Q[4]), q1 = pk2(Q[1], Q[5]), q2 = pk2(Q[2], Q[6]), q3 = pk2(Q[3], Q[7]);
-#pragma unroll
-    for (int j = 0; j < MAXM; ++j) {
-      const float X = sc.markers[3 * j], Y = sc.markers[3 * j + 1], Z = sc.markers[3 * j + 2];
-      f32x2 s = q0 * X;
-      s = pk_fma(q1, pk2(Y, Y), s);
-      s = pk_fma(q2, pk2(Z, Z), s);
-      s = s + q3;
-      float z = Q[8] * X;
-      z = fmadd(Q[9], Y, z);
-      z = fmadd(Q[10], Z, z);
-      z = z + Q[11];
-      const f32x2 uv = s * rcp_t(z);  // persp(): p0 * rcp(p2), p1 * rcp(p2)
-      u[j] = uv.x;
-      v[j] = uv.y;
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < MAXM; ++j) {
-    if (marker_live<MAXM>(j, fa.M)) {
-      const T X = sc.markers[3 * j], Y = sc.markers[3 * j + 1], Z = sc.markers[3 * j + 2];
-      T p[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        T s = Q[i * 4 + 0] * X;
-        s = fmadd(Q[i * 4 + 1], Y, s);
-        s = fmadd(Q[i * 4 + 2], Z, s);
-        p[i] = s + Q[i * 4 + 3];
-      }
-      persp(p[0], p[1], p[2], &u[j], &v[j]);
-    } else {
-      u[j] = v[j] = (T)0;
-    }
-  }
-}
-
-// project_markers' arithmetic for ONE marker j (wave-uniform index): the same operation order, so the
-// same bits
-template <typename T>
-__device__ __forceinline__ void project_one(const LdsConst<T>& sc, const T* P, int j, bool k_upper, T& u, T& v) {
-  T Q[12];
-  k_times_pose<T>(sc, P, k_upper, Q);
-  const T X = sc.markers[3 * j], Y = sc.markers[3 * j + 1], Z = sc.markers[3 * j + 2];
-  T p[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    T s = Q[i * 4 + 0] * X;
-    s = fmadd(Q[i * 4 + 1], Y, s);
-    s = fmadd(Q[i * 4 + 2], Z, s);
-    p[i] = s + Q[i * 4 + 3];
-  }
-  persp(p[0], p[1], p[2], &u, &v);
-}
-
-// x-buckets per frame: 2 per blob rounded up to a power of two, in [128, kMaxBuckets] — narrow enough
-// that the +-tolq window stays close to its own width when B is large (C3: 200 blobs, 1.5 px buckets)
-__host__ __device__ __forceinline__ constexpr int bucket_count(int B) {
-  int nb = 128;
-  while (nb < kMaxBuckets && nb < 2 * B) nb *= 2;
-  return nb;
-}
-// x -> bucket index (monotone in x; identical formula for table build and queries)
-template <typename T>
-__host__ __device__ __forceinline__ int bucket_of(T x, T xmin, T inv_bw, int nb) {
-  const T f = (x - xmin) * inv_bw;
-  if (!(f >= (T)0)) return 0;
-  if (f >= (T)(nb - 1)) return nb - 1;
-  return (int)f;
-}
-template <typename T>
-struct alignas(2 * sizeof(T)) BlobXY {
-  T x, y;
-};
-
-// calculateEstimationProbability (PE:2385-2445) in its closed form.  Step 1: per marker the first-minimum
-// blob over all blobs (column minimum of the B x M distance matrix; ties -> lowest blob index).
-// Step 2 (score_minima): extraction in ascending (distance, marker) order — the order Eigen's minCoeff
-// visitor finds them — with the same gate (tol_PF), score ((tol-d)/tol)^2 with tol NOT tol_PF,
-// self-occlusion (3*s) and downgrade (2) penalties, capped at min(B, M) pairs.
-//
-// Exact pruning (DESIGN.md "Exact blob pruning"): only blobs in the x-buckets overlapping the window
-// |bx-u| <= tolq (tolq >= tol_PF plus rounding slack) are visited.  Every blob within tol_PF lies in the
-// window, and a marker whose true minimum lies outside it fails the gate anyway, so accepted pairs,
-// penalties and the weight are unchanged; rejected markers only change their (unused) distance value.
-// fp32 tables also carry a 2D cell grid (build_blob_table_host): a marker's candidates are then ONE cell's
-// list (a 2D window instead of an x-strip), walked by column_minima's grid branch.
-template <typename T>
-struct LdsBlobs;
-
-// bucket_of without branches (fp32 kernels): max(f, 0) maps NaN and negatives to 0 (v_max_f32 returns the
-// non-NaN operand), min(., nb-1) clamps; the same bucket as bucket_of for every input
-__device__ __forceinline__ int bucket_of_bf(float x, float xmin, float inv_bw, int nb) {
-  const float f = (x - xmin) * inv_bw;
-  return (int)__builtin_fminf(__builtin_fmaxf(f, 0.0f), (float)(nb - 1));
-}
-
-// PHASED (k_frame2, whose VGPR budget holds every marker's cell record): the grid branch in phases over the
-// markers; the register-capped streaming kernels keep the per-marker form (the phases spill there)
-template <typename T, int MAXM, bool PRUNE, bool PHASED = false>
-__device__ __forceinline__ int column_minima(const FrameArgsT<T>& fa, const T* u, const T* v,
-                                             const LdsBlobs<T>& tb, T* m, int* r) {
-  const int B = fa.B, M = fa.M;
-  int visited = 0;
-  if constexpr (std::is_same<T, float>::value) {
-    // fp32: branch-free visits on ONE 64-bit key per candidate, {distance bits : original index}.  Distances
-    // are sums of squares (>= +0 or NaN), whose IEEE bits order like the values, and every NaN's bits lie
-    // above +inf's, so "key < best key" is exactly "strictly closer, or equally close with a lower original
-    // index" (the general form's tie rule) and a NaN distance is never taken.  A minimum that stays +inf keeps
-    // r = 0 (the general form's bc < 0 case); it fails the gate anyway.  Candidates go two per step, the
-    // second masked past the window end (its LDS reads stay inside the padded table, kTablePad).
-    // The query buckets: f = (u - (xmin -+ tolq)) * inv_bw, clamped by one med3 (NaN -> bucket 0 or any
-    // in-range bucket: a NaN projection never takes a candidate).  The two roundings of xmin -+ tolq and
-    // u - base are each within half an ulp of a pixel coordinate, like bucket_of's own, far inside tolq's
-    // slack (1e-3 px + 0.1 %): the window still holds every blob within tol_PF.
-    // The 2D grid (when the table has one built for at least this frame's window): the candidates of marker j
-    // are the one cell list its projection falls in (build_blob_table_host proves every blob within tol_PF is
-    // listed there); ~1 candidate per marker instead of an x-strip's ~2, so the wave's candidate walk is
-    // usually a single step.  Otherwise the x-buckets.
-    const GridArgs& ga = fa.grid;
-    if (PRUNE && ga.on) {  // wave-uniform (host: the table's grid covers this frame's window)
-      // Grid walk: one cell list per marker (~1 candidate).  Its entries are in increasing original index, so
-      // a strict "closer" test keeps the first (lowest-index) of equally close blobs, the key order above,
-      // and a NaN distance is never taken.  The list's first entry (the +inf sentinel for an empty cell) is
-      // taken without a test: bd = min(d, +inf) maps a NaN distance to +inf, and an empty cell leaves r = 0.
-      // Further entries are walked only when some lane's cell lists more than one blob (wave-uniform branch;
-      // the particles of a wave project each marker into one or two neighbouring cells, so it is rare).
-      // A non-finite first distance leaves r at that entry's index instead of 0: r is read only for a finite
-      // minimum within tol_PF (the gate), so no weight, pair or record changes.
-      const unsigned char* cells = tb.base + ga.cell_off;
-      const unsigned char* ents = tb.base + ga.ent_off;
-      const f32x2 ic = pk2(ga.inv_c, ga.inv_c), oc = pk2(ga.ox, ga.oy);
-      if constexpr (PHASED) {
-        // In phases over the markers (every cell record, then every first entry, then the longer lists behind
-        // one wave-uniform test): a per-marker branch kept each marker's two dependent LDS round trips from
-        // overlapping the next marker's, and at C2 (1.5 waves per SIMD) nothing else hides them
-        uint32_t rec[MAXM];
-  #pragma unroll
-        for (int j = 0; j < MAXM; ++j) {
-          rec[j] = 0;
-          if (marker_live<MAXM>(j, M)) {
-            const f32x2 f = pk_fma(pk2(u[j], v[j]), ic, oc);  // both cell coordinates in one v_pk_fma_f32
-            const int cx = (int)__builtin_amdgcn_fmed3f(f.x, 0.0f, ga.fmaxx);
-            const int cy = (int)__builtin_amdgcn_fmed3f(f.y, 0.0f, ga.fmaxy);
-            // byte offset cy * 4 ncx + 4 cx (the row pitch scaled on the host)
-            rec[j] = *(const uint32_t*)(cells + mad24(cy, ga.ncx4, cx << 2));
-          }
-        }
-        // The 12 / 16-marker buckets (C3: 200 blobs, clustered, most lists longer than one) read the first two
-        // entries together; the exact 5-marker bucket (50 blobs) reads one and walks further entries only when
-        // some lane of the wave needs them.
-        constexpr int c1 = MAXM > kExactM ? 2 : 1;
-        bool more = false;  // some live marker's list has more than c1 entries
-  #pragma unroll
-        for (int j = 0; j < MAXM; ++j) {
-          float bd = INFINITY;
-          int bo = 0;
-          if (marker_live<MAXM>(j, M)) {
-            const f32x2 uvj = pk2(u[j], v[j]);
-            const GridEnt* e = (const GridEnt*)(ents + (rec[j] & 0xffffu));
-            const int n = (int)(rec[j] >> 16);
-            visited += n;
-            more |= n > c1;
-            const GridEnt e0 = e[0];
-            const f32x2 dd = pk2(e0.x, e0.y) - uvj;  // (dx, dy) in one v_pk_add_f32
-            bd = __builtin_fminf(fmadd(dd.x, dd.x, dd.y * dd.y), INFINITY);
-            bo = e0.orig;
-            if constexpr (c1 == 2) {
-              const GridEnt e1 = e[1];
-              const f32x2 d1 = pk2(e1.x, e1.y) - uvj;
-              const float d = fmadd(d1.x, d1.x, d1.y * d1.y);
-              const bool take = (n > 1) & (d < bd);
-              bd = take ? d : bd;
-              bo = take ? e1.orig : bo;
-            }
-          }
-          m[j] = bd;
-          r[j] = bo;
-        }
-        if (__builtin_amdgcn_ballot_w64(more)) {  // rare at 50 blobs
-  #pragma unroll
-          for (int j = 0; j < MAXM; ++j) {
-            if (!marker_live<MAXM>(j, M)) continue;
-            const int n = (int)(rec[j] >> 16);
-            if (!__builtin_amdgcn_ballot_w64(n > c1)) continue;
-            const f32x2 uvj = pk2(u[j], v[j]);
-            const GridEnt* e = (const GridEnt*)(ents + (rec[j] & 0xffffu));
-            float bd = m[j];
-            int bo = r[j];
-            auto visit = [&](const GridEnt& ec, bool in) {
-              const f32x2 dd = pk2(ec.x, ec.y) - uvj;
-              const float d = fmadd(dd.x, dd.x, dd.y * dd.y);
-              const bool take = in & (d < bd);
-              bd = take ? d : bd;
-              bo = take ? ec.orig : bo;
-            };
-            // two entries per step, the second masked past the list end (its LDS read stays inside the table
-            // or its 16-B tail granule, BlobTable::lds_bytes)
-  #pragma unroll 2
-            for (int c = c1; c < n; c += 2) {
-              const GridEnt ea = e[c], eb = e[c + 1];
-              visit(ea, true);
-              visit(eb, c + 1 < n);
-            }
-            m[j] = bd;
-            r[j] = bo;
-          }
-        }
-      } else {
-  #pragma unroll
-        for (int j = 0; j < MAXM; ++j) {
-          float bd = INFINITY;
-          int bo = 0;
-          if (marker_live<MAXM>(j, M)) {
-            const f32x2 uvj = pk2(u[j], v[j]);
-            const f32x2 f = pk_fma(uvj, ic, oc);  // both cell coordinates in one v_pk_fma_f32
-            const int cx = (int)__builtin_amdgcn_fmed3f(f.x, 0.0f, ga.fmaxx);
-            const int cy = (int)__builtin_amdgcn_fmed3f(f.y, 0.0f, ga.fmaxy);
-            // byte offset cy * 4 ncx + 4 cx (the row pitch scaled on the host)
-            const uint32_t rec = *(const uint32_t*)(cells + mad24(cy, ga.ncx4, cx << 2));
-            const GridEnt* e = (const GridEnt*)(ents + (rec & 0xffffu));
-            const int n = (int)(rec >> 16);
-            visited += n;
-            auto visit = [&](const GridEnt& ec, bool in) {
-              const f32x2 dd = pk2(ec.x, ec.y) - uvj;
-              const float d = fmadd(dd.x, dd.x, dd.y * dd.y);
-              const bool take = in & (d < bd);
-              bd = take ? d : bd;
-              bo = take ? ec.orig : bo;
-            };
-            // The 12 / 16-marker buckets (C3: 200 blobs, clustered, most lists longer than one) read the first
-            // two entries together; the exact 5-marker bucket (50 blobs) reads one and walks further entries only
-            // when some lane of the wave needs them.
-            constexpr int c1 = MAXM > kExactM ? 2 : 1;
-            {
-              const GridEnt e0 = e[0];
-              const f32x2 dd = pk2(e0.x, e0.y) - uvj;  // (dx, dy) in one v_pk_add_f32
-              bd = __builtin_fminf(fmadd(dd.x, dd.x, dd.y * dd.y), INFINITY);
-              bo = e0.orig;
-              if constexpr (c1 == 2) visit(e[1], n > 1);
-            }
-            if (__builtin_amdgcn_ballot_w64(n > c1)) {  // some lane's list has more entries (rare at 50 blobs)
-              // two entries per step, the second masked past the list end (its LDS read stays inside the table
-              // or its 16-B tail granule, BlobTable::lds_bytes)
-  #pragma unroll 2
-              for (int c = c1; c < n; c += 2) {
-                const GridEnt ea = e[c], eb = e[c + 1];
-                visit(ea, true);
-                visit(eb, c + 1 < n);
-              }
-            }
-          }
-          m[j] = bd;
-          r[j] = bo;
-        }
-      }
-      return visited;
-    }
-    const float fmaxb = (float)(tb.nb - 1);
-    const float base_lo = tb.xmin + fa.tolq, base_hi = tb.xmin - fa.tolq;
-#pragma unroll
-    for (int j = 0; j < MAXM; ++j) {
-      uint64_t best = ((uint64_t)0x7f800000u << 32) | 0x7fffffffu;
-      if (marker_live<MAXM>(j, M)) {
-        int c0 = 0, c1 = B;
-        if (PRUNE) {
-          const float flo = (u[j] - base_lo) * tb.inv_bw;
-          const float fhi = (u[j] - base_hi) * tb.inv_bw;
-          c0 = tb.bstart[(int)__builtin_amdgcn_fmed3f(flo, 0.0f, fmaxb)];
-          c1 = tb.bstart[(int)__builtin_amdgcn_fmed3f(fhi, 0.0f, fmaxb) + 1];
-        }
-        visited += c1 - c0;
-        const float uj = u[j], vj = v[j];
-        const f32x2 uvj = pk2(uj, vj);
-        auto visit = [&](BlobXY<float> p, int o, bool in) {
-          const f32x2 dd = pk2(p.x, p.y) - uvj;  // (dx, dy) in one v_pk_add_f32
-          const float d = fmadd(dd.x, dd.x, dd.y * dd.y);
-          const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)o;
-          best = (in & (key < best)) ? key : best;
-        };
-        for (int c = c0; c < c1; c += 2) {
-          const BlobXY<float> pa = tb.bxy[c], pb = tb.bxy[c + 1];
-          const int oa = tb.orig[c], ob = tb.orig[c + 1];
-          visit(pa, oa, true);
-          visit(pb, ob, c + 1 < c1);
-        }
-      }
-      const float bm = __uint_as_float((uint32_t)(best >> 32));
-      m[j] = bm;
-      r[j] = bm < INFINITY ? (int)(uint32_t)best : 0;
-    }
-    return visited;
-  }
-#pragma unroll
-  for (int j = 0; j < MAXM; ++j) {
-    T best = inf_t<T>();
-    int bc = -1;  // table position of the current minimum
-    if (marker_live<MAXM>(j, M)) {
-      int c0 = 0, c1 = B;
-      if (PRUNE) {
-        c0 = tb.bstart[bucket_of(u[j] - fa.tolq, tb.xmin, tb.inv_bw, tb.nb)];
-        c1 = tb.bstart[bucket_of(u[j] + fa.tolq, tb.xmin, tb.inv_bw, tb.nb) + 1];
-      }
-      visited += c1 - c0;
-      auto visit = [&](int c, BlobXY<T> p) {
-        const T dx = p.x - u[j];
-        const T dy = p.y - v[j];
-        const T d = fmadd(dx, dx, dy * dy);
-        if (d < best) {
-          best = d;
-          bc = c;
-        } else if (d == best && bc >= 0 && tb.orig[c] < tb.orig[bc]) {
-          bc = c;
-        }
-      };
-      int c = c0;
-      for (; c + 1 < c1; c += 2) {  // two candidates' LDS reads in flight per step
-        const BlobXY<T> pa = tb.bxy[c], pb = tb.bxy[c + 1];
-        visit(c, pa);
-        visit(c + 1, pb);
-      }
-      if (c < c1) visit(c, tb.bxy[c]);
-    }
-    m[j] = best;
-    r[j] = bc >= 0 ? tb.orig[bc] : 0;
-  }
-  return visited;
-}
-
-// Eigen's visitor starts from coeff(0,0): a NaN distance there poisons the first minCoeff -> break at k=0
-template <typename T>
-__device__ __forceinline__ bool nan_at_origin(T b0x, T b0y, T u0, T v0) {
-  const T dx = b0x - u0, dy = b0y - v0;
-  const T d = dx * dx + dy * dy;
-  return d != d;
-}
-// The same test with the table's blob 0 finite (host flag, wave-uniform): (b0 - u0)^2 + (b0y - v0)^2 is NaN
-// exactly when u0 or v0 is NaN (an infinite difference squares to +inf and inf + inf = inf), one v_cmp_u; the
-// blob is read from the table header only when it is not finite.
-template <typename T>
-__device__ __forceinline__ bool nan_at_origin_tb(const FrameArgsT<T>& fa, const LdsBlobs<T>& tb, T u0, T v0) {
-  if (fa.grid.b0fin) return __builtin_isunordered(u0, v0);
-  const T* hdr = (const T*)tb.base;
-  return nan_at_origin(hdr[2], hdr[3], u0, v0);
-}
-
-// Extraction order = ascending (m_j, j): column minima are never NaN (they start at +inf and a NaN
-// distance never compares smaller), so a sorting network on the (m_j, j) keys yields exactly the pair
-// sequence of the reference's repeated minCoeff.  Batcher's odd-even merge sort, fully unrolled
-// (MAXM = 8: 19 compare-exchanges); markers j >= M sort last with key +inf and lie beyond L anyway.
-template <typename T>
-__device__ __forceinline__ void cas_key(T& ma, int& ja, int& ra, T& mb, int& jb, int& rb) {
-  const bool sw = mb < ma || (mb == ma && jb < ja);
-  const T m0 = sw ? mb : ma, m1 = sw ? ma : mb;
-  const int j0 = sw ? jb : ja, j1 = sw ? ja : jb;
-  const int r0 = sw ? rb : ra, r1 = sw ? ra : rb;
-  ma = m0; mb = m1; ja = j0; jb = j1; ra = r0; rb = r1;
-}
-template <typename T, int MAXM>
-__device__ __forceinline__ void sort_minima(T* km, int* kj, int* kr) {
-#pragma unroll
-  for (int p = 1; p < MAXM; p <<= 1)
-#pragma unroll
-    for (int k = p; k >= 1; k >>= 1)
-#pragma unroll
-      for (int j = k % p; j + k < MAXM; j += 2 * k)
-#pragma unroll
-        for (int i = 0; i < k; ++i)
-          if (i + j + k < MAXM && (i + j) / (2 * p) == (i + j + k) / (2 * p))
-            cas_key(km[i + j], kj[i + j], kr[i + j], km[i + j + k], kj[i + j + k], kr[i + j + k]);
-}
-
-template <typename T, int MAXM, bool PAIRS>
-__device__ __forceinline__ T score_minima(const FrameArgsT<T>& fa, const T* m, const int* r, uint32_t* pairs,
-                                          int* npairs) {
-  const int B = fa.B, M = fa.M;
-  const int L = B < M ? B : M;
-  const T tol = fa.tol, tol_pf = fa.tol_pf, Mt = (T)M;
-  T km[MAXM];
-  int kj[MAXM], kr[MAXM];
-#pragma unroll
-  for (int j = 0; j < MAXM; ++j) {
-    km[j] = marker_live<MAXM>(j, M) ? m[j] : inf_t<T>();
-    kj[j] = j;
-    kr[j] = r[j];
-  }
-  sort_minima<T, MAXM>(km, kj, kr);
-  T Pr = (T)0;
-  int s = 1;
-  bool live = true;
-  if (PAIRS) *npairs = 0;
-#pragma unroll
-  for (int k = 0; k < MAXM; ++k) {
-    if (k < L && live) {
-      const T d = sqrt_t(km[k]);
-      if (!(d <= tol_pf)) {
-        live = false;  // the reference's break
-      } else {
-        const T q = div_t(tol - d, tol);
-        Pr = Pr + (Mt + q * q);
-        bool dup = false;  // an earlier (accepted) pair holds the same blob
-#pragma unroll
-        for (int e = 0; e < k; ++e) dup |= kr[e] == kr[k];
-        if (dup) {
-          Pr = Pr - (T)(s * 3);
-          ++s;
-        }
-        if ((fa.downgrade >> kj[k]) & 1u) Pr = Pr - (T)2;
-        if (PAIRS) {
-          pairs[2 * k] = (uint32_t)kj[k] + 1u;
-          pairs[2 * k + 1] = (uint32_t)kr[k] + 1u;
-          *npairs = k + 1;
-        }
-      }
-    }
-  }
-  return Pr;
-}
-
-// The weight of score_minima<PAIRS = false> without the sort, for B >= M (fp32 tolerance path).  With
-// L = min(B, M) = M the cap never binds, and since the extraction runs in ascending distance the reference's
-// break leaves exactly the markers whose own minimum passes the gate: A = {j : sqrt(m_j) <= tol_PF}.  The
-// penalties depend on A only: 3*(1 + ... + D) with D = |A| - #distinct blobs over A (each marker whose blob
-// an earlier marker of A holds, in ANY fixed order, counts once: the same D as in extraction order), and 2
-// per downgraded marker of A.  Only the order of the fp32 additions differs from the extraction order
-// (a few ulp of a weight <= M(M+1)).
-template <int MAXM>
-__device__ __forceinline__ float score_unordered(const FrameArgsT<float>& fa, const float* m, const int* r) {
-  const int M = fa.M;
-  const float tol = fa.tol, tol_pf = fa.tol_pf, Mt = (float)M;
-  const float rtol = rcp_t(tol);
-  float Pr = 0.0f;
-  int dups = 0;
-  bool acc[MAXM];
-#pragma unroll
-  for (int j = 0; j < MAXM; ++j) {
-    const float d = sqrt_t(m[j]);
-    acc[j] = d <= tol_pf;  // markers past M have m = +inf (column_minima), never accepted
-    const float q = (tol - d) * rtol;
-    Pr = acc[j] ? Pr + (Mt + q * q) : Pr;
-    bool dup = false;
-#pragma unroll
-    for (int e = 0; e < j; ++e) dup |= acc[e] & (r[e] == r[j]);
-    dups += (acc[j] & dup) ? 1 : 0;
-  }
-  int ndg = 0;
-  if (fa.downgrade) {  // wave-uniform: the downgrade penalties (2 per accepted downgraded marker)
-#pragma unroll
-    for (int j = 0; j < MAXM; ++j) ndg += (acc[j] && ((fa.downgrade >> j) & 1u)) ? 1 : 0;
-  }
-  return Pr - (float)(3 * dups * (dups + 1) / 2 + 2 * ndg);
-}
-
-// ----------------------------------------------------------------------------- wave/block helpers
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-// Lanes of ONE wave exchanging data through LDS without a workgroup barrier: the hardware keeps a
-// wave's LDS operations in order, but the compiler must also be told that other lanes wrote (else it
-// may forward a lane's own earlier store to its read).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
-// the same, as an SGPR (block sizes are multiples of 64): a loop over the earlier waves then has a scalar trip
-// count instead of a per-wave v_cndmask chain.  (Used where that pays: as the general wave_id it moved the
-// weighing pass's register allocation for the worse.)
-__device__ __forceinline__ int wave_id_u() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-
-// All wave-level scans and reductions run on DPP lane moves (no LDS, no ds_bpermute): row_shr 1/2/4/8
-// builds the inclusive scan inside each 16-lane row, row_bcast:15 / row_bcast:31 carry row totals
-// across rows (GFX9-family DPP, kept by gfx950), so lane 63 ends with the wave total.  The pattern is
-// fixed, so a sum has ONE association everywhere it is evaluated (k_propagate_weigh and k_resample
-// must agree bit-for-bit).  Every lane of the wave must execute these (no divergent calls).
-enum : int {
-  kDppRowShr1 = 0x111, kDppRowShr2 = 0x112, kDppRowShr4 = 0x114, kDppRowShr8 = 0x118,
-  kDppWaveShr1 = 0x138, kDppBcast15 = 0x142, kDppBcast31 = 0x143
-};
-template <int CTRL, int RM = 0xf>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t src, uint32_t old) {
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, CTRL, RM, 0xf, false);
-}
-template <int CTRL, int RM = 0xf>
-__device__ __forceinline__ int dpp(int src, int old) {
-  return (int)dpp_u32<CTRL, RM>((uint32_t)src, (uint32_t)old);
-}
-template <int CTRL, int RM = 0xf>
-__device__ __forceinline__ float dpp(float src, float old) {
-  return __uint_as_float(dpp_u32<CTRL, RM>(__float_as_uint(src), __float_as_uint(old)));
-}
-template <int CTRL, int RM = 0xf>
-__device__ __forceinline__ double dpp(double src, double old) {
-  const uint64_t s = (uint64_t)__double_as_longlong(src), o = (uint64_t)__double_as_longlong(old);
-  const uint32_t lo = dpp_u32<CTRL, RM>((uint32_t)s, (uint32_t)o);
-  const uint32_t hi = dpp_u32<CTRL, RM>((uint32_t)(s >> 32), (uint32_t)(o >> 32));
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-// value of lane L in every lane (scalar result)
-// A value the optimiser may not look through.  In a select chain over a register array (lane q picks word
-// q) the loads would otherwise be folded into ONE load of a selected address, which pins the array in
-// scratch memory (a VMEM round trip per use); with the values opaque the chain stays v_cndmask.
-template <typename V>
-__device__ __forceinline__ V opaque(V x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ int lane_value(int x, int L) { return __builtin_amdgcn_readlane(x, L); }
-__device__ __forceinline__ float lane_value(float x, int L) {
-  return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(x), L));
-}
-__device__ __forceinline__ double lane_value(double x, int L) {
-  const uint64_t v = (uint64_t)__double_as_longlong(x);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, L);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), L);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-// lane i receives lane i-1's value, lane 0 receives `fill`
-template <typename V>
-__device__ __forceinline__ V wave_shr1(V x, V fill) {
-  return dpp<kDppWaveShr1>(x, fill);
-}
-
-struct OpSum {
-  __device__ double operator()(double a, double b) const { return a + b; }
-};
-struct OpMax {
-  __device__ double operator()(double a, double b) const { return b > a ? b : a; }
-};
-struct OpMin {
-  __device__ double operator()(double a, double b) const { return b < a ? b : a; }
-};
-struct OpMaxI {
-  __device__ int operator()(int a, int b) const { return b > a ? b : a; }
-};
-// inclusive scan x_0 op ... op x_i; `id` is the identity of op
-template <typename V, typename Op>
-__device__ __forceinline__ V wave_scan(V x, V id, Op op) {
-  x = op(x, dpp<kDppRowShr1>(x, id));
-  x = op(x, dpp<kDppRowShr2>(x, id));
-  x = op(x, dpp<kDppRowShr4>(x, id));
-  x = op(x, dpp<kDppRowShr8>(x, id));
-  x = op(x, dpp<kDppBcast15, 0xa>(x, id));
-  x = op(x, dpp<kDppBcast31, 0xc>(x, id));
-  return x;
-}
-// Sum scan of doubles: the four row_shr steps read 0 (bound_ctrl) from a lane outside the row, which is the
-// sum's identity (+0.0 is all-zero bits), so they need no fill register; the two row_bcast steps write only
-// some rows and keep the fill.  Bit-identical to wave_scan(v, 0.0, OpSum()).
-template <int CTRL>
-__device__ __forceinline__ double dpp_zf(double x) {
-  const uint64_t v = (uint64_t)__double_as_longlong(x);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)v, CTRL, 0xf, 0xf, true);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(v >> 32), CTRL, 0xf, 0xf, true);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-__device__ __forceinline__ double wave_incl_sum(double x) {
-  x = x + dpp_zf<kDppRowShr1>(x);
-  x = x + dpp_zf<kDppRowShr2>(x);
-  x = x + dpp_zf<kDppRowShr4>(x);
-  x = x + dpp_zf<kDppRowShr8>(x);
-  x = x + dpp<kDppBcast15, 0xa>(x, 0.0);
-  x = x + dpp<kDppBcast31, 0xc>(x, 0.0);
-  return x;
-}
-__device__ __forceinline__ double wave_incl_max(double v) { return wave_scan(v, -(double)INFINITY, OpMax()); }
-__device__ __forceinline__ double wave_incl_min(double v) { return wave_scan(v, (double)INFINITY, OpMin()); }
-__device__ __forceinline__ double wave_max(double v) { return lane_value(wave_incl_max(v), 63); }
-__device__ __forceinline__ double wave_min(double v) { return lane_value(wave_incl_min(v), 63); }
-
-// (value, index): larger value wins, lower index on ties
-// (selects, not branches: the wave reductions stay one basic block)
-template <typename V>
-__device__ __forceinline__ void cmb_max(V& v, int& i, V v2, int i2) {
-  const bool t = (v2 > v) | ((v2 == v) & (i2 < i));  // non-short-circuit: no exec-mask branches
-  v = t ? v2 : v;
-  i = t ? i2 : i;
-}
-template <typename V>
-__device__ __forceinline__ void cmb_min(V& v, int& i, V v2, int i2) {
-  const bool t = (v2 < v) | ((v2 == v) & (i2 < i));
-  v = t ? v2 : v;
-  i = t ? i2 : i;
-}
-// wave arg-reductions: the lexicographic (value, index) order is associative and commutative, so the
-// scan pattern reduces it exactly; the result is broadcast to every lane
-template <typename V, int CTRL, int RM = 0xf>
-__device__ __forceinline__ void argmax_step(V& v, int& i, V idv) {
-  const V v2 = dpp<CTRL, RM>(v, idv);
-  const int i2 = dpp<CTRL, RM>(i, 0x7fffffff);
-  cmb_max(v, i, v2, i2);
-}
-template <typename V, int CTRL, int RM = 0xf>
-__device__ __forceinline__ void argmin_step(V& v, int& i, V idv) {
-  const V v2 = dpp<CTRL, RM>(v, idv);
-  const int i2 = dpp<CTRL, RM>(i, 0x7fffffff);
-  cmb_min(v, i, v2, i2);
-}
-template <typename V>
-__device__ __forceinline__ void wave_argmax(V& v, int& i) {
-  const V id = -(V)INFINITY;
-  argmax_step<V, kDppRowShr1>(v, i, id);
-  argmax_step<V, kDppRowShr2>(v, i, id);
-  argmax_step<V, kDppRowShr4>(v, i, id);
-  argmax_step<V, kDppRowShr8>(v, i, id);
-  argmax_step<V, kDppBcast15, 0xa>(v, i, id);
-  argmax_step<V, kDppBcast31, 0xc>(v, i, id);
-  v = lane_value(v, 63);
-  i = lane_value(i, 63);
-}
-template <typename V>
-__device__ __forceinline__ void wave_argmin(V& v, int& i) {
-  const V id = (V)INFINITY;
-  argmin_step<V, kDppRowShr1>(v, i, id);
-  argmin_step<V, kDppRowShr2>(v, i, id);
-  argmin_step<V, kDppRowShr4>(v, i, id);
-  argmin_step<V, kDppRowShr8>(v, i, id);
-  argmin_step<V, kDppBcast15, 0xa>(v, i, id);
-  argmin_step<V, kDppBcast31, 0xc>(v, i, id);
-  v = lane_value(v, 63);
-  i = lane_value(i, 63);
-}
-// int counts: "-infinity" is INT_MIN
-template <>
-__device__ __forceinline__ void wave_argmax<int>(int& v, int& i) {
-  const int id = (int)0x80000000;
-  argmax_step<int, kDppRowShr1>(v, i, id);
-  argmax_step<int, kDppRowShr2>(v, i, id);
-  argmax_step<int, kDppRowShr4>(v, i, id);
-  argmax_step<int, kDppRowShr8>(v, i, id);
-  argmax_step<int, kDppBcast15, 0xa>(v, i, id);
-  argmax_step<int, kDppBcast31, 0xc>(v, i, id);
-  v = lane_value(v, 63);
-  i = lane_value(i, 63);
-}
-
-// Deterministic block inclusive scan: pre_w = ((0 + t_0) + t_1) + ... over earlier waves' totals, then
-// incl = pre_w + (wave inclusive).  k_propagate_weigh derives its partial extrema with exactly this
-// association, so both launches see bit-identical prefixes.  sh: >= kWaves doubles.
-// The wave scan of fp32 weights on the 2^-21 grid as integers.  Every weight of an M >= 4 frame is a multiple of
-// 2^-21 (each score term Mt + q^2 is >= 4, so every partial score, the integer penalties subtracted, is too), so
-// with 0 <= w < 32 in the wave, w * 2^21 is an integer below 2^26 and every 64-lane prefix lies below 2^32: the u32
-// scan is the exact prefix sum, which wave_incl_sum's fp64 partial sums (at most 32 significant bits) also are.
-// One v_add_u32_dpp per step instead of two v_mov_b32_dpp and a v_add_f64.
-__device__ __forceinline__ double wave_incl_sum_fx(float w) {
-  uint32_t x = (uint32_t)(w * 0x1p21f);
-  x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, kDppRowShr1, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, kDppRowShr2, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, kDppRowShr4, 0xf, 0xf, true);
-  x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, kDppRowShr8, 0xf, 0xf, true);
-  x += dpp_u32<kDppBcast15, 0xa>(x, 0u);
-  x += dpp_u32<kDppBcast31, 0xc>(x, 0u);
-  return (double)x * 0x1p-21;
-}
-// block inclusive prefix from the wave's inclusive scan wi (the earlier waves' totals through LDS)
-__device__ __forceinline__ void block_incl_from_wave(double wi, double& incl, double* sh) {
-  if (lane_id() == 63) sh[wave_id()] = wi;
-  __syncthreads();
-  double pre = 0.0;
-  const int wv = wave_id_u();
-#pragma clang loop unroll(disable)
-  for (int w = 0; w < wv; ++w) pre = pre + sh[w];  // a scalar trip count: no per-wave select chain
-  incl = pre + wi;
-}
-__device__ __forceinline__ void block_incl_sum(double v, double& incl, double* sh) {
-  const double wi = wave_incl_sum(v);
-  if (lane_id() == 63) sh[wave_id()] = wi;
-  __syncthreads();
-  double pre = 0.0;
-  const int wv = wave_id_u();
-#pragma clang loop unroll(disable)
-  for (int w = 0; w < wv; ++w) pre = pre + sh[w];  // a scalar trip count: no per-wave select chain
-  incl = pre + wi;
-}
-
-// ---- interleaved wave scans: several independent chains advanced step by step in ONE basic block, so
-// the DPP / f64 latencies of one chain hide behind the others.  Each chain's arithmetic is exactly that
-// of wave_scan / wave_argmax / wave_argmin (same steps, same identities, same operand order).
-template <int C, int R>
-struct DppStep {
-  static constexpr int ctrl = C, rm = R;
-};
-template <typename F>
-__device__ __forceinline__ void scan_steps(F&& f) {
-  f(DppStep<kDppRowShr1, 0xf>{});
-  f(DppStep<kDppRowShr2, 0xf>{});
-  f(DppStep<kDppRowShr4, 0xf>{});
-  f(DppStep<kDppRowShr8, 0xf>{});
-  f(DppStep<kDppBcast15, 0xa>{});
-  f(DppStep<kDppBcast31, 0xc>{});
-}
-template <typename S>
-__device__ __forceinline__ void st_sum(double& x) {
-  x = x + dpp<S::ctrl, S::rm>(x, 0.0);
-}
-template <typename S>
-__device__ __forceinline__ void st_max(double& x) {
-  const double y = dpp<S::ctrl, S::rm>(x, -(double)INFINITY);
-  x = y > x ? y : x;
-}
-template <typename S>
-__device__ __forceinline__ void st_min(double& x) {
-  const double y = dpp<S::ctrl, S::rm>(x, (double)INFINITY);
-  x = y < x ? y : x;
-}
-template <typename S, typename V>
-__device__ __forceinline__ void st_argmax(V& v, int& i) {
-  const V v2 = dpp<S::ctrl, S::rm>(v, -(V)INFINITY);
-  const int i2 = dpp<S::ctrl, S::rm>(i, 0x7fffffff);
-  cmb_max(v, i, v2, i2);
-}
-template <typename S, typename V>
-__device__ __forceinline__ void st_argmin(V& v, int& i) {
-  const V v2 = dpp<S::ctrl, S::rm>(v, (V)INFINITY);
-  const int i2 = dpp<S::ctrl, S::rm>(i, 0x7fffffff);
-  cmb_min(v, i, v2, i2);
-}
-template <typename V>
-__device__ __forceinline__ void bcast63(V& v, int& i) {
-  v = lane_value(v, 63);
-  i = lane_value(i, 63);
-}
-
-// fl(a / b) without the fp64 division: y = fl(1 / b) (Ctrl::invS, one division per frame), q0 = fl(a y), then two
-// Newton corrections with fma residuals.  After the first, q1 is a faithful approximation of a / b, so its residual
-// a - b q1 is exact, and fl(q1 + r1 y) = fl(a / b) (Markstein's theorem: y correctly rounded, no overflow or
-// underflow; tests/test_div_by_s.py checks 10^7 cases against IEEE division).  Callers use it only where the
-// quotient is in [0, ~1] and b is a normal positive double (fp32 weights, no negative weight in the wave), and
-// keep the IEEE division otherwise.
-__device__ __forceinline__ double div_by_S(double a, double b, double y) {
-  const double q0 = a * y;
-  const double r0 = __builtin_fma(-b, q0, a);
-  const double q1 = __builtin_fma(r0, y, q0);
-  const double r1 = __builtin_fma(-b, q1, a);
-  return __builtin_fma(r1, y, q1);
-}
 
 // ----------------------------------------------------------------------------- stratified targets
 // r_k = (k + U_k) / N  (PE:671); U_k is the k-th resample draw, taken after all motion draws.
@@ -1590,7 +179,6 @@ __device__ __forceinline__ double ld_wt_d(const double* p) { return __longlong_a
 // a whole BlockPart as three 16-B write-through-coherent (sc1) loads, issued without waiting.  The raw
 // registers are asm outputs; wait_parts drains vmcnt with them as in/out operands, so no use of them can
 // be scheduled before the wait.
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 struct PartRaw {
   u32x4_t a, b, c;
 };
@@ -1630,56 +218,12 @@ __device__ __forceinline__ bool wave_arrive_last(uint32_t* counter, int count) {
   return lane_value(last, 0) != 0;
 }
 
-// Diagnostic stamps (fa.diag & 4 only): s_memrealtime (100 MHz).  0/4 first block start of K1/K2 (min),
-// 1/5 last block partial (max), 2-3 / 6-7 top wave start/end, 8 table built, 9 weights done, 10 K2 scan
-// done, 11 counts done, 12 scatter done, 13-18 finalize phases, 19 earliest table built (min).
-constexpr int kStamps = 32;
-// diagnostic switches (FrameArgsT::diag, pfmpe_set_option(ctx, 99, bits)); 0 in production
-enum : int {
-  kDiagStamps = 4,      // phase stamps (s_memrealtime) into d_stamps
-  kDiagVisits = 8,      // pruned-candidate counts into d_stamps
-  kDiagTreeCount = 16,  // k_frame: count barrier as a tree instead of flat
-  kDiagSqrtGroups = 32, // groups of ~sqrt(nblk) blocks even when the frame fits k_frame2
-  kDiagLagLoads = 64,   // k_frame2: the last block sleeps ~20 us before loading the block partials
-  kDiagAbandon = 128,   // k_frame2: every block gives up its first weighing-barrier wait (recovery test)
-  kDiagSortedScore = 256, // fp32: the sorted (extraction-order) score even when B >= M (A/B of score_unordered)
-  kDiagNoStream = 512,     // two-launch path: never the streaming weighing pass (k_weigh_stream + k_group + k_top)
-  kDiagForceStream = 1024, // two-launch path: always the streaming weighing pass (tests / A/B)
-  kDiagSerialTop = 2048,   // streaming pass with > 64 groups: the one-wave k_top instead of k_top_wide (A/B)
-  kDiagNoPk = 4096,        // two-launch path: never the two-particles-per-lane pass k_weigh_pk (A/B, tests)
-  kDiagCorruptDesc = 8192, // pfmpe_step_multi: the first stream's descriptor is altered after its tag (test of the
-                           // staging check; the altered word is a key word, never a pointer)
-  kDiagNoDefer = 16384,    // two-launch frames materialise the new prior even with the kept set (A/B of deferral)
-  kDiagMinSide = 65536,      // k_frame2: run the zmin scans (group_zmin2) even when no weight can be negative (tests)
-  kDiagAbandonFinish = 131072,  // k_resample_owners(_multi): the finishing wave gives up before polling the arrivals
-                                // (the two-launch recovery tests)
-  kDiagBlockResample = 32768, // deferred two-launch frames resample with the block-per-256 k_resample instead of
-                              // k_resample_owners' wave per 256 (A/B, identity tests)
-  kDiagAssocDirect = 262144,  // pfmpe_assoc_stats: every vote straight into the device table even when the bins fit
-                              // in LDS (tests: both voting paths on one input)
-  kDiagDetCopy = 524288       // pfmpe_find_leds_streams: the crops go up by one async copy command instead of the
-                              // pull kernel k_detm_pull (A/B)
-};
-__device__ __forceinline__ uint64_t rt_now() { return __builtin_amdgcn_s_memrealtime(); }
-// per-block stamps go to the block's own row (plain stores, no contended atomics); the host reduces rows
-// (min for 0/4/19, max otherwise).  Row 0 holds the single-writer stamps (top / final waves).
-__device__ __forceinline__ void stamp_min(uint64_t* st, int idx, uint64_t t) {
-  if (st) st[(size_t)(1 + blockIdx.x) * kStamps + idx] = t;
-}
-__device__ __forceinline__ void stamp_max(uint64_t* st, int idx, uint64_t t) {
-  if (st) st[(size_t)(1 + blockIdx.x) * kStamps + idx] = t;
-}
 
 // ---- flat hand-off (k_frame2): sharded, monotonic arrival counters (no resets: the host tracks the running
 // totals and passes this frame's bases, uint32 arithmetic that wraps consistently).  A counter set is
 // kShards counters one 128-B line apart; an arrival goes to shard blk % kShards (one XCD's blocks under
 // round-robin placement: speed only).  Set 0: weighing barrier (one arrival per block per iteration),
 // set 1: count barrier (one per block per resampled frame).
-constexpr int kShards = 8;
-constexpr int kShardStride = 32;                         // uint32 words: 128 B
-constexpr int kFlatCountSet = kShards * kShardStride;    // offset of set 1
-constexpr int kFlatWords = 2 * kShards * kShardStride;
-constexpr int kFlatMaxGroups = 8;                        // k_frame2: <= 512 blocks in groups of 64
 __device__ __forceinline__ void flat_arrive(uint32_t* set, int blk) {  // one lane, after its sc1 stores
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __hip_atomic_fetch_add((gu32_t*)(set + (blk & (kShards - 1)) * kShardStride), 1u, __ATOMIC_RELAXED,
@@ -1711,11 +255,6 @@ __device__ __forceinline__ bool flat_wait(const uint32_t* set, uint32_t target, 
 // count wraps, so a stale word never carries a live tag.  (The weighing barrier keeps its counter: there every
 // block reads every partial, and polling 391 blocks x 96 B of granules from every block hammered the fabric: the
 // barrier took 20 us instead of 5 at C2, profiles/r05/granule_weighing_rejected.txt.)
-// The flat path's area: the two parities of block partials (BlockPart, k_frame2's weighing barrier), then the count
-// granules {count, index} of up to kFlatMaxGroups * kGroup blocks.
-constexpr size_t kGranPartBytes = (size_t)kFlatMaxGroups * kGroup * sizeof(BlockPart);  // per parity
-constexpr size_t kGranCountOff = 2 * kGranPartBytes;
-constexpr size_t kGranBytes = kGranCountOff + (size_t)kFlatMaxGroups * kGroup * 16;
 __device__ __forceinline__ void store_granule(uint64_t* g, uint32_t tag, uint32_t v) {
   __hip_atomic_store((gu64_t*)g, ((uint64_t)tag << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1724,277 +263,6 @@ __device__ __forceinline__ u32x4_t ld_gran2_issue(const uint64_t* p) {
   u32x4_t r;
   asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(r) : "v"((const char*)p) : "memory");
   return r;
-}
-
-// ============================================================================== kernels
-// ---- blob table (DESIGN.md "Exact blob pruning"), built once per frame on the host (build_blob_table_host,
-// O(B)) and copied whole into each block's LDS by the weighing kernels.  Layout, every part 16-byte aligned:
-//   base  hdr {T xmin, inv_bw, b0x, b0y} | int32 bstart[nb+1] | BlobXY<T> xy[B] | int32 orig[B]
-//         (the blobs grouped into nb = bucket_count(B) x-buckets, increasing original index within a bucket;
-//         every blob once: the linear scans of pose_pairs / k_resample_final and the fp64 pruned minima)
-//   grid  GridHdr | uint32 cell[ncell] (byte offset of the list in ent[] | count << 16) | GridEnt ent[nent + 1]
-//         (fp32 tables: a 2D cell grid over the blobs' bounding box widened by the pruning half-window; cell c
-//         lists every blob whose +-tolq box (plus 0.01 px) overlaps it, so a marker's candidates are ONE
-//         cell's list.  ent[0] is a sentinel {+inf, +inf, 0}: an empty cell points at it, so every query reads
-//         one entry without a test.  ncell = 0: no grid, the x-buckets serve; fp64 tables and large B never
-//         build one)
-__host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) / 16 * 16; }
-struct GridHdr {
-  float inv_c, gx0, gy0, pad0;     // cell of (u, v): ((u - gx0) * inv_c, (v - gy0) * inv_c), clamped
-  float fmaxx, fmaxy;              // ncx - 1, ncy - 1
-  float gtolq;                     // half-window the lists were built for (>= the frame's tolq to be used)
-  int32_t ncx, ncell, nent;        // columns, cells, list entries
-  int32_t b0fin, pad;              // blob 0 finite (every table, grid or not)
-};
-static_assert(sizeof(GridHdr) == 48, "grid header");
-// The cell budget of a table's grid: the coarse one (2,048 cells, 8 KB of records) for ordinary blob counts, the 4x
-// finer one (8,192, 32 KB) from kGridFineMinBlobs blobs (C3's 200 with clutter), whose cell lists are otherwise long
-// enough that most waves walk them: measured (profiles/r06/ab_grid_cells.txt) C3 weighing 56.5 -> 50.8 us with the
-// fine grid, while at 50 blobs (C2 / C4 / C5) its larger table copy costs 1.5-1.8 us per frame.  A fine grid over the
-// entry budget falls back to the coarse one, then to the x-buckets.
-constexpr int kGridMaxCells = 8192;   // cell records: 32 KB
-constexpr int kGridCoarseCells = 2048;
-#ifndef PFMPE_GRID_FINE_MIN_BLOBS
-#define PFMPE_GRID_FINE_MIN_BLOBS 128
-#endif
-constexpr int kGridFineMinBlobs = PFMPE_GRID_FINE_MIN_BLOBS;
-constexpr int kGridMaxEntries = 1024; // list entries: 16 KB (B up to ~400 blobs at 2-3 cells each)
-template <typename T>
-struct BlobTable {
-  static constexpr size_t off_bstart() { return align16(4 * sizeof(T)); }
-  static constexpr size_t off_xy(int B) { return off_bstart() + align16((size_t)(bucket_count(B) + 1) * 4); }
-  static constexpr size_t off_orig(int B) { return off_xy(B) + align16((size_t)B * sizeof(BlobXY<T>)); }
-  // the base part (every blob once): all the linear scans need
-  static constexpr size_t bytes(int B) { return off_orig(B) + align16((size_t)B * 4); }
-  static constexpr size_t off_grid(int B) { return bytes(B); }
-  static constexpr size_t grid_bytes(int ncell, int nent) {
-    return sizeof(GridHdr) + align16((size_t)ncell * 4) + (size_t)(nent + 1) * sizeof(GridEnt);
-  }
-  // a table's total size: base + grid (the host builder returns it; FrameArgsT::tbytes carries it)
-  static constexpr size_t total_bytes(int B, int ncell, int nent) { return bytes(B) + grid_bytes(ncell, nent); }
-  static constexpr size_t max_bytes() { return total_bytes(kMaxBlobs, kGridMaxCells, kGridMaxEntries); }
-  // LDS of the weighing kernels: the table plus one 16-B granule, so the masked second candidate of the
-  // fp32 column_minima steps (x-buckets, grid lists) reads inside the allocation
-  static constexpr size_t lds_bytes(size_t tbytes) { return tbytes + 16; }
-};
-
-template <typename T>
-struct LdsBlobs {
-  const unsigned char* base;  // the table (the grid's parts sit at FrameArgsT::grid offsets from it)
-  const BlobXY<T>* bxy;
-  const int32_t* orig;
-  const int32_t* bstart;  // nb + 1
-  T xmin, inv_bw;  // blob 0 (header words 2, 3): read where needed (nan_at_origin_tb)
-  int nb;
-};
-
-template <typename T>
-__host__ __device__ __forceinline__ LdsBlobs<T> view_table(const unsigned char* base, int B) {
-  LdsBlobs<T> t;
-  const T* hdr = (const T*)base;
-  t.base = base;
-  t.xmin = hdr[0];
-  t.inv_bw = hdr[1];
-  t.nb = bucket_count(B);
-  t.bstart = (const int32_t*)(base + BlobTable<T>::off_bstart());
-  t.bxy = (const BlobXY<T>*)(base + BlobTable<T>::off_xy(B));
-  t.orig = (const int32_t*)(base + BlobTable<T>::off_orig(B));
-  return t;
-}
-
-// The kernel arguments of a table's grid (host): on only when the table has a grid built for at least the
-// frame's window (tolq: FrameArgsT::tolq of the frame).  gh: the table's GridHdr (at off_grid(B)).
-template <typename T>
-inline GridArgs grid_args(const GridHdr& gh, int B, float tolq) {
-  GridArgs g{};
-  g.b0fin = gh.b0fin;
-  g.on = (gh.ncell > 0 && gh.gtolq >= tolq) ? 1 : 0;
-  if (!g.on) return g;
-  g.inv_c = gh.inv_c;
-  g.ox = (float)(-(double)gh.gx0 * (double)gh.inv_c);  // build_blob_table_host's proof covers this rounding
-  g.oy = (float)(-(double)gh.gy0 * (double)gh.inv_c);
-  g.fmaxx = gh.fmaxx;
-  g.fmaxy = gh.fmaxy;
-  g.ncx4 = 4 * gh.ncx;
-  g.cell_off = (int32_t)(BlobTable<T>::off_grid(B) + sizeof(GridHdr));
-  g.ent_off = g.cell_off + (int32_t)align16((size_t)gh.ncell * 4);
-  return g;
-}
-
-// Host builder; returns the table's size in bytes.  The bucket formula is bucket_of in T arithmetic (this TU:
-// -ffp-contract=off), the same expression the kernels evaluate for their query windows.  tolq: the pruning
-// half-window of the frames that will use the table (FrameArgsT::tolq, from tol_PF).
-template <typename T>
-inline size_t build_blob_table_host(const double* blobs, int B, double tolq, unsigned char* dst) {
-  T xmin = (T)INFINITY, xmax = -(T)INFINITY;
-  for (int i = 0; i < B; ++i) {
-    const T x = (T)blobs[2 * i];
-    xmin = x < xmin ? x : xmin;
-    xmax = x > xmax ? x : xmax;
-  }
-  if (B == 0 || !(xmax - xmin < (T)INFINITY)) {
-    xmin = (T)0;
-    xmax = (T)1;
-  }
-  T span = xmax - xmin;
-  if (!(span > (T)0)) span = (T)1;
-  const int nb = bucket_count(B);
-  const T inv_bw = (T)nb / span;
-  T* hdr = (T*)dst;
-  hdr[0] = xmin;
-  hdr[1] = inv_bw;
-  hdr[2] = B > 0 ? (T)blobs[0] : (T)0;
-  hdr[3] = B > 0 ? (T)blobs[1] : (T)0;
-  int32_t* bstart = (int32_t*)(dst + BlobTable<T>::off_bstart());
-  BlobXY<T>* xy = (BlobXY<T>*)(dst + BlobTable<T>::off_xy(B));
-  int32_t* orig = (int32_t*)(dst + BlobTable<T>::off_orig(B));
-  int32_t cnt[kMaxBuckets + 1] = {0};
-  for (int i = 0; i < B; ++i) ++cnt[bucket_of((T)blobs[2 * i], xmin, inv_bw, nb) + 1];
-  for (int b = 0; b < nb; ++b) cnt[b + 1] += cnt[b];
-  for (int b = 0; b <= nb; ++b) bstart[b] = cnt[b];
-  for (int i = 0; i < B; ++i) {
-    const int pos = cnt[bucket_of((T)blobs[2 * i], xmin, inv_bw, nb)]++;
-    xy[pos].x = (T)blobs[2 * i];
-    xy[pos].y = (T)blobs[2 * i + 1];
-    orig[pos] = i;
-  }
-  // ---- the grid (fp32 tables).  Device query: cell coordinate f = fma(u, inv_c, ox), ox = fl(-gx0 * inv_c),
-  // clamped by med3 to [0, ncx - 1], truncated.  Every blob within tol_PF of a query must be in the query's
-  // cell list:
-  //  * a blob is listed in every cell whose real-arithmetic interval [g(bx - m), g(bx + m)] it overlaps,
-  //    g(x) = (x - gx0) * inv_c with the fp32 constants the device uses, m = tolq + 0.01 px;
-  //  * the device's f differs from g(u) by the rounding of ox and of the fma (cell coordinates < 2^7: a few
-  //    1e-6 cells, 1e-4 px), far below the m - tol_PF >= 0.01 px slack; a clamped query (outside the widened
-  //    box) has no blob within tolq at all, so whatever its cell lists, its minimum fails the gate;
-  //  * every blob's own interval is clamped to the grid the same way.
-  // Each list holds its blobs in increasing original index (the fill below runs over i), so the device's
-  // strict "closer" comparison keeps the lowest index among equally close blobs: the reference's tie rule.
-  GridHdr* gh = (GridHdr*)(dst + BlobTable<T>::off_grid(B));
-  std::memset(gh, 0, sizeof(GridHdr));
-  gh->b0fin = (B > 0 && std::isfinite((double)hdr[2]) && std::isfinite((double)hdr[3])) ? 1 : 0;
-  size_t total = BlobTable<T>::total_bytes(B, 0, 0);
-  if (!std::is_same<T, float>::value || B == 0) return total;
-  const double m = tolq + 0.01;
-  double bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY;
-  for (int i = 0; i < B; ++i) {
-    const double x = (double)(float)blobs[2 * i], y = (double)(float)blobs[2 * i + 1];
-    if (!(x - x == 0.0) || !(y - y == 0.0)) return total;  // a non-finite blob: no grid
-    bx0 = std::min(bx0, x), bx1 = std::max(bx1, x), by0 = std::min(by0, y), by1 = std::max(by1, y);
-  }
-  const double gx0 = bx0 - m, gy0 = by0 - m, w = bx1 - bx0 + 2 * m, h = by1 - by0 + 2 * m;
-  for (int budget = B >= kGridFineMinBlobs ? kGridMaxCells : kGridCoarseCells;; budget = kGridCoarseCells) {
-  // square cells: at least the window (2m) and few enough for the cell budget
-  double cs = std::max(2.0 * m, std::sqrt(w * h / (double)budget));
-  int ncx = (int)std::ceil(w / cs), ncy = (int)std::ceil(h / cs);
-  while ((int64_t)ncx * ncy > budget) {
-    cs *= 1.0625;
-    ncx = (int)std::ceil(w / cs);
-    ncy = (int)std::ceil(h / cs);
-  }
-  ncx = std::max(1, ncx);
-  ncy = std::max(1, ncy);
-  const float inv_c = (float)(1.0 / cs), gx0f = (float)gx0, gy0f = (float)gy0;
-  // The device's cell coordinate fma(u, inv_c, ox) rounds twice (ox = fl(-gx0 * inv_c), then the fma), each by at
-  // most half an ulp of a value below |ox| + ncx cells, i.e. 2^-24 (|ox| + ncx) cells of cs px.  The lists hold
-  // every blob within m = tolq + 0.01 px of a cell, so the proof needs that error well inside m - tolq = 0.01 px:
-  // far-out blob coordinates (|gx0| ~ 1e5 px and beyond) make |ox| large, and then the x-buckets
-  // serve instead of the grid.
-  {
-    const double ex = std::ldexp(std::abs((double)gx0f) * (double)inv_c + ncx + 1.0, -23) * cs;
-    const double ey = std::ldexp(std::abs((double)gy0f) * (double)inv_c + ncy + 1.0, -23) * cs;
-    if (!(std::max(ex, ey) <= 0.25 * (m - tolq))) return total;
-  }
-  auto crange = [&](double lo, double hi, float inv, float org, int n, int& c0, int& c1) {
-    const double f0 = (lo - (double)org) * (double)inv, f1 = (hi - (double)org) * (double)inv;
-    c0 = (int)std::max(0.0, std::min((double)(n - 1), std::floor(f0)));
-    c1 = (int)std::max(0.0, std::min((double)(n - 1), std::floor(f1)));
-  };
-  const int ncell = ncx * ncy;
-  std::vector<int32_t> count(ncell + 1, 0);
-  int nent = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int32_t> fill;
-    if (pass == 1) {
-      for (int c = 0; c < ncell; ++c) count[c + 1] += count[c];
-      fill.assign(count.begin(), count.end() - 1);
-    }
-    for (int i = 0; i < B; ++i) {
-      const double x = (double)(float)blobs[2 * i], y = (double)(float)blobs[2 * i + 1];
-      int cx0, cx1, cy0, cy1;
-      crange(x - m, x + m, inv_c, gx0f, ncx, cx0, cx1);
-      crange(y - m, y + m, inv_c, gy0f, ncy, cy0, cy1);
-      for (int cy = cy0; cy <= cy1; ++cy)
-        for (int cx = cx0; cx <= cx1; ++cx) {
-          const int c = cy * ncx + cx;
-          if (pass == 0) {
-            ++count[c + 1];
-            ++nent;
-          } else {
-            const int e = 1 + fill[c]++;  // ent[0]: the sentinel
-            GridEnt* ent = (GridEnt*)((unsigned char*)gh + sizeof(GridHdr) + align16((size_t)ncell * 4));
-            ent[e] = GridEnt{(float)blobs[2 * i], (float)blobs[2 * i + 1], i, 0};
-          }
-        }
-    }
-    if (pass == 0 && nent > kGridMaxEntries) break;  // too many entries: a coarser grid, then the x-buckets
-  }
-  if (nent > kGridMaxEntries) {
-    if (budget == kGridCoarseCells) return total;
-    continue;
-  }
-  uint32_t* cell = (uint32_t*)((unsigned char*)gh + sizeof(GridHdr));
-  for (int c = 0; c < ncell; ++c) {  // an empty cell points at the sentinel (byte offset 0)
-    const uint32_t n = (uint32_t)(count[c + 1] - count[c]);
-    cell[c] = (n ? (uint32_t)(1 + count[c]) * (uint32_t)sizeof(GridEnt) : 0u) | (n << 16);
-  }
-  GridEnt* ent = (GridEnt*)((unsigned char*)cell + align16((size_t)ncell * 4));
-  ent[0] = GridEnt{INFINITY, INFINITY, 0, 0};  // sentinel: distance +inf (NaN for a non-finite query), index 0
-
-  gh->inv_c = inv_c;
-  gh->gx0 = gx0f;
-  gh->gy0 = gy0f;
-  gh->fmaxx = (float)(ncx - 1);
-  gh->fmaxy = (float)(ncy - 1);
-  gh->gtolq = (float)tolq;
-  gh->ncx = ncx;
-  gh->ncell = ncell;
-  gh->nent = nent;
-  return BlobTable<T>::total_bytes(B, ncell, nent);
-  }
-}
-
-// block-wide copy of the table into LDS (16-byte words); callers barrier before use
-__device__ __forceinline__ void copy_table(const unsigned char* __restrict__ src, unsigned char* dst, size_t bytes) {
-  // global loads (src may come from a batched launch's stream descriptor, which hides its address space)
-  typedef __attribute__((address_space(1))) const u32x4_t gv4_t;
-  gv4_t* s4 = (gv4_t*)src;
-  u32x4_t* d4 = (u32x4_t*)dst;
-  const int n4 = (int)(bytes / 16);
-  for (int i = threadIdx.x; i < n4; i += kBlock) d4[i] = s4[i];
-}
-
-// copy_table + stage_consts_from with every load issued before the first LDS store: one memory round trip for the
-// table (its first 8 KB: two 16-B loads per thread), the frame constants and whatever the caller issued before
-// (k_frame2: the prior), instead of one per loop and per copy
-template <typename T>
-__device__ __forceinline__ void stage_table_consts(const unsigned char* __restrict__ src, unsigned char* dst, size_t bytes,
-                                                   const uint32_t* cw_src, LdsConst<T>& sc) {
-  typedef __attribute__((address_space(1))) const u32x4_t gv4_t;
-  gv4_t* s4 = (gv4_t*)src;
-  u32x4_t* d4 = (u32x4_t*)dst;
-  const int n4 = (int)(bytes / 16);
-  const int t = threadIdx.x;
-  constexpr int kWordsC = (int)(sizeof(LdsConst<T>) / 4);
-  static_assert(kWordsC <= kBlock, "one constant word per thread");
-  u32x4_t r0 = {0u, 0u, 0u, 0u}, r1 = {0u, 0u, 0u, 0u};
-  uint32_t cw = 0u;
-  if (t < n4) r0 = s4[t];
-  if (t + kBlock < n4) r1 = s4[t + kBlock];
-  if (t < kWordsC) cw = cw_src[t];
-  if (t < n4) d4[t] = r0;
-  if (t + kBlock < n4) d4[t + kBlock] = r1;
-  if (t < kWordsC) ((uint32_t*)&sc)[t] = cw;
-  for (int i = t + 2 * kBlock; i < n4; i += kBlock) d4[i] = s4[i];  // tables past 8 KB (large B)
 }
 
 // Control record / scan records move between blocks of one launch (and, in k_frame, between the
@@ -2307,35 +575,6 @@ __device__ __forceinline__ void propagate_top(const FrameArgsT<T>& fa, Ctrl* __r
       __hip_atomic_store((gu32_t*)gen, gen_base + (uint32_t)iter + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-}
-
-// ---- one particle through the motion model, projection and likelihood (PE:543-604, PE:2385)
-template <typename T, int RNG, int MAXM, bool PRUNE, bool PHASED = false>
-__device__ __forceinline__ T weigh_particle(const FrameArgsT<T>& fa, const LdsConst<T>& sc, const LdsBlobs<T>& tb,
-                                            const T* A, int n, int iter, T* P, int* nvisit = nullptr,
-                                            uint64_t* st = nullptr) {
-  T u[MAXM], v[MAXM];
-  propagate<T, RNG>(fa, sc, A, n, iter, P);
-  if (st && threadIdx.x == 0) stamp_max(st, 27, rt_now() + (P[11] == (T)12345 ? 1 : 0));
-  project_markers<T, MAXM>(fa, sc, P, u, v);
-  if (st && threadIdx.x == 0) stamp_max(st, 28, rt_now() + (u[0] == (T)12345 ? 1 : 0));
-  T w = (T)0;
-  if (fa.B > 0 && !nan_at_origin_tb(fa, tb, u[0], v[0])) {
-    T m[MAXM];
-    int r[MAXM];
-    const int visited = column_minima<T, MAXM, PRUNE, PHASED>(fa, u, v, tb, m, r);
-    if (nvisit) *nvisit = visited;
-    if (st && threadIdx.x == 0) stamp_max(st, 29, rt_now() + (m[0] == (T)12345 ? 1 : 0));
-    if constexpr (std::is_same<T, float>::value) {
-      if (fa.B >= fa.M && !(fa.diag & kDiagSortedScore))  // wave-uniform
-        w = score_unordered<MAXM>(fa, m, r);
-      else
-        w = score_minima<T, MAXM, false>(fa, m, r, nullptr, nullptr);
-    } else {
-      w = score_minima<T, MAXM, false>(fa, m, r, nullptr, nullptr);
-    }
-  }
-  return w;
 }
 
 // A wave's weight partials (the wave-inclusive scan wi of the weights, the extrema of wi over valid lanes,
@@ -3069,7 +1308,7 @@ __global__ __launch_bounds__(kBlock) void k_stage_multi(const unsigned char* __r
 
 // The block's stream and its stream-local block index, or -1 for a block the map does not place inside a
 // stream of this batch whose descriptor passed the staging check (never on a consistent batch: the host audits
-// the layout before every launch, pfmpe_ctx.hpp audit_batch, and tags every descriptor; the guard keeps a
+// the layout before every launch, pfmpe_seq.hpp audit_batch, and tags every descriptor; the guard keeps a
 // corrupt map or descriptor from turning into out-of-range accesses).  A stale map entry cannot misplace a
 // block: the range test runs against a checked descriptor, and checked streams' ranges are disjoint.
 template <typename T, typename SP>
@@ -3102,17 +1341,6 @@ __global__ __launch_bounds__(kBlock) void k_propagate_weigh_multi(const StreamDe
                                                  d.gpart1, d.gscan, d.ctrl, d.gcount_w, d.tcount_w, d.prop0, d.prop1,
                                                  iter, nullptr, smem, sc, sh);
 }
-
-// Winner candidate of one block: the block's first max-count particle, its kept pose and its
-// correspondences, published by the block's wave 1 (in parallel with wave 0's arrival) as data-tagged
-// granules: 8-byte words {payload (low 32 bits), frame sequence (high 32)}, each written by ONE
-// write-through store, so a reader that sees every tag current has every payload (MI355X_MICROARCH.md
-// "handoff-1to1").  Granules 0-23: the 12 pose doubles as lo/hi halves; 24-55: the 32 corr words;
-// 56: n_corr.  The global winner is one of these, so the final wave loads one block's granules.
-constexpr int kCandGran = 57;
-struct alignas(16) Cand {
-  uint64_t g[64];
-};
 
 // correspondences (PE:2385-2445 with pairs) of ONE pose P (uniform across the wave): blobs spread over
 // the lanes, (distance, original index) order as column_minima, then the sorting-network score.
@@ -4803,7 +3031,7 @@ __device__ __forceinline__ Ctrl top_math_regs(const FrameArgsT<T>& fa, Ctrl c, i
   return c;
 }
 
-// The flat frame is one launch only while 2 blocks fit per CU next to the occupancy margin (pfmpe_ctx.hpp
+// The flat frame is one launch only while 2 blocks fit per CU next to the occupancy margin (pfmpe_seq.hpp
 // frame_fused), i.e. 3 waves per SIMD (<= 168 VGPRs).  Without the cap fp64 took 214 VGPRs and fp32 187 once the
 // granule polls kept 12 16-B loads per lane in flight (both would silently fall back to two launches above 256
 // blocks); with it fp32 fits without scratch.
@@ -5043,29 +3271,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PFMPE_FR
                                              seq, stamps, smem, S2);
 }
 
-// ---- state import / export / regeneration (API helpers, not on the timed path).  anchor: the set's
-// anchor pose (fp16 state), ignored for fp32 / fp64 planes.
-template <typename T>
-struct Pose12 {
-  T v[12];
-};
-template <typename T, typename SP>
-__global__ void k_import(const double* __restrict__ poses, SP* __restrict__ st, int N, int64_t ld,
-                         const Pose12<T> anchor) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  for (int q = 0; q < 12; ++q)
-    st[plane_index<SP>(q, n, ld)] = StateIO<T, SP>::store((T)poses[12 * (int64_t)n + q], anchor.v[q]);
-}
-template <typename T, typename SP>
-__global__ void k_export(const SP* __restrict__ st, double* __restrict__ poses, int N, int64_t ld,
-                         const Pose12<T> anchor, const uint32_t* __restrict__ owner) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  const int r = owner ? (int)owner[n] : n;  // a deferred prior: stored row owner[n]
-  for (int q = 0; q < 12; ++q)
-    poses[12 * (int64_t)n + q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ld)], anchor.v[q]);
-}
 template <typename T, int RNG, typename SP>
 __global__ __launch_bounds__(kBlock) void k_regen(const FrameArgsT<T> fa, int kept_iter, const SP* __restrict__ prior,
                                                  double* __restrict__ poses) {
@@ -5078,500 +3283,60 @@ __global__ __launch_bounds__(kBlock) void k_regen(const FrameArgsT<T> fa, int ke
   make_particle<T, RNG, SP>(fa, sc, prior, n, kept_iter, P);
   for (int q = 0; q < 12; ++q) poses[12 * (int64_t)n + q] = (double)P[q];
 }
-// ---- ROI prediction (§8f next row 1): predictMarkerPositionsInImage (PE:1036-1053) projects every marker
-// through camMoveInv * prior_j * predictionMatrix (Eigen left-to-right products) for all N particles of
-// the current prior; LEDDetector::determineROI (led_detector.cpp:217-243) keeps x_min / y_min from +inf and
-// x_max / y_max from 0 with strict comparisons (NaN positions never win).  fp64 throughout: the same
-// arithmetic as the oracle, so the box is exact for every state type.  One partial per block, then one
-// block reduces them.
-struct RoiArgs {
-  double cam[12], predm[12], K[9], markers[kMaxMarkers * 3], anchor[12];
-  int32_t N, M;
-  int64_t ld;
-  const uint32_t* owner;  // a deferred prior's owner indices (FrameArgsT::owner), or null
-};
-// One particle's share of the box: prior particle n (stored row owner[n] of a deferred prior) through
-// camMoveInv * prior_n * predictionMatrix, K * that, and the M projections folded into box = {x_min, x_max, y_min,
-// y_max} with the reference's strict comparisons.  The one body of k_roi, k_roi_multi and the host twin
-// (pfmpe_host_predict_roi, which passes each caller-given pose as a one-particle set with ld = 1); host and device
-// are built with -ffp-contract=off, so they round alike.
-template <typename T, typename SP>
-__host__ __device__ __forceinline__ void roi_particle_box(const RoiArgs& ra, const SP* __restrict__ prior, const int n,
-                                                          double& xmin, double& xmax, double& ymin, double& ymax) {
-  double A[12], X[12], P[12];
-  const int r = ra.owner ? (int)ra.owner[n] : n;
-#pragma unroll
-  for (int q = 0; q < 12; ++q)
-    A[q] = (double)StateIO<T, SP>::load(prior[plane_index<SP>(q, r, ra.ld)], (T)ra.anchor[q]);
-  compose(ra.cam, A, X);   // camMoveInv * newPoseEstimation[j]
-  compose(X, ra.predm, P); // ... * predictionMatrix
-  double Q[12];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double s = ra.K[i * 3 + 0] * P[0 * 4 + j];
-      s = s + ra.K[i * 3 + 1] * P[1 * 4 + j];
-      s = s + ra.K[i * 3 + 2] * P[2 * 4 + j];
-      Q[i * 4 + j] = s;
-    }
-  for (int m = 0; m < ra.M; ++m) {
-    const double x = ra.markers[3 * m], y = ra.markers[3 * m + 1], z = ra.markers[3 * m + 2];
-    double p[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      double s = Q[i * 4 + 0] * x;
-      s = s + Q[i * 4 + 1] * y;
-      s = s + Q[i * 4 + 2] * z;
-      p[i] = s + Q[i * 4 + 3];
-    }
-    const double u = p[0] / p[2], v = p[1] / p[2];
-    if (u < xmin) xmin = u;
-    if (u > xmax) xmax = u;
-    if (v < ymin) ymin = v;
-    if (v > ymax) ymax = v;
-  }
-}
-// the lanes' boxes of one block -> o[0..3], written by thread 0
-__device__ __forceinline__ void roi_block_box(double (&sh)[4][kWaves], double xmin, double xmax, double ymin,
-                                              double ymax, double* __restrict__ o) {
-  xmin = wave_min(xmin);
-  xmax = wave_max(xmax);
-  ymin = wave_min(ymin);
-  ymax = wave_max(ymax);
-  const int lane = lane_id(), wv = wave_id();
-  if (lane == 0) {
-    sh[0][wv] = xmin;
-    sh[1][wv] = xmax;
-    sh[2][wv] = ymin;
-    sh[3][wv] = ymax;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; ++w) {
-      xmin = sh[0][w] < xmin ? sh[0][w] : xmin;
-      xmax = sh[1][w] > xmax ? sh[1][w] : xmax;
-      ymin = sh[2][w] < ymin ? sh[2][w] : ymin;
-      ymax = sh[3][w] > ymax ? sh[3][w] : ymax;
-    }
-    o[0] = xmin;
-    o[1] = xmax;
-    o[2] = ymin;
-    o[3] = ymax;
-  }
-}
-// nblk block partials -> out[0..3], by one block (several passes of the strided loop when nblk > kBlock)
-__device__ __forceinline__ void roi_partials_box(double (&sh)[4][kWaves], const double* __restrict__ part,
-                                                 const int nblk, double* __restrict__ out) {
-  double xmin = INFINITY, xmax = 0.0, ymin = INFINITY, ymax = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += kBlock) {
-    const double* o = part + 4 * (size_t)b;
-    xmin = o[0] < xmin ? o[0] : xmin;
-    xmax = o[1] > xmax ? o[1] : xmax;
-    ymin = o[2] < ymin ? o[2] : ymin;
-    ymax = o[3] > ymax ? o[3] : ymax;
-  }
-  roi_block_box(sh, xmin, xmax, ymin, ymax, out);
+// stream of the batch, one launch each): grid (max groups, streams) for the group scans, (streams) for the tops.
+// The bodies are the one-stream kernels' (same functions, same association), with the stream's frame arguments,
+// buffers and counters from its descriptor; blocks past a stream's groups, and streams that failed the staging
+// check, return at once.
+template <typename T, int RNG, typename SP>
+__global__ __launch_bounds__(64) void k_group_top_multi(const StreamDesc<T, SP>* __restrict__ descs, int S,
+                                                        const uint32_t* __restrict__ status, uint32_t gen, int iter) {
+  const int s = (int)blockIdx.y;
+  if (s >= S || __builtin_amdgcn_readfirstlane(status[s]) != gen) return;
+  const StreamDesc<T, SP>& d = descs[s];
+  const int g = (int)blockIdx.x;
+  const int ngrp = __builtin_amdgcn_readfirstlane(d.fa.ngrp);
+  if (g >= ngrp) return;
+  Ctrl* ctrl = d.ctrl;
+  if (load_ctrl_word<(int)offsetof(Ctrl, done)>(ctrl)) return;  // every block reads ctrl before it arrives
+  const int slot = load_ctrl_word<(int)offsetof(Ctrl, cur_slot)>(ctrl);
+  const GroupPart gr = propagate_group<true>(__builtin_amdgcn_readfirstlane(d.fa.nblk), __builtin_amdgcn_readfirstlane(d.fa.gsz),
+                                             g, slot ? d.part1 : d.part0, slot ? d.bscan1 : d.bscan0,
+                                             slot ? d.gpart1 : d.gpart0);
+  const bool single = ngrp == 1;
+  if (!single && !wave_arrive_last(d.tcount_w, ngrp)) return;
+  propagate_top<T, RNG>(d.fa, ctrl, iter, d.gpart0, d.gpart1, d.gscan, nullptr, 0u, gr, single, slot);
 }
 template <typename T, typename SP>
-__global__ __launch_bounds__(kBlock) void k_roi(const RoiArgs ra, const SP* __restrict__ prior,
-                                               double* __restrict__ part) {
-  __shared__ double sh[4][kWaves];
-  const int n = blockIdx.x * kBlock + threadIdx.x;
-  double xmin = INFINITY, xmax = 0.0, ymin = INFINITY, ymax = 0.0;
-  // (the text of roi_particle_box and roi_block_box, kept here: calling either changes this kernel's register
-  // allocation, and the single call is the timing baseline of the batch)
-  if (n < ra.N) {
-    double A[12], X[12], P[12];
-    const int r = ra.owner ? (int)ra.owner[n] : n;
-#pragma unroll
-    for (int q = 0; q < 12; ++q)
-      A[q] = (double)StateIO<T, SP>::load(prior[plane_index<SP>(q, r, ra.ld)], (T)ra.anchor[q]);
-    compose(ra.cam, A, X);   // camMoveInv * newPoseEstimation[j]
-    compose(X, ra.predm, P); // ... * predictionMatrix
-    double Q[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        double s = ra.K[i * 3 + 0] * P[0 * 4 + j];
-        s = s + ra.K[i * 3 + 1] * P[1 * 4 + j];
-        s = s + ra.K[i * 3 + 2] * P[2 * 4 + j];
-        Q[i * 4 + j] = s;
-      }
-    for (int m = 0; m < ra.M; ++m) {
-      const double x = ra.markers[3 * m], y = ra.markers[3 * m + 1], z = ra.markers[3 * m + 2];
-      double p[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        double s = Q[i * 4 + 0] * x;
-        s = s + Q[i * 4 + 1] * y;
-        s = s + Q[i * 4 + 2] * z;
-        p[i] = s + Q[i * 4 + 3];
-      }
-      const double u = p[0] / p[2], v = p[1] / p[2];
-      if (u < xmin) xmin = u;
-      if (u > xmax) xmax = u;
-      if (v < ymin) ymin = v;
-      if (v > ymax) ymax = v;
-    }
-  }
-  xmin = wave_min(xmin);
-  xmax = wave_max(xmax);
-  ymin = wave_min(ymin);
-  ymax = wave_max(ymax);
-  const int lane = lane_id(), wv = wave_id();
-  if (lane == 0) {
-    sh[0][wv] = xmin;
-    sh[1][wv] = xmax;
-    sh[2][wv] = ymin;
-    sh[3][wv] = ymax;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; ++w) {
-      xmin = sh[0][w] < xmin ? sh[0][w] : xmin;
-      xmax = sh[1][w] > xmax ? sh[1][w] : xmax;
-      ymin = sh[2][w] < ymin ? sh[2][w] : ymin;
-      ymax = sh[3][w] > ymax ? sh[3][w] : ymax;
-    }
-    double* o = part + 4 * (size_t)blockIdx.x;
-    o[0] = xmin;
-    o[1] = xmax;
-    o[2] = ymin;
-    o[3] = ymax;
-  }
+__global__ __launch_bounds__(64) void k_group_multi(const StreamDesc<T, SP>* __restrict__ descs, int S,
+                                                    const uint32_t* __restrict__ status, uint32_t gen) {
+  const int s = (int)blockIdx.y;
+  if (s >= S || __builtin_amdgcn_readfirstlane(status[s]) != gen) return;
+  const StreamDesc<T, SP>& d = descs[s];
+  const int g = (int)blockIdx.x;
+  if (g >= __builtin_amdgcn_readfirstlane(d.fa.ngrp)) return;
+  if (load_ctrl_word<(int)offsetof(Ctrl, done)>(d.ctrl)) return;
+  const int slot = load_ctrl_word<(int)offsetof(Ctrl, cur_slot)>(d.ctrl);
+  (void)propagate_group<true>(__builtin_amdgcn_readfirstlane(d.fa.nblk), __builtin_amdgcn_readfirstlane(d.fa.gsz), g,
+                              slot ? d.part1 : d.part0, slot ? d.bscan1 : d.bscan0, slot ? d.gpart1 : d.gpart0);
 }
-template <typename T>  // (a template only for COMDAT linkage: the header is in several TUs)
-__global__ __launch_bounds__(kBlock) void k_roi_final(const T* __restrict__ part, int nblk, T* __restrict__ out) {
-  __shared__ double sh[4][kWaves];
-  roi_partials_box(sh, part, nblk, out);
+template <typename T, int RNG, typename SP>
+__global__ __launch_bounds__(64 * kTopWaves) void k_top_wide_multi(const StreamDesc<T, SP>* __restrict__ descs, int S,
+                                                                const uint32_t* __restrict__ status, uint32_t gen,
+                                                                int iter) {
+  extern __shared__ __attribute__((aligned(16))) GroupPart gsm[];  // the largest stream's ngrp entries
+  __shared__ TopWideLds tw;
+  const int s = (int)blockIdx.x;
+  if (s >= S || __builtin_amdgcn_readfirstlane(status[s]) != gen) return;
+  const StreamDesc<T, SP>& d = descs[s];
+  top_wide_body<T, RNG>(d.fa, d.gpart0, d.gpart1, d.gscan, d.ctrl, iter, gsm, tw);
 }
-
-// ---- the ROIs of S contexts in one batch (pfmpe_predict_roi_multi).  One flat grid: stream s owns the blocks
-// first[s] .. first[s + 1] (kBlock particles each, the blocks of its single call), so a small cloud next to a large
-// one launches its own block count only.  A block finds its stream by one wave-wide comparison against the prefix
-// (S <= 64 = the wave size: lane s holds first[s]); the index is wave-uniform, so the descriptor is read with scalar
-// loads.  Block and wave boundaries, the partials and their reduction are the single call's, so are the bits.
-constexpr int kRoiMaxStreams = 64;
-static_assert(kRoiMaxStreams <= 64, "roi_stream_of_block compares one prefix entry per lane of a wave");
-struct RoiBatch {  // head of the batch's device image, the descriptors follow
-  int32_t S, pad;
-  int32_t first[kRoiMaxStreams + 1];  // first block of stream s; first[S] = all blocks
-  int32_t pad2;
-};
-struct RoiDesc {
-  RoiArgs a;
-  const void* prior;
-};
-static_assert(sizeof(RoiBatch) % sizeof(uint64_t) == 0 && sizeof(RoiDesc) % sizeof(uint64_t) == 0,
-              "k_roi_stage copies 8-byte words");
-__device__ __forceinline__ int roi_stream_of_block(const int32_t* __restrict__ first, const int S, const int b) {
-  const int lane = threadIdx.x & 63;
-  const bool le = lane < S && first[lane] <= b;  // first[0] = 0: at least one
-  return __builtin_amdgcn_readfirstlane(__popcll(__ballot(le)) - 1);
-}
-// The batch's first launch: head and descriptors from the host's pinned image into device memory, so that the
-// particle blocks read them from L2 and not over the host link.
-template <typename W>
-__global__ __launch_bounds__(kBlock) void k_roi_stage(const W* __restrict__ src, W* __restrict__ dst, const int nwords) {
-  for (int i = threadIdx.x; i < nwords; i += kBlock) dst[i] = src[i];
-}
-template <typename T, typename SP>
-__global__ __launch_bounds__(kBlock) void k_roi_multi(const RoiBatch* __restrict__ hd, const RoiDesc* __restrict__ descs,
-                                                     double* __restrict__ part) {
-  __shared__ double sh[4][kWaves];
-  const int s = roi_stream_of_block(hd->first, hd->S, blockIdx.x);
-  const RoiDesc& d = descs[s];
-  const int n = ((int)blockIdx.x - hd->first[s]) * kBlock + threadIdx.x;
-  double xmin = INFINITY, xmax = 0.0, ymin = INFINITY, ymax = 0.0;
-  if (n < d.a.N) roi_particle_box<T, SP>(d.a, (const SP*)d.prior, n, xmin, xmax, ymin, ymax);
-  roi_block_box(sh, xmin, xmax, ymin, ymax, part + 4 * (size_t)blockIdx.x);
-}
-// one block per stream: its partials -> box s of `out` (pinned, host-mapped: no copy back)
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_roi_multi_final(const RoiBatch* __restrict__ hd, const T* __restrict__ part,
-                                                           T* __restrict__ out) {
-  __shared__ double sh[4][kWaves];
-  const int s = blockIdx.x, b0 = hd->first[s];
-  roi_partials_box(sh, part + 4 * (size_t)b0, hd->first[s + 1] - b0, out + 4 * (size_t)s);
-}
-
-template <typename T>
-__global__ void k_weights_export(const T* __restrict__ w, double* __restrict__ out, int N) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  out[n] = (double)w[n];
-}
-
-// ---- cloud statistics (pfmpe_cloud_stats; the definition is in include/pfmpe.h): weighted sums of the particles'
-// twists about a reference pose.  fp64 throughout, for every state type.
-// Twist xi = [upsilon; omega] of D = T * ref^-1 (left perturbation T = exp(xi) * ref), logarithmMap's order
-// (PE:2228-2296).  The stored matrices are used as they are (no re-orthonormalisation).  1 - cos(phi) is formed as
-// 2 sin^2(phi / 2): the same number without the cancellation at small phi.  A pose bit-equal to the reference has
-// twist exactly 0 (R R^T of a stored R is the identity only up to rounding).  Shared by the kernel and the host
-// helper (pfmpe_host_pose_twist), built with -ffp-contract=off on both sides.
-__host__ __device__ inline void pose_twist(const double* T, const double* ref, double* xi) {
-  bool same = true;
-#pragma unroll
-  for (int q = 0; q < 12; ++q) same = same && (T[q] == ref[q]);
-  double DR[9], d[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {  // D_R = R_i R_r^T
-      double s = T[i * 4 + 0] * ref[j * 4 + 0];
-      s = s + T[i * 4 + 1] * ref[j * 4 + 1];
-      s = s + T[i * 4 + 2] * ref[j * 4 + 2];
-      DR[i * 3 + j] = s;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {  // d = t_i - D_R t_r
-    double s = DR[i * 3 + 0] * ref[3];
-    s = s + DR[i * 3 + 1] * ref[7];
-    s = s + DR[i * 3 + 2] * ref[11];
-    d[i] = T[i * 4 + 3] - s;
-  }
-  const double a0 = 0.5 * (DR[7] - DR[5]), a1 = 0.5 * (DR[2] - DR[6]), a2 = 0.5 * (DR[3] - DR[1]);
-  const double s = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
-  const double c = 0.5 * (((DR[0] + DR[4]) + DR[8]) - 1.0);
-  const double phi = atan2(s, c);
-  const double f = s > 1e-8 ? phi / s : 1.0 + (s * s) / 6.0;
-  const double w0 = f * a0, w1 = f * a1, w2 = f * a2;
-  const double sh = sin(0.5 * phi), p2 = phi * phi;
-  const double k = phi >= 1e-4 ? (1.0 - (phi * sin(phi)) / (2.0 * ((2.0 * sh) * sh))) / p2 : 1.0 / 12.0 + p2 / 720.0;
-  // upsilon = (I - 1/2 w^ + k w^ w^) d
-  const double c10 = w1 * d[2] - w2 * d[1], c11 = w2 * d[0] - w0 * d[2], c12 = w0 * d[1] - w1 * d[0];
-  const double c20 = w1 * c12 - w2 * c11, c21 = w2 * c10 - w0 * c12, c22 = w0 * c11 - w1 * c10;
-  xi[0] = same ? 0.0 : (d[0] - 0.5 * c10) + k * c20;
-  xi[1] = same ? 0.0 : (d[1] - 0.5 * c11) + k * c21;
-  xi[2] = same ? 0.0 : (d[2] - 0.5 * c12) + k * c22;
-  xi[3] = same ? 0.0 : w0;
-  xi[4] = same ? 0.0 : w1;
-  xi[5] = same ? 0.0 : w2;
-}
-
-// One partial row per block, kCloudWords doubles: sum w, sum w^2, sum w xi (6), the upper triangle of sum w xi xi^T
-// (21, row by row), max |upsilon|^2 and max |omega|^2 over particles with w > 0, one unused word.
-constexpr int kCloudWords = 32;
-constexpr int kCloudSums = 29;
-// The grid is a function of N alone (one N, one reduction tree): a block per 256 particles up to 1024 blocks (two
-// rounds of the resident grid: 256 CUs x 2 blocks at the kernel's ~210 VGPRs), grid-stride beyond.
-constexpr int kCloudMaxBlocks = 1024;
-inline int cloud_blocks(int N) {
-  const int b = (N + kBlock - 1) / kBlock;
-  return b < kCloudMaxBlocks ? b : kCloudMaxBlocks;
-}
-struct CloudArgs {
-  double ref[12], anchor[12];
-  int32_t N, pad;
-  int64_t ld;
-  const uint32_t* owner;  // a deferred prior's owner indices (FrameArgsT::owner), or null
-  const double* dense;    // DENSE: N x 12 poses (the regenerated kept set)
-  const void* w;          // DENSE: its raw weights (compute type T)
-};
-// DENSE = false: the resident prior through StateIO / the owner indices, exactly the rows k_export writes, unit
-// weights.  DENSE = true: N x 12 doubles with weights widened as k_weights_export widens them.  Each lane sums its
-// particles in index order; one DPP reduction per wave after the stride loop; the block's waves are added in wave
-// order through LDS.  No atomics, no waits on other blocks: k_cloud_final is a second launch.
-template <typename T, typename SP, bool DENSE>
-__global__ __launch_bounds__(kBlock) void k_cloud_partials(const CloudArgs ca, const SP* __restrict__ st,
-                                                          double* __restrict__ part) {
-  __shared__ double sh[kWaves][kCloudWords];
-  double acc[kCloudSums];
-#pragma unroll
-  for (int q = 0; q < kCloudSums; ++q) acc[q] = 0.0;
-  double mt = 0.0, mr = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t n = (int64_t)blockIdx.x * kBlock + threadIdx.x; n < ca.N; n += stride) {
-    double P[12], w = 1.0;
-    if constexpr (DENSE) {
-#pragma unroll
-      for (int q = 0; q < 12; ++q) P[q] = ca.dense[12 * n + q];
-      w = (double)((const T*)ca.w)[n];
-    } else {
-      const int64_t r = ca.owner ? (int64_t)ca.owner[n] : n;
-#pragma unroll
-      for (int q = 0; q < 12; ++q)
-        P[q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ca.ld)], (T)ca.anchor[q]);
-    }
-    double xi[6], wx[6];
-    pose_twist(P, ca.ref, xi);
-    acc[0] = acc[0] + w;
-    acc[1] = acc[1] + w * w;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      wx[q] = w * xi[q];
-      acc[2 + q] = acc[2 + q] + wx[q];
-    }
-    int k = 8;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = i; j < 6; ++j, ++k) acc[k] = acc[k] + wx[i] * xi[j];
-    const double t2 = (xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2];
-    const double r2 = (xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5];
-    mt = (w > 0.0 && t2 > mt) ? t2 : mt;
-    mr = (w > 0.0 && r2 > mr) ? r2 : mr;
-  }
-#pragma unroll
-  for (int q = 0; q < kCloudSums; ++q) acc[q] = lane_value(wave_incl_sum(acc[q]), 63);
-  mt = wave_max(mt);
-  mr = wave_max(mr);
-  const int wv = wave_id();
-  if (lane_id() == 0) {
-#pragma unroll
-    for (int q = 0; q < kCloudSums; ++q) sh[wv][q] = acc[q];
-    sh[wv][kCloudSums] = mt;
-    sh[wv][kCloudSums + 1] = mr;
-    sh[wv][kCloudSums + 2] = 0.0;
-  }
-  __syncthreads();
-  if (threadIdx.x < kCloudWords) {
-    const int q = threadIdx.x;
-    double v = sh[0][q];
-    for (int x = 1; x < kWaves; ++x) v = q < kCloudSums ? v + sh[x][q] : (sh[x][q] > v ? sh[x][q] : v);
-    part[(size_t)blockIdx.x * kCloudWords + q] = v;
-  }
-}
-// One block: word q of the result = the partial rows' word q combined in block order.  The rows are cut into
-// kCloudSegs runs of consecutive rows; 32 lanes per run add its rows in index order (16 loads in flight: one lane
-// walking all 1024 rows, a load's latency per row, took 50 us), then the runs are added in run order.  The tree
-// depends on nblk alone.  (0 is the identity of the sums and of the maxima, which are of squares.)
-constexpr int kCloudSegs = 8;
-template <typename V>  // (a template only for COMDAT linkage: the header is in several TUs)
-__global__ __launch_bounds__(kCloudSegs* kCloudWords) void k_cloud_final(const V* __restrict__ part, int nblk,
-                                                                        V* __restrict__ out) {
-  __shared__ V sh[kCloudSegs][kCloudWords];
-  const int q = threadIdx.x % kCloudWords, sg = threadIdx.x / kCloudWords;
-  const int per = (nblk + kCloudSegs - 1) / kCloudSegs;
-  const int b0 = sg * per, b1 = b0 + per < nblk ? b0 + per : nblk;
-  const bool sum = q < kCloudSums;
-  V v = 0;
-  int b = b0;
-  for (; b + 16 <= b1; b += 16) {
-    V x[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x[i] = part[(size_t)(b + i) * kCloudWords + q];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v = sum ? v + x[i] : (x[i] > v ? x[i] : v);
-  }
-  for (; b < b1; ++b) {
-    const V x = part[(size_t)b * kCloudWords + q];
-    v = sum ? v + x : (x > v ? x : v);
-  }
-  sh[sg][q] = v;
-  __syncthreads();
-  if (sg == 0) {
-    for (int s = 1; s < kCloudSegs; ++s) v = sum ? v + sh[s][q] : (sh[s][q] > v ? sh[s][q] : v);
-    out[q] = v;
-  }
-}
-
-// ---- LED-blob association of the cloud (pfmpe_assoc_stats / pfmpe_get_pairs; the definition is in include/pfmpe.h):
-// every particle's pairs by the weighing kernels' per-lane path (project_markers, the NaN-at-origin rule,
-// column_minima, score_minima<PAIRS>), then either one vote per pair into integer bins or the particle's row.
-struct AssocArgs {
-  const double* dense;   // DENSE: N x 12 poses (the regenerated kept set)
-  uint32_t* votes;       // votes mode: M x B bins (LED m + 1 with blob b + 1 at m * B + b), then the M + 1 bins of the
-                         // pair count; null: rows mode
-  uint32_t* corr;        // rows mode: 2 * kMaxMarkers words per particle of the range (16-byte aligned)
-  int32_t* n_corr;       // rows mode: its pair count
-  int32_t first, count;  // the particles first .. first + count - 1
-  int32_t lds_votes;     // votes mode: the block's bins in LDS behind the blob table, flushed once per block; 0: every
-                         // vote straight into `votes` (the bins do not fit beside the table)
-  int32_t pad;
-};
-// a block per 256 particles up to 1024 blocks (as cloud_blocks), grid-stride beyond
-constexpr int kAssocMaxBlocks = 1024;
-// the workgroup's LDS: the blob table, the bins and the frame constants must fit
-constexpr size_t kAssocLdsLimit = 64 * 1024;
-__host__ __device__ inline int assoc_bins(int M, int B) { return M * B + M + 1; }
-// DENSE = false: the resident prior through StateIO / the owner indices (fa.owner, fa.anc_in, fa.ld), exactly the
-// rows k_export writes.  DENSE = true: N x 12 doubles, narrowed to T (exact: they are widened T values).  The bins
-// are integers, so the order of the adds does not matter: returnless LDS adds per vote, then one device-scope add
-// per non-zero bin and block into the table the host cleared.  No waits on other blocks.
-template <typename T, typename SP, bool DENSE, int MAXM, bool PRUNE>
-__global__ __launch_bounds__(kBlock) void k_assoc_votes(const FrameArgsT<T> fa, const AssocArgs aa,
-                                                       const unsigned char* __restrict__ table,
-                                                       const SP* __restrict__ st) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ LdsConst<T> sc;
-  const int M = fa.M, B = fa.B;
-  const int nbins = assoc_bins(M, B);
-  const bool lds = aa.votes && aa.lds_votes;
-  uint32_t* bins = (uint32_t*)(smem + BlobTable<T>::lds_bytes((size_t)fa.tbytes));
-  copy_table(table, smem, (size_t)fa.tbytes);
-  stage_consts(fa, sc);
-  if (lds)
-    for (int i = threadIdx.x; i < nbins; i += kBlock) bins[i] = 0u;
-  __syncthreads();  // table, constants and cleared bins visible
-  const LdsBlobs<T> tb = view_table<T>(smem, B);
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < aa.count; i += stride) {
-    const int64_t n = (int64_t)aa.first + i;
-    T P[12];
-    if constexpr (DENSE) {
-#pragma unroll
-      for (int q = 0; q < 12; ++q) P[q] = (T)aa.dense[12 * n + q];
-    } else {
-      const int64_t r = fa.owner ? (int64_t)fa.owner[n] : n;
-#pragma unroll
-      for (int q = 0; q < 12; ++q) P[q] = StateIO<T, SP>::load(st[plane_index<SP>(q, r, fa.ld)], fa.anc_in[q]);
-    }
-    T u[MAXM], v[MAXM];
-    project_markers<T, MAXM>(fa, sc, P, u, v);
-    uint32_t pairs[2 * MAXM];
-#pragma unroll
-    for (int q = 0; q < 2 * MAXM; ++q) pairs[q] = 0u;
-    int np = 0;
-    if (B > 0 && !nan_at_origin_tb(fa, tb, u[0], v[0])) {  // else the step's likelihood short-circuits: no pairs
-      T m[MAXM];
-      int r[MAXM];
-      (void)column_minima<T, MAXM, PRUNE>(fa, u, v, tb, m, r);
-      (void)score_minima<T, MAXM, true>(fa, m, r, pairs, &np);
-    }
-    if (aa.votes) {
-      // each add through its own pointer (the LDS add as ds_add_u32 without a return value, not a flat atomic)
-      auto vote = [&](int idx) {
-        if (lds)
-          (void)__hip_atomic_fetch_add(bins + idx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        else
-          (void)__hip_atomic_fetch_add(aa.votes + idx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      };
-#pragma unroll
-      for (int k = 0; k < MAXM; ++k)
-        if (k < np) vote(((int)pairs[2 * k] - 1) * B + ((int)pairs[2 * k + 1] - 1));
-      vote(M * B + np);
-    } else {
-      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-      u32x4* row = (u32x4*)(aa.corr + (size_t)i * (2 * kMaxMarkers));
-#pragma unroll
-      for (int g = 0; g < 2 * kMaxMarkers / 4; ++g) {
-        u32x4 w = {0u, 0u, 0u, 0u};
-        if (4 * g < 2 * MAXM) {
-          w.x = pairs[4 * g];
-          w.y = pairs[4 * g + 1];
-        }
-        if (4 * g + 2 < 2 * MAXM) {
-          w.z = pairs[4 * g + 2];
-          w.w = pairs[4 * g + 3];
-        }
-        row[g] = w;
-      }
-      aa.n_corr[i] = np;
-    }
-  }
-  if (lds) {
-    __syncthreads();  // every wave's votes are in the bins
-    for (int i = threadIdx.x; i < nbins; i += kBlock) {
-      const uint32_t x = bins[i];
-      if (x) (void)__hip_atomic_fetch_add(aa.votes + i, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+template <typename T, int RNG, typename SP>
+__global__ __launch_bounds__(64) void k_top_multi(const StreamDesc<T, SP>* __restrict__ descs, int S,
+                                                  const uint32_t* __restrict__ status, uint32_t gen, int iter) {
+  const int s = (int)blockIdx.x;
+  if (s >= S || __builtin_amdgcn_readfirstlane(status[s]) != gen) return;
+  const StreamDesc<T, SP>& d = descs[s];
+  top_body<T, RNG>(d.fa, d.gpart0, d.gpart1, d.gscan, d.ctrl, iter, 0, nullptr);
 }
 
 }  // namespace pfmpe
-
-#include "pf_weigh_pk.hpp"

@@ -3,7 +3,7 @@
 // Same job, same outputs and the same bits as k_weigh_stream (pf_kernels.hpp; PE:543-604: motion model,
 // project2d, calculateEstimationProbability), for the frames the throughput configurations run: fp32 compute,
 // the Philox stream, exactly 5 markers, the 2D blob grid, small motion angles, an identity camMoveInv, an
-// upper-triangular K and at least as many blobs as markers (the host checks: pk_eligible in pfmpe_ctx.hpp;
+// upper-triangular K and at least as many blobs as markers (the host checks: pk_eligible in pfmpe_seq.hpp;
 // every other frame takes k_weigh_stream).
 //
 // Why: k_weigh_stream is VALU-issue bound (C4: 486 VALU per particle at ~4.3 cycles per wave instruction,
@@ -242,7 +242,7 @@ __device__ __forceinline__ void pk_wave_partial(float w, bool valid, bool full, 
     const uint64_t bx = __builtin_amdgcn_ballot_w64(__float_as_int(w) == mxb);
     const int ix = nbase + (int)__builtin_ctzll(bx);
     // the total: with every weight below 32 (the usual case: at most 5 * 6), as integers on the 2^-21 grid every
-    // weight of this pass lies on (wave_incl_sum_fx, pf_kernels.hpp): the exact sum, which is what the fp64
+    // weight of this pass lies on (wave_incl_sum_fx, pf_wave.hpp): the exact sum, which is what the fp64
     // butterfly yields too (its partial sums need at most 32 significant bits)
     double wi;
     if (mxb < 0x42000000) {  // 32.0f; a scalar branch
@@ -926,63 +926,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PFMPE_WE
   if ((int)blockIdx.x >= nwg) return;
   weigh_pk_body<SP, true>(d.fa, (const uint32_t*)&d.fa, (int)blockIdx.x, nwg, d.table, d.prior, d.w0, d.w1, d.part0,
                           d.part1, d.ctrl, d.prop0, d.prop1, iter, smem, sc, pl);
-}
-
-// ---- the batched streaming pass's group / top hand-off (k_group_top / k_group + k_top_wide / k_top of every
-// stream of the batch, one launch each): grid (max groups, streams) for the group scans, (streams) for the tops.
-// The bodies are the one-stream kernels' (same functions, same association), with the stream's frame arguments,
-// buffers and counters from its descriptor; blocks past a stream's groups, and streams that failed the staging
-// check, return at once.
-template <typename T, int RNG, typename SP>
-__global__ __launch_bounds__(64) void k_group_top_multi(const StreamDesc<T, SP>* __restrict__ descs, int S,
-                                                        const uint32_t* __restrict__ status, uint32_t gen, int iter) {
-  const int s = (int)blockIdx.y;
-  if (s >= S || __builtin_amdgcn_readfirstlane(status[s]) != gen) return;
-  const StreamDesc<T, SP>& d = descs[s];
-  const int g = (int)blockIdx.x;
-  const int ngrp = __builtin_amdgcn_readfirstlane(d.fa.ngrp);
-  if (g >= ngrp) return;
-  Ctrl* ctrl = d.ctrl;
-  if (load_ctrl_word<(int)offsetof(Ctrl, done)>(ctrl)) return;  // every block reads ctrl before it arrives
-  const int slot = load_ctrl_word<(int)offsetof(Ctrl, cur_slot)>(ctrl);
-  const GroupPart gr = propagate_group<true>(__builtin_amdgcn_readfirstlane(d.fa.nblk), __builtin_amdgcn_readfirstlane(d.fa.gsz),
-                                             g, slot ? d.part1 : d.part0, slot ? d.bscan1 : d.bscan0,
-                                             slot ? d.gpart1 : d.gpart0);
-  const bool single = ngrp == 1;
-  if (!single && !wave_arrive_last(d.tcount_w, ngrp)) return;
-  propagate_top<T, RNG>(d.fa, ctrl, iter, d.gpart0, d.gpart1, d.gscan, nullptr, 0u, gr, single, slot);
-}
-template <typename T, typename SP>
-__global__ __launch_bounds__(64) void k_group_multi(const StreamDesc<T, SP>* __restrict__ descs, int S,
-                                                    const uint32_t* __restrict__ status, uint32_t gen) {
-  const int s = (int)blockIdx.y;
-  if (s >= S || __builtin_amdgcn_readfirstlane(status[s]) != gen) return;
-  const StreamDesc<T, SP>& d = descs[s];
-  const int g = (int)blockIdx.x;
-  if (g >= __builtin_amdgcn_readfirstlane(d.fa.ngrp)) return;
-  if (load_ctrl_word<(int)offsetof(Ctrl, done)>(d.ctrl)) return;
-  const int slot = load_ctrl_word<(int)offsetof(Ctrl, cur_slot)>(d.ctrl);
-  (void)propagate_group<true>(__builtin_amdgcn_readfirstlane(d.fa.nblk), __builtin_amdgcn_readfirstlane(d.fa.gsz), g,
-                              slot ? d.part1 : d.part0, slot ? d.bscan1 : d.bscan0, slot ? d.gpart1 : d.gpart0);
-}
-template <typename T, int RNG, typename SP>
-__global__ __launch_bounds__(64 * kTopWaves) void k_top_wide_multi(const StreamDesc<T, SP>* __restrict__ descs, int S,
-                                                                const uint32_t* __restrict__ status, uint32_t gen,
-                                                                int iter) {
-  extern __shared__ __attribute__((aligned(16))) GroupPart gsm[];  // the largest stream's ngrp entries
-  __shared__ TopWideLds tw;
-  const int s = (int)blockIdx.x;
-  if (s >= S || __builtin_amdgcn_readfirstlane(status[s]) != gen) return;
-  const StreamDesc<T, SP>& d = descs[s];
-  top_wide_body<T, RNG>(d.fa, d.gpart0, d.gpart1, d.gscan, d.ctrl, iter, gsm, tw);
-}
-template <typename T, int RNG, typename SP>
-__global__ __launch_bounds__(64) void k_top_multi(const StreamDesc<T, SP>* __restrict__ descs, int S,
-                                                  const uint32_t* __restrict__ status, uint32_t gen, int iter) {
-  const int s = (int)blockIdx.x;
-  if (s >= S || __builtin_amdgcn_readfirstlane(status[s]) != gen) return;
-  const StreamDesc<T, SP>& d = descs[s];
-  top_body<T, RNG>(d.fa, d.gpart0, d.gpart1, d.gscan, d.ctrl, iter, 0, nullptr);
 }
 
 }  // namespace pfmpe

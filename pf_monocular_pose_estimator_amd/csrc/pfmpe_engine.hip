@@ -1,25 +1,24 @@
 // pfmpe_engine.hip — host side of the MI355X PF engine: context, buffers, C-ABI (include/pfmpe.h).
 //
 // Replaces the PF block of PoseEstimator::estimateBodyPose (pf_mpe_lib/src/pose_estimator.cpp:475-733).
-// The launch sequences live in pfmpe_ctx.hpp (Seq) and are instantiated per (state type, RNG) in the
-// pfmpe_k_*.hip translation units.
-#include "pfmpe_prior.hpp"
+// The launch sequences live in pfmpe_seq.hpp (Seq) and are instantiated per (state type, RNG) in the
+// pfmpe_k_*.hip translation units; this unit launches the side calls' kernels and builds the blob tables.
+#include "pf_cloud.hpp"
 #include "pf_gn.hpp"
+#include "pf_likelihood.hpp"
+#include "pf_roi.hpp"
+#include "pfmpe_prior.hpp"
 
-using namespace pfmpe;
 using namespace pfmpe_impl;
 
-namespace pfmpe_impl {
 PFMPE_DECLARE_INSTANCE(float, kRngReference, float, extern)
 PFMPE_DECLARE_INSTANCE(float, kRngPhilox, float, extern)
 PFMPE_DECLARE_INSTANCE(double, kRngReference, double, extern)
 PFMPE_DECLARE_INSTANCE(double, kRngPhilox, double, extern)
 PFMPE_DECLARE_INSTANCE(float, kRngReference, __half, extern)
 PFMPE_DECLARE_INSTANCE(float, kRngPhilox, __half, extern)
-}  // namespace pfmpe_impl
 
 namespace {
-using namespace pfmpe_impl;
 
 int dispatch_step(pfmpe_ctx* c, const pfmpe_frame_in* in, const unsigned char* table, size_t tbytes,
                   const GridHdr& gh) {
@@ -154,7 +153,7 @@ int pfmpe_create(pfmpe_ctx** out, int hip_device, int max_particles, int max_mar
 
   c->max_blk = (max_particles + kBlock - 1) / kBlock;
   // fp32 / fp16 planes are addressed through one 32-bit buffer resource per state buffer
-  // (pf_kernels.hpp BufPlanes): 12 planes must stay below 4 GiB (89M fp32 / 178M fp16 particles)
+  // (pf_state.hpp BufPlanes): 12 planes must stay below 4 GiB (89M fp32 / 178M fp16 particles)
   if (state_dtype != PFMPE_STATE_F64 && (int64_t)kPlanes * c->ld * (int64_t)c->es >= ((int64_t)1 << 32)) {
     delete c;
     return PFMPE_E_CAP;

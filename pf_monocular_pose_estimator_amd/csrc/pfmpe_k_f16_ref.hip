@@ -8,9 +8,6 @@
 #ifndef PFMPE_WEIGH_MIN_WAVES
 #define PFMPE_WEIGH_MIN_WAVES 6  // k_propagate_weigh: >= 6 waves per SIMD (12/16-marker instances)
 #endif
-#include "pfmpe_ctx.hpp"
+#include "pfmpe_seq.hpp"
 
-namespace pfmpe_impl {
-using namespace pfmpe;
 PFMPE_DECLARE_INSTANCE(float, kRngReference, __half, )
-}  // namespace pfmpe_impl

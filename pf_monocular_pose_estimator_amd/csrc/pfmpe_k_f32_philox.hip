@@ -14,9 +14,6 @@
 #ifndef PFMPE_WEIGH_PK_MIN_WAVES
 #define PFMPE_WEIGH_PK_MIN_WAVES 4  // k_weigh_pk<float>: 4 waves per SIMD (135 -> 128 VGPRs, no scratch)
 #endif
-#include "pfmpe_ctx.hpp"
+#include "pfmpe_seq.hpp"
 
-namespace pfmpe_impl {
-using namespace pfmpe;
 PFMPE_DECLARE_INSTANCE(float, kRngPhilox, float, )
-}  // namespace pfmpe_impl

@@ -1,8 +1,37 @@
 #pragma once
 // pfmpe_prior.hpp — the resident particle set to and from the transfer buffer d_xfer (N x 12 doubles), for the
 // three storage types.  Included only by the translation units that move particle sets (pfmpe_engine.hip,
-// pfmpe_init.hip): each of them instantiates k_import / k_export.
+// pfmpe_init.hip): each of them instantiates k_import / k_export, which are defined here.
+#include "pf_state.hpp"
 #include "pfmpe_ctx.hpp"
+
+namespace pfmpe {
+
+// ---- state import / export (API helpers, not on the timed path).  anchor: the set's
+// anchor pose (fp16 state), ignored for fp32 / fp64 planes.
+template <typename T>
+struct Pose12 {
+  T v[12];
+};
+template <typename T, typename SP>
+__global__ void k_import(const double* __restrict__ poses, SP* __restrict__ st, int N, int64_t ld,
+                         const Pose12<T> anchor) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  for (int q = 0; q < 12; ++q)
+    st[plane_index<SP>(q, n, ld)] = StateIO<T, SP>::store((T)poses[12 * (int64_t)n + q], anchor.v[q]);
+}
+template <typename T, typename SP>
+__global__ void k_export(const SP* __restrict__ st, double* __restrict__ poses, int N, int64_t ld,
+                         const Pose12<T> anchor, const uint32_t* __restrict__ owner) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const int r = owner ? (int)owner[n] : n;  // a deferred prior: stored row owner[n]
+  for (int q = 0; q < 12; ++q)
+    poses[12 * (int64_t)n + q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ld)], anchor.v[q]);
+}
+
+}  // namespace pfmpe
 
 namespace pfmpe_impl {
 

@@ -1,11 +1,11 @@
 // pfmpe_refine.hip — k_refine / k_refine_fold (pfmpe_refine_poses / pfmpe_refine_cloud) and their launch: Gauss-Newton
 // (pf_gn.hpp) of one hypothesis per lane, fp64 for every state type, and the call's summary.  A TU of its own so it
 // builds beside the others.
-#include "pfmpe_ctx.hpp"
 #include "pf_gn.hpp"
+#include "pf_wave.hpp"
+#include "pfmpe_ctx.hpp"
 
 namespace pfmpe_impl {
-using namespace pfmpe;
 
 namespace {
 constexpr int kWave = 64;

@@ -1,4 +1,4 @@
-/* div_by_S (csrc/pf_kernels.hpp) against IEEE division: fl(a / b) from y = fl(1 / b), q0 = fl(a y) and two fma
+/* div_by_S (csrc/pf_wave.hpp) against IEEE division: fl(a / b) from y = fl(1 / b), q0 = fl(a y) and two fma
    corrections.  Cases: quotients in [0, 1] over wide exponent ranges, decimal-like numerators, sums on the 2^-21
    grid of fp32 scores (the k_resample case), and numerators just below b.  Exit status 1 on any mismatch. */
 #include <math.h>

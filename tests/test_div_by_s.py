@@ -1,4 +1,4 @@
-"""div_by_S (pf_kernels.hpp, k_resample's normalised cumulative weights) equals IEEE fp64 division: the C restatement
+"""div_by_S (pf_wave.hpp, k_resample's normalised cumulative weights) equals IEEE fp64 division: the C restatement
 in tests/div_by_s_check.c, built with gcc (-ffp-contract=off, libm fma), over 10^7 cases of the shapes k_resample
 divides (quotients in [0, 1]; sums on the 2^-21 grid of fp32 scores; numerators just below S)."""
 import os

@@ -1,4 +1,4 @@
-"""The fixed-point wave sums of k_resample / k_weigh_pk (pf_kernels.hpp wave_incl_sum_fx, pf_weigh_pk.hpp
+"""The fixed-point wave sums of k_resample / k_weigh_pk (pf_wave.hpp wave_incl_sum_fx, pf_weigh_pk.hpp
 pk_wave_partial) against the fp64 DPP scan they replace, in numpy.
 
 Claim: every fp32 weight of an M >= 4 frame is a multiple of 2^-21 (its score terms Mt + q^2 are >= 4 and the
@@ -11,7 +11,7 @@ F = np.float32
 
 
 def scores(rng, n, m=5, tol=F(3.0), tol_pf=F(4.0), downgrade=0b00100):
-    """score_unordered (pf_kernels.hpp) in fp32: accepted markers add Mt + q^2, then the penalties."""
+    """score_unordered (pf_likelihood.hpp) in fp32: accepted markers add Mt + q^2, then the penalties."""
     d = rng.uniform(0.0, 5.0, size=(n, m)).astype(F)
     d[rng.random((n, m)) < 0.1] = F(np.inf)
     blob = rng.integers(0, 6, size=(n, m))

@@ -1,5 +1,5 @@
 """Cell lists longer than one in the one-launch frame (k_frame2's column minima in phases over the markers,
-DESIGN.md §4.2c; pf_kernels.hpp column_minima<..., PHASED>).
+DESIGN.md §4.2c; pf_likelihood.hpp column_minima<..., PHASED>).
 
 Every blob gets a twin 0.25-0.4 px away on each axis, so the cells around a blob list its twin too and a marker
 that projects near a blob walks a list of two or more: the phased form's rare path.  The pruned one-launch frame

@@ -207,7 +207,7 @@ def test_owners_dominant_particles(state, N, doms):
 def test_owners_abandoned_finish_leaves_no_state():
     """A two-launch frame whose finishing wave gives up (PFMPE_DIAG 131072, as if the wait bound expired) returns an
     error without a record and leaves the winner keys and arrival shards set; the host zeroes them
-    (reset_handoffs, pfmpe_ctx.hpp), so the next frame, a different one, equals the same frame on an engine that
+    (reset_handoffs, pfmpe_seq.hpp), so the next frame, a different one, equals the same frame on an engine that
     never saw the failure (its finisher would otherwise stop polling early and count the failed frame's keys)."""
     N = 100_003
     st = syn.make_stream(syn.StreamConfig("t", M=5, B=50, N=N), 3)

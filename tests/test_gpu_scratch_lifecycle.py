@@ -10,7 +10,7 @@ any context) must be back where it was: device free-memory readings cannot tell 
 Shapes are the smallest that reach each path: M = 5, B = 8, N = 300 (two blocks, the second partial).
 
 step_multi's batch scratch starts at 64 KiB and holds one descriptor per stream, so it only grows with the stream
-count: the smallest count whose need (batch_layout, csrc/pfmpe_ctx.hpp, mirrored in batch_need below) exceeds 64 KiB
+count: the smallest count whose need (batch_layout, csrc/pfmpe_seq.hpp, mirrored in batch_need below) exceeds 64 KiB
 is 58 one-block streams for fp32 / fp16 state and 38 for fp64, within the 64 streams of 256 particles a test may
 spend, so that growth is driven too (every stream reads a staged bank frame: the need then depends on nothing else).
 

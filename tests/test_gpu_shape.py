@@ -1,7 +1,7 @@
 """GPU: the frame shape the engine actually runs.
 
 A one-launch frame needs every block resident at once; a kernel whose registers grow past the residency
-rule (csrc/pfmpe_ctx.hpp frame_fused: at most 2 blocks per CU, one below the occupancy answer) silently
+rule (csrc/pfmpe_seq.hpp frame_fused: at most 2 blocks per CU, one below the occupancy answer) silently
 takes the two-launch path, which is correct but slower.  These tests pin the shape at the sizes the
 bench and the scale configs use, for every state precision: the default (k_frame2) and the tree frame
 must run as ONE launch up to 512 blocks, and the two-launch path above.

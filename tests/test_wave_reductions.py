@@ -1,4 +1,4 @@
-"""The integer wave reductions of pf_kernels.hpp, simulated lane by lane in numpy (no GPU).
+"""The integer wave reductions of pf_wave.hpp, simulated lane by lane in numpy (no GPU).
 
 * The reduction pattern of wave_argmin_dist / the winner-key maxima: quad_perm [1,0,3,2], quad_perm [2,3,0,1],
   row_half_mirror, row_mirror, then row_bcast15 (rows 1, 3) and row_bcast31 (rows 2, 3).  Lane 63 ends with the
