@@ -251,6 +251,60 @@ int pfmpe_p3p_histogram(pfmpe_ctx* ctx, const double* blobs, int B, uint32_t* hi
 int pfmpe_initialise(pfmpe_ctx* ctx, const double* blobs, int B, const pfmpe_init_params* params,
                      pfmpe_init_out* out, uint32_t* hist);
 
+#define PFMPE_INIT_MAX_STREAMS 64
+
+/* The single call above for S contexts as one batch (the numUAV loop, PE:89, in the branch it_since_initialized_ < 1,
+ * PE:128-205: every object on the first frame, any number of them after a shared occlusion): one upload, one launch
+ * sequence and one synchronise per stage, three synchronises per batch where S single calls make 3 x S.  in[s],
+ * params[s] (params = NULL: the defaults for all), out[s] and hist[s] (hist = NULL or hist[s] = NULL: not wanted, else
+ * B_s x M_s) belong to ctxs[s].  out[s], hist[s] and the particle set of ctxs[s] afterwards are what
+ * pfmpe_initialise(ctxs[s], in[s].blobs, in[s].B, &params[s], &out[s], hist[s]) gives: out[s] byte for byte
+ * (predicted_pose included), the histogram entry for entry, the seeded prior the same bits from
+ * pfmpe_get_particles(ctxs[s], 1, ...); the counts are order-free integer sums of per-item decisions and the host
+ * stages are the same code on the same inputs.  Per stream: M, the markers, K and params.tol (from the context), B,
+ * every field of params[s], and N by the single call's rule.  Contexts of any state types may be mixed (the device
+ * stages are fp64, only the final import is typed); they must be distinct and on one device.  ctxs[0] leads: the
+ * batch runs on its stream and in its initialisation scratch (grown once per stage to the batch's size), fills its
+ * last-error text, and with PFMPE_OPT_TIMING on ctxs[0] is one PFMPE_K_P3P_HIST bracket and one PFMPE_K_P3P_CHECK
+ * bracket of ctxs[0] (nothing is added to another context's statistics).  Work a member has pending on its own stream
+ * is ordered before the batch; blocking, so nothing of the batch is pending when it returns.  A stream that is not
+ * found (B < M: flag 10; an empty histogram: 12; no candidate: 11 / 6 / 7 / 8 / 9) keeps its particle set untouched
+ * and does not affect the other streams; hist[s] is not written for a stream with B < M.
+ * Everything is checked before anything is staged or launched; on such an error out and hist are untouched and no
+ * context's state changes: PFMPE_E_ARG (S < 1, NULL ctxs / in / out / ctxs[s], a context twice, a device mismatch,
+ * B < 0, NULL blobs with B > 0, M < 3), PFMPE_E_CAP (S > PFMPE_INIT_MAX_STREAMS, a stream's B > max_blobs,
+ * n_particles > max_particles), PFMPE_E_STATE (a stream without a model); the text, "initialise_multi: stream <s>:
+ * ...", is the last-error text of ctxs[0].  With ctxs = NULL or ctxs[0] = NULL: PFMPE_E_ARG, no text.
+ * A candidate explosion is a run-time result, found after stage 1: when the correspondence vectors of stream s exceed
+ * its max_candidates the call returns PFMPE_E_CAP with the same "stream <s>: " prefix.  By then the histograms of
+ * stage 1 have been written to hist (every stream with B >= M); out is untouched and no context is seeded. */
+typedef struct {
+  const double* blobs;   /* B x 2 undistorted px (image_points_), host pointer; may be NULL when B == 0 */
+  int32_t B;
+  int32_t pad;
+} pfmpe_init_in;         /* 16 bytes */
+int pfmpe_initialise_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_init_in* in, const pfmpe_init_params* params,
+                           pfmpe_init_out* out, uint32_t* const* hist);
+
+/* host-only (no GPU, no context): the work mapping of the batch's histogram stage, which the call above launches
+ * exactly.  Streams are grouped by the unused-marker bucket of their M (one launch per bucket present).  A stream
+ * wants ceil(items / 256) blocks of 256 threads; a bucket's launch holds at most 8 * max(num_cu, 1) blocks, the single
+ * call's cap; when the wants of a bucket exceed it, stream s gets floor(want_s * cap / wants) blocks, and one block
+ * where that is zero, so the launch exceeds the cap by at most one block per stream with work.  Block b (counted from
+ * first_block) of a stream with `blocks` blocks visits the items b * 256 + t + k * blocks * 256 (thread t, round k).
+ * blocks_per_bucket: the three launches' sizes (0: no launch).  PFMPE_E_ARG for a NULL pointer, S outside
+ * 1..PFMPE_INIT_MAX_STREAMS, M outside 3..PFMPE_MAX_MARKERS or B < 0, PFMPE_E_CAP for B > PFMPE_MAX_BLOBS; the
+ * outputs are untouched then. */
+typedef struct {
+  int64_t items;        /* C(B,3) * M(M-1)(M-2); 0 when B < M or B < 3                                   */
+  int32_t first_block;  /* first block of this stream in its launch                                      */
+  int32_t blocks;       /* blocks given to it (0 when items == 0)                                        */
+  int32_t bucket;       /* 0 / 1 / 2: the unused-marker bucket (M - 3 <= 2, <= 9, else)                  */
+  int32_t lds_hist;     /* 1: histogram in LDS (B * M * 4 <= 32 KiB), 0: global atomics                  */
+} pfmpe_init_plan;      /* 24 bytes */
+int pfmpe_host_init_plan(const int32_t* M, const int32_t* B, int S, int num_cu, pfmpe_init_plan* plan,
+                         int32_t* blocks_per_bucket);
+
 /* ---------------------------------------------------------------- LED detector (§8f row 4) */
 /* LEDDetector::findLeds (pf_mpe_lib/src/led_detector.cpp:46-215) on the device for one ROI of an 8-bit
  * grey image: threshold (THRESH_TOZERO for active markers, else THRESH_BINARY_INV), GaussianBlur (ksize
@@ -620,7 +674,8 @@ enum { PFMPE_INFO_FUSED = 1,            /* current one-launch mode (0/1/2; 0 aft
        PFMPE_INFO_LAST_WEIGH_PASS = 6,  /* PFMPE_WEIGH_* of the last two-launch weighing (-1: none)  */
        PFMPE_INFO_LAST_GRID = 7,        /* 1: the last frame's blob table searched its cell grid; 0: the
                                          * x-buckets (no grid for this table or its window; fp64)    */
-       PFMPE_INFO_LAST_RESAMPLE = 8 };  /* PFMPE_RESAMPLE_* of the last two-launch resampling (-1: none) */
+       PFMPE_INFO_LAST_RESAMPLE = 8,    /* PFMPE_RESAMPLE_* of the last two-launch resampling (-1: none) */
+       PFMPE_INFO_NUM_CU = 9 };         /* compute units of the context's device (pfmpe_host_init_plan's num_cu) */
 /* The two-launch shape's weighing pass: one block per 256 particles (k_propagate_weigh), or
  * resident blocks streaming over them with the next block's state prefetched (k_weigh_stream + k_group +
  * k_top), or the streaming pass with two particles per lane in packed fp32 (k_weigh_pk: 5 markers, fp32 / fp16

@@ -20,6 +20,7 @@ from ._capi import (  # noqa: F401
     DETECT_MAX_ROIS, DetectParams, DetectOut, host_grow_roi,
     ROI_MAX_STREAMS, RoiIn, RoiOut, host_predict_roi,
     DETECT_MAX_IMAGES, DIAG_DET_COPY, DetectImage, DetectCrop, host_detect_plan, host_detect_pack,
+    INIT_MAX_STREAMS, INFO_NUM_CU, InitIn, InitPlan, InitParams, InitOut, host_init_plan,
 )
 
 __all__ = [

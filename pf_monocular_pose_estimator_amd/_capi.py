@@ -31,7 +31,7 @@ DIAG_ASSOC_DIRECT = 262144  # assoc_stats: every vote straight into the device t
 OPT_DEFER_RESAMPLE = 9
 SHAPE_TWO_LAUNCH, SHAPE_FRAME, SHAPE_FRAME2 = 0, 1, 2
 INFO_FUSED, INFO_FUSED_FALLBACKS, INFO_LAST_SHAPE, INFO_GUARD_SKIPS, INFO_N, INFO_LAST_WEIGH_PASS = 1, 2, 3, 4, 5, 6
-INFO_LAST_GRID, INFO_LAST_RESAMPLE = 7, 8
+INFO_LAST_GRID, INFO_LAST_RESAMPLE, INFO_NUM_CU = 7, 8, 9
 WEIGH_BLOCKS, WEIGH_STREAM, WEIGH_PK = 0, 1, 2
 RESAMPLE_BLOCKS, RESAMPLE_OWNERS = 0, 1
 CLOUD_WEIGHTED, CLOUD_POSTERIOR = 0, 1
@@ -56,10 +56,12 @@ EXPORTED_SYMBOLS = (
     "pfmpe_find_leds_multi", "pfmpe_host_grow_roi",
     "pfmpe_predict_roi_multi", "pfmpe_host_predict_roi",
     "pfmpe_find_leds_streams", "pfmpe_host_detect_plan", "pfmpe_host_detect_pack",
+    "pfmpe_initialise_multi", "pfmpe_host_init_plan",
 )
 DETECT_MAX_ROIS = 64
 DETECT_MAX_IMAGES = 64
 ROI_MAX_STREAMS = 64
+INIT_MAX_STREAMS = 64
 
 
 class Params(C.Structure):
@@ -112,6 +114,18 @@ class InitOut(C.Structure):
                 "n_candidates": self.n_candidates, "first_match": self.first_match,
                 "pairs": np.array(self.corr[: 2 * self.n_corr], dtype=np.uint32).reshape(-1, 2),
                 "predicted_pose": np.array(self.predicted_pose), "hist_total": self.hist_total}
+
+
+class InitIn(C.Structure):
+    _fields_ = [("blobs", C.POINTER(C.c_double)), ("B", C.c_int32), ("pad", C.c_int32)]
+
+
+class InitPlan(C.Structure):
+    _fields_ = [("items", C.c_int64), ("first_block", C.c_int32), ("blocks", C.c_int32), ("bucket", C.c_int32),
+                ("lds_hist", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class DetectParams(C.Structure):
@@ -281,6 +295,10 @@ def load() -> C.CDLL:
         "pfmpe_default_init_params": (None, [C.POINTER(InitParams)]),
         "pfmpe_p3p_histogram": (I, [P, dp, I, C.POINTER(C.c_uint32)]),
         "pfmpe_initialise": (I, [P, dp, I, C.POINTER(InitParams), C.POINTER(InitOut), C.POINTER(C.c_uint32)]),
+        "pfmpe_initialise_multi": (I, [C.POINTER(P), I, C.POINTER(InitIn), C.POINTER(InitParams), C.POINTER(InitOut),
+                                       C.POINTER(C.POINTER(C.c_uint32))]),
+        "pfmpe_host_init_plan": (I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, I, C.POINTER(InitPlan),
+                                     C.POINTER(C.c_int32)]),
         "pfmpe_parse_marker_yaml": (I, [C.c_char_p, dp, I]),
         "pfmpe_default_launch_config": (None, [C.POINTER(LaunchConfig)]),
         "pfmpe_parse_launch": (I, [C.c_char_p, C.POINTER(LaunchConfig)]),
@@ -526,6 +544,52 @@ class Engine:
             self.N = int(n_particles) if n_particles else (self.N or self.max_particles)
             self._last_out = None
         return d, h
+
+    @staticmethod
+    def initialise_multi(engines, blobs_list, n_particles=0, certainty_threshold=1.0, valid_corr_threshold=0.5,
+                         max_candidates=1 << 20, want_hist=True) -> list:
+        """PoseEstimator::initialise of every engine as ONE batch on the device (pfmpe_initialise_multi): blobs_list[s]
+        belongs to engines[s]; the four parameters are one value for all or one per engine.  Returns one
+        (out dict, histogram) per engine, each what engines[s].initialise returns (the histogram is None with
+        want_hist=False, and all zeros for a stream with fewer blobs than markers).  A PFError carries the histogram
+        arrays as .hist: after a candidate explosion (E_CAP) they hold stage 1's result."""
+        S = len(engines)
+        if S != len(blobs_list) or S == 0:
+            raise ValueError("initialise_multi: one blob list per engine")
+
+        def per(v):
+            return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * S
+
+        lib = engines[0].lib
+        ctxs = (C.c_void_p * S)(*[e.ctx.value for e in engines])
+        bl = [np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2) for b in blobs_list]
+        ins, ips, outs = (InitIn * S)(), (InitParams * S)(), (InitOut * S)()
+        nps = [int(v) for v in per(n_particles)]
+        for s in range(S):
+            ins[s].blobs = _dptr(bl[s]) if bl[s].shape[0] else C.POINTER(C.c_double)()
+            ins[s].B = bl[s].shape[0]
+            lib.pfmpe_default_init_params(C.byref(ips[s]))
+            ips[s].certainty_threshold = per(certainty_threshold)[s]
+            ips[s].valid_corr_threshold = per(valid_corr_threshold)[s]
+            ips[s].n_particles = nps[s]
+            ips[s].max_candidates = int(per(max_candidates)[s])
+        hs = [np.zeros((bl[s].shape[0], engines[s].M), dtype=np.uint32) if want_hist else None for s in range(S)]
+        hp = None
+        if want_hist:
+            hp = (C.POINTER(C.c_uint32) * S)(*[h.ctypes.data_as(C.POINTER(C.c_uint32)) for h in hs])
+        try:
+            engines[0]._chk(lib.pfmpe_initialise_multi(ctxs, S, ins, ips, outs, hp))
+        except PFError as e:
+            e.hist = hs  # a candidate explosion (E_CAP after stage 1) leaves stage 1's histograms here
+            raise
+        res = []
+        for s, e in enumerate(engines):
+            d = outs[s].as_dict()
+            if d["found"]:
+                e.N = nps[s] if nps[s] else (e.N or e.max_particles)
+                e._last_out = None
+            res.append((d, hs[s]))
+        return res
 
     def stage_image(self, image: np.ndarray):
         img = np.ascontiguousarray(image, dtype=np.uint8)
@@ -993,6 +1057,23 @@ def host_detect_pack(images, image_of, rois, crops=None, buffer_bytes=None) -> n
     if rc != OK:
         raise PFError(rc, "host_detect_pack: bad batch, crops that are not its plan, or a buffer too small")
     return buf[: int(buffer_bytes)]
+
+
+def host_init_plan(M, B, num_cu: int) -> tuple:
+    """pfmpe_host_init_plan: the work mapping of an initialise_multi batch's histogram stage.  M, B: markers and blobs
+    per stream.  Returns (one dict per stream: items, first_block, blocks, bucket, lds_hist; blocks_per_bucket)."""
+    m = np.ascontiguousarray(M, dtype=np.int32).reshape(-1)
+    b = np.ascontiguousarray(B, dtype=np.int32).reshape(-1)
+    if m.shape != b.shape:
+        raise ValueError("host_init_plan: one M and one B per stream")
+    S = int(m.shape[0])
+    plan = (InitPlan * max(S, 1))()
+    per_bucket = (C.c_int32 * 3)()
+    i32 = C.POINTER(C.c_int32)
+    rc = load().pfmpe_host_init_plan(m.ctypes.data_as(i32), b.ctypes.data_as(i32), S, int(num_cu), plan, per_bucket)
+    if rc != OK:
+        raise PFError(rc, "pfmpe_host_init_plan")
+    return [plan[s].as_dict() for s in range(S)], list(per_bucket)
 
 
 def host_grow_roi(roi, margin: int, image_w: int, image_h: int) -> tuple:

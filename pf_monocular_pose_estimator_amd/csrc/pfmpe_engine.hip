@@ -1182,6 +1182,7 @@ int pfmpe_get_info(const pfmpe_ctx* c, int key, int64_t* value) {
     case PFMPE_INFO_LAST_GRID: *value = c->last_grid; return PFMPE_OK;
     case PFMPE_INFO_GUARD_SKIPS: *value = c->guard_skips; return PFMPE_OK;
     case PFMPE_INFO_N: *value = c->N; return PFMPE_OK;
+    case PFMPE_INFO_NUM_CU: *value = c->num_cu; return PFMPE_OK;
     case 110: case 111: case 112: case 113: *value = c->mt_ns[key - 110]; return PFMPE_OK;  // batch host timing
     case 114: *value = c->mt_batches; return PFMPE_OK;
     case 115: *value = live_blocks().load(); return PFMPE_OK;  // buffers alive in this process (any context)

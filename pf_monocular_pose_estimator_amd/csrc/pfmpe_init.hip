@@ -17,6 +17,11 @@
 // Integer histogram increments are commutative, so the device enumerates combinations in colex order
 // and marker triples in any order; the reference's lexicographic order only matters for
 // checkCorrespondences (particle slot order), which keeps it.
+//
+// pfmpe_initialise_multi runs the same stages for S contexts as one batch: the *_multi kernels below share the
+// per-element bodies with the kernels above and are driven by per-stream descriptors in device memory; the host
+// stages are the same functions, called per stream (the work mapping of its histogram stage: pfmpe_init_plan.hpp).
+#include "pfmpe_init_plan.hpp"
 #include "pfmpe_prior.hpp"
 #include "pf_p3p.hpp"
 
@@ -89,15 +94,21 @@ __device__ __forceinline__ void unused_markers(int x, int y, int z, int* un) {
   }
 }
 
-__global__ void k_init_prep(const InitArgs ia, const double* __restrict__ blobs, double* __restrict__ iv) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= ia.B) return;
+// calculateImageVectors (PE:1072-1085) of blob i
+__device__ __forceinline__ void prep_blob(const InitArgs& ia, const double* __restrict__ blobs, double* __restrict__ iv,
+                                          int i) {
   double v[3];
   v[0] = (blobs[2 * i] - ia.K[2]) / ia.K[0];
   v[1] = (blobs[2 * i + 1] - ia.K[5]) / ia.K[4];
   v[2] = 1;
   const double n = p3p::norm3(v);
   for (int k = 0; k < 3; ++k) iv[3 * i + k] = v[k] / n;
+}
+
+__global__ void k_init_prep(const InitArgs ia, const double* __restrict__ blobs, double* __restrict__ iv) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ia.B) return;
+  prep_blob(ia, blobs, iv, i);
 }
 
 __device__ __forceinline__ double sqd(double ax, double ay, double bx, double by) {
@@ -107,9 +118,8 @@ __device__ __forceinline__ double sqd(double ax, double ay, double bx, double by
 
 // PE:1554-1581: the three blobs pairwise within threshDist, and >= 5 blobs within threshDist2 of
 // their centroid (the three themselves included)
-__global__ void k_p3p_filter(const InitArgs ia, const double* __restrict__ blobs, uint8_t* __restrict__ pass) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= ia.ncomb) return;
+__device__ __forceinline__ void filter_comb(int B, const double* __restrict__ blobs, uint8_t* __restrict__ pass,
+                                            int64_t r) {
   int a, b, c;
   unrank3(r, a, b, c);
   const double x1 = blobs[2 * a], y1 = blobs[2 * a + 1];
@@ -120,16 +130,137 @@ __global__ void k_p3p_filter(const InitArgs ia, const double* __restrict__ blobs
   if (ok) {
     const double mx = (x1 + x2 + x3) / 3, my = (y1 + y2 + y3) / 3;
     int cd = 0;
-    for (int k = 0; k < ia.B; ++k) cd += sqd(mx, my, blobs[2 * k], blobs[2 * k + 1]) < kThreshDist ? 1 : 0;
+    for (int k = 0; k < B; ++k) cd += sqd(mx, my, blobs[2 * k], blobs[2 * k + 1]) < kThreshDist ? 1 : 0;
     ok = cd >= 5;
   }
   pass[r] = ok ? 1 : 0;
+}
+
+__global__ void k_p3p_filter(const InitArgs ia, const double* __restrict__ blobs, uint8_t* __restrict__ pass) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= ia.ncomb) return;
+  filter_comb(ia.B, blobs, pass, r);
 }
 
 
 // Stage 1: one thread per (colex combination, ordered marker triple), grid-stride.  HLDS: histogram in
 // LDS (flushed once per block with integer atomics) or straight to global atomics for large B x M.
 // Dynamic LDS: sorted blob x, y (doubles), original index (int), then the LDS histogram.
+//
+// hist_block: one block's share of one stream's histogram in the batch kernel (k_p3p_hist_multi): the items first,
+// first + stride, ... of ia.items; Kc = the camera matrix where the block keeps it (LDS), lds = the block's carve
+// (laid out as above), s_mk = its marker table.  The per-item body is k_p3p_hist's, statement for statement: the
+// single-stream kernel below keeps its own copy, because calling this function from it changed its register
+// allocation and schedule (scripts/device_code_diff.py), and its assembly is what DESIGN.md §4.7 measured.
+template <int MAXU, bool HLDS>
+__device__ __forceinline__ void hist_block(const InitArgs& ia, const double* Kc, unsigned char* lds, double* s_mk,
+                                           int64_t first, int64_t stride, const double* __restrict__ blobs,
+                                           const double* __restrict__ iv, const double* __restrict__ sorted_xy,
+                                           const int* __restrict__ sorted_idx, const uint8_t* __restrict__ pass,
+                                           uint32_t* __restrict__ hist) {
+  const int B = ia.B, M = ia.M;
+  double* sx = (double*)lds;
+  double* sy = sx + B;
+  int* sidx = (int*)(sy + B);
+  uint32_t* lh = (uint32_t*)(sidx + ((B + 3) & ~3));
+  for (int i = threadIdx.x; i < B; i += blockDim.x) {
+    sx[i] = sorted_xy[2 * i];
+    sy[i] = sorted_xy[2 * i + 1];
+    sidx[i] = sorted_idx[i];
+  }
+  for (int i = threadIdx.x; i < 3 * M; i += blockDim.x) s_mk[i] = ia.markers[i];
+  if (HLDS)
+    for (int i = threadIdx.x; i < B * M; i += blockDim.x) lh[i] = 0;
+  __syncthreads();
+  uint32_t* H = HLDS ? lh : hist;
+  const double tol = ia.tol, win = ia.win;
+  const int nuo = M - 3;
+
+  const int64_t items = ia.items;
+  const int nperm = ia.nperm;
+  for (int64_t item = first; item < items; item += stride) {
+    const int64_t r = item / nperm;
+    const int p = (int)(item - r * nperm);
+    if (!pass[r]) continue;
+    int sa[3];
+    unrank3(r, sa[0], sa[1], sa[2]);
+    int pm[3];
+    perm3(p, M, pm[0], pm[1], pm[2]);
+    double fv[3][3], wp[3][3];
+    for (int k = 0; k < 3; ++k)
+      for (int q = 0; q < 3; ++q) {
+        fv[k][q] = iv[3 * sa[k] + q];
+        wp[k][q] = s_mk[3 * pm[k] + q];
+      }
+    p3p::Setup st;
+    double roots[4];
+    if (!p3p::setup(fv, wp, st, roots)) continue;
+    int un[MAXU > 0 ? MAXU : 1];
+    unused_markers<MAXU>(pm[0], pm[1], pm[2], un);
+    const double dmx = (blobs[2 * sa[0]] + blobs[2 * sa[1]] + blobs[2 * sa[2]]) / 3;
+    const double dmy = (blobs[2 * sa[0] + 1] + blobs[2 * sa[1] + 1] + blobs[2 * sa[2] + 1]) / 3;
+    double prev[12];
+    for (int k = 0; k < 4; ++k) {
+      double sol[12];
+      p3p::solution(st, roots[k], sol);
+      bool repeated = false;  // (solutions(k) - solutions(k-1)).all() == 0: some entry unchanged
+      if (k > 0)
+        for (int q = 0; q < 12; ++q) repeated = repeated || (sol[q] - prev[q] == 0);
+      for (int q = 0; q < 12; ++q) prev[q] = sol[q];
+      if (repeated || !p3p::finite12(sol)) continue;
+      double inv[12];
+      p3p::inverse34(sol, inv);
+      double pu[MAXU > 0 ? MAXU : 1], pv[MAXU > 0 ? MAXU : 1];
+#pragma unroll
+      for (int m = 0; m < MAXU; ++m)
+        if (m < nuo) p3p::project(Kc, inv, &s_mk[3 * un[m]], pu[m], pv[m]);
+      bool any = false;
+#pragma unroll
+      for (int m = 0; m < MAXU; ++m) {
+        if (m >= nuo) break;
+        const double u = pu[m];
+        if (!(fabs(u) < 1e300) || !(fabs(pv[m]) < 1e300)) continue;  // NaN / inf never wins a strict '<'
+        int lo = 0, hi = B;                                           // first sx >= u - win
+        const double xl = u - win, xh = u + win;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (sx[mid] < xl) lo = mid + 1;
+          else hi = mid;
+        }
+        for (int q = lo; q < B && sx[q] <= xh; ++q) {
+          const int bi = sidx[q];
+          if (bi == sa[0] || bi == sa[1] || bi == sa[2]) continue;
+          const double bx = sx[q], by = sy[q];
+          if (!(sqd(dmx, dmy, bx, by) < kThreshDist)) continue;
+          // calculateMinDistancesAndPairs (PE:2093-2137): nearest projection, strict '<' from +inf
+          double mind = INFINITY;
+          int pr = -1;
+#pragma unroll
+          for (int m2 = 0; m2 < MAXU; ++m2)
+            if (m2 < nuo) {
+              const double d = sqd(bx, by, pu[m2], pv[m2]);
+              if (d < mind) {
+                mind = d;
+                pr = m2;
+              }
+            }
+          if (pr != m || !(sqrt(mind) < tol)) continue;
+          if (!any) {
+            any = true;
+            for (int mm = 0; mm < 3; ++mm) atomicAdd(&H[sa[mm] * M + pm[mm]], 1u);
+          }
+          atomicAdd(&H[bi * M + un[m]], 1u);
+        }
+      }
+    }
+  }
+  if (HLDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < B * M; i += blockDim.x)
+      if (lh[i]) atomicAdd(&hist[i], lh[i]);
+  }
+}
+
 template <int MAXU, bool HLDS>
 __global__ __launch_bounds__(kInitBlock, PFMPE_P3P_MINB) void k_p3p_hist(const InitArgs ia, const double* __restrict__ blobs,
                                                           const double* __restrict__ iv,
@@ -245,6 +376,89 @@ __global__ __launch_bounds__(kInitBlock, PFMPE_P3P_MINB) void k_p3p_hist(const I
 // its M correspondence rows.  cand: per candidate 2*M ints (LED, detection), 1-based.
 // status: 0 = P3P failed (collinear), 1 = no solution within certainty_threshold, 2 = valid (inv = the
 // inverse of the smallest-error valid solution, top 3 rows).
+//
+// check_item: item `item` of one stream in the batch kernel (k_p3p_check_multi).  The body is k_p3p_check's,
+// statement for statement; as with hist_block the single-stream kernel keeps its own copy, since calling this
+// function from it changed its assembly.
+template <int MAXU>
+__device__ __forceinline__ void check_item(const InitArgs& ia, double certainty_threshold,
+                                           const double* __restrict__ blobs, const double* __restrict__ iv,
+                                           const int* __restrict__ cand, const int* __restrict__ triples,
+                                           uint8_t* __restrict__ status, double* __restrict__ out_inv, int64_t item) {
+  const int ci = (int)(item / ia.ncomb_m);
+  const int q = (int)(item - (int64_t)ci * ia.ncomb_m);
+  const int M = ia.M;
+  const int* cp = cand + (int64_t)ci * 2 * M;
+  const int t = triples[q];
+  const int s[3] = {t & 0xff, (t >> 8) & 0xff, (t >> 16) & 0xff};
+  double fv[3][3], wp[3][3];
+  for (int k = 0; k < 3; ++k)
+    for (int d = 0; d < 3; ++d) {
+      wp[k][d] = ia.markers[3 * (cp[2 * s[k]] - 1) + d];
+      fv[k][d] = iv[3 * (cp[2 * s[k] + 1] - 1) + d];
+    }
+  int un[MAXU > 0 ? MAXU : 1];
+  unused_markers<MAXU>(s[0], s[1], s[2], un);
+  const int nu = M - 3;
+  p3p::Setup st;
+  double roots[4];
+  if (!p3p::setup(fv, wp, st, roots)) {
+    status[item] = 0;
+    return;
+  }
+  const double tol2 = ia.tol * ia.tol;  // pow(tol, 2) folds to tol * tol
+  double min_err = INFINITY;
+  double best[12];
+  bool any_valid = false;
+  for (int j = 0; j < 4; ++j) {
+    double sol[12];
+    p3p::solution(st, roots[j], sol);
+    if (!p3p::finite12(sol)) continue;
+    double inv[12];
+    p3p::inverse34(sol, inv);
+    // calculateSquaredReprojectionErrorAndCertainty (PE:1087-1132): index-paired squared distances,
+    // then up to min(size) extractions of Eigen's minCoeff (first minimum, from coeff(0)) while <= tol^2
+    double dist[MAXU > 0 ? MAXU : 1];
+#pragma unroll
+    for (int a = 0; a < MAXU; ++a)
+      if (a < nu) {
+        double u, v;
+        p3p::project(ia.K, inv, &ia.markers[3 * (cp[2 * un[a]] - 1)], u, v);
+        const int bi = cp[2 * un[a] + 1] - 1;
+        dist[a] = sqd(blobs[2 * bi], blobs[2 * bi + 1], u, v);
+      }
+    double sq_err = 0;
+    int ncorr = 0;
+    for (int it = 0; it < nu; ++it) {
+      double mv = dist[0];
+      int r = 0;
+#pragma unroll
+      for (int a = 1; a < MAXU; ++a)
+        if (a < nu && dist[a] < mv) {
+          mv = dist[a];
+          r = a;
+        }
+      if (!(mv <= tol2)) break;
+      sq_err += mv;
+      ncorr++;
+#pragma unroll
+      for (int a = 0; a < MAXU; ++a)
+        if (a == r) dist[a] = INFINITY;
+    }
+    const double certainty = (double)ncorr / (double)nu;
+    if (certainty >= certainty_threshold) {
+      any_valid = true;
+      if (sq_err < min_err) {
+        min_err = sq_err;
+        for (int k = 0; k < 12; ++k) best[k] = inv[k];
+      }
+    }
+  }
+  status[item] = any_valid ? 2 : 1;
+  if (any_valid)
+    for (int k = 0; k < 12; ++k) out_inv[item * 12 + k] = best[k];
+}
+
 template <int MAXU>
 __global__ __launch_bounds__(kInitBlock) void k_p3p_check(const InitArgs ia, double certainty_threshold,
                                                            const double* __restrict__ blobs,
@@ -335,6 +549,127 @@ __global__ void k_init_seed(const double* __restrict__ est, int K, int N, double
   if (s >= N || (s == 0 && K < N)) return;
   const int e = (N - s - 1) % K;  // 0-based estimate
   for (int q = 0; q < 12; ++q) poses[12 * (int64_t)s + q] = est[12 * (int64_t)e + q];
+}
+
+// ---------------------------------------------------------------- the batch (pfmpe_initialise_multi)
+// S streams share each stage's launches.  A stage's descriptors (one InitDesc per stream, in device memory: S x 0.6 KB
+// do not belong in kernel arguments) and its head go up with the stage's one upload.  The flat kernels (prep, filter,
+// check, seed) run over the concatenation of the streams' elements and find the stream of an element in a prefix
+// table of the head; a histogram block finds its stream from the plan's first_block.
+constexpr int kInitMaxStreams = PFMPE_INIT_MAX_STREAMS;
+struct InitDesc {
+  InitArgs a;                  // items: the stage's (histogram / check)
+  double certainty_threshold;  // check
+  const double* blobs;
+  double* iv;
+  const double* sxy;           // histogram: x-sorted blobs, their original indices, the filter's verdicts, the counts
+  const int* sidx;
+  uint8_t* pass;
+  uint32_t* hist;
+  const int* cand;             // check: candidate table, 3-subsets, results
+  const int* triples;
+  uint8_t* status;
+  double* out_inv;
+  const double* est;           // seed: stored estimates, the member's transfer block
+  double* poses;
+  int32_t K, N;
+  int32_t identity0;           // seed, K < N: 1 = slot 0 becomes the identity (no prior), 0 = it is there already
+  int32_t first_block, blocks, lds_hist;  // histogram: the plan (pfmpe_init_plan.hpp)
+};
+struct InitHead {
+  int32_t S, pad;
+  int64_t pre[2][kInitMaxStreams + 1];        // element prefixes: [0] blobs / seed slots, [1] combinations / check items
+  int32_t hb_n[4];                            // histogram launch of bucket b: its streams,
+  int32_t hb_first[3][kInitMaxStreams + 1];   // their first blocks (ascending; [n] = the launch's size)
+  int32_t hb_stream[3][kInitMaxStreams];      // and stream indices
+};
+
+// the stream of element g: the last s with pre[s] <= g (streams without elements are skipped)
+__device__ __forceinline__ int stream_of(const int64_t* __restrict__ pre, int S, int64_t g) {
+  int lo = 0, hi = S;  // pre[lo] <= g < pre[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (pre[mid] <= g) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ void k_init_prep_multi(const InitHead* __restrict__ hd, const InitDesc* __restrict__ descs) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int S = hd->S;
+  if (g >= hd->pre[0][S]) return;
+  const int s = stream_of(hd->pre[0], S, g);
+  const InitDesc& d = descs[s];
+  prep_blob(d.a, d.blobs, d.iv, (int)(g - hd->pre[0][s]));
+}
+
+__global__ void k_p3p_filter_multi(const InitHead* __restrict__ hd, const InitDesc* __restrict__ descs) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int S = hd->S;
+  if (g >= hd->pre[1][S]) return;
+  const int s = stream_of(hd->pre[1], S, g);
+  const InitDesc& d = descs[s];
+  filter_comb(d.a.B, d.blobs, d.pass, g - hd->pre[1][s]);
+}
+
+// Stage 1 of the batch, one launch per unused-marker bucket present.  Block -> stream by a binary search over the
+// launch's first blocks (uniform: scalar code, once per block); then the block is block (blockIdx - first_block) of
+// `blocks` of a single-stream grid over that stream's items.  Dynamic LDS: K (16 doubles), then the single kernel's
+// carve for this stream; the launch is sized for its largest stream.
+template <int MAXU>
+__global__ __launch_bounds__(kInitBlock, PFMPE_P3P_MINB) void k_p3p_hist_multi(const InitHead* __restrict__ hd,
+                                                                                const InitDesc* __restrict__ descs,
+                                                                                int bucket) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  __shared__ double s_mk[kMaxMarkers * 3];
+  const int32_t* first = hd->hb_first[bucket];
+  int lo = 0, hi = hd->hb_n[bucket];  // first[lo] <= blockIdx.x < first[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (first[mid] <= (int)blockIdx.x) lo = mid;
+    else hi = mid;
+  }
+  const InitDesc& d = descs[hd->hb_stream[bucket][lo]];
+  double* sK = (double*)lds;
+  if (threadIdx.x < 9) sK[threadIdx.x] = d.a.K[threadIdx.x];  // hist_block's barrier publishes it
+  const int64_t at = (int64_t)((int)blockIdx.x - d.first_block) * kInitBlock + threadIdx.x;
+  const int64_t stride = (int64_t)d.blocks * kInitBlock;
+  if (d.lds_hist)
+    hist_block<MAXU, true>(d.a, sK, lds + 128, s_mk, at, stride, d.blobs, d.iv, d.sxy, d.sidx, d.pass, d.hist);
+  else
+    hist_block<MAXU, false>(d.a, sK, lds + 128, s_mk, at, stride, d.blobs, d.iv, d.sxy, d.sidx, d.pass, d.hist);
+}
+
+// Stage 3 of the batch: flat over the streams' (candidate, 3-subset) items.  MAXU: the largest bucket in the batch (a
+// wider bucket runs the same operations on a stream of fewer markers, as within a bucket).
+template <int MAXU>
+__global__ __launch_bounds__(kInitBlock) void k_p3p_check_multi(const InitHead* __restrict__ hd,
+                                                                 const InitDesc* __restrict__ descs) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int S = hd->S;
+  if (g >= hd->pre[1][S]) return;
+  const int s = stream_of(hd->pre[1], S, g);
+  const InitDesc& d = descs[s];
+  check_item<MAXU>(d.a, d.certainty_threshold, d.blobs, d.iv, d.cand, d.triples, d.status, d.out_inv,
+                   g - hd->pre[1][s]);
+}
+
+// Stage 4 of the batch: k_init_seed over the slots of every found stream, each into its member's transfer block.
+__global__ void k_init_seed_multi(const InitHead* __restrict__ hd, const InitDesc* __restrict__ descs) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int S = hd->S;
+  if (g >= hd->pre[0][S]) return;
+  const int si = stream_of(hd->pre[0], S, g);
+  const InitDesc& d = descs[si];
+  const int s = (int)(g - hd->pre[0][si]);
+  if (s == 0 && d.K < d.N) {
+    if (d.identity0)
+      for (int q = 0; q < 12; ++q) d.poses[q] = (q == 0 || q == 5 || q == 10) ? 1.0 : 0.0;
+    return;
+  }
+  const int e = (d.N - s - 1) % d.K;  // 0-based estimate
+  for (int q = 0; q < 12; ++q) d.poses[12 * (int64_t)s + q] = d.est[12 * (int64_t)e + q];
 }
 
 }  // namespace pfmpe
@@ -435,8 +770,9 @@ int run_histogram(pfmpe_ctx* c, const double* blobs, int B, uint32_t* hist) {
 }
 
 // correspondencesFromHistogram (PE:1134-1288) with bInitialisation = true: candidate (LED, detection)
-// vectors, most probable first; ambiguous ones (a detection used twice, zeros included) dropped.
-int candidates(pfmpe_ctx* c, int B, int M, const uint32_t* hist, int max_cand,
+// vectors, most probable first; ambiguous ones (a detection used twice, zeros included) dropped.  An error is
+// reported on c with the text `who` + ...
+int candidates(pfmpe_ctx* c, const std::string& who, int B, int M, const uint32_t* hist, int max_cand,
                std::vector<std::vector<uint32_t>>& out) {
   out.clear();
   const double prob_threshold = (1.3 * 1.0) / (double)((unsigned)B * (unsigned)M);
@@ -467,7 +803,7 @@ int candidates(pfmpe_ctx* c, int B, int M, const uint32_t* hist, int max_cand,
   int64_t Ntot = 1;
   for (int k = 0; k < M; ++k) {
     Ntot *= std::max<int64_t>(1, (int64_t)up[k].size());
-    if (Ntot > max_cand) return fail(c, PFMPE_E_CAP, "initialise: correspondence vectors exceed max_candidates");
+    if (Ntot > max_cand) return fail(c, PFMPE_E_CAP, who + "correspondence vectors exceed max_candidates");
   }
   const int N = (int)Ntot;
   std::vector<double> vp(N);
@@ -598,137 +934,24 @@ void compute_transformation(int M, const double* obj, const double* rep, double*
     T12[4 * r + 3] = mr[r] - (T12[4 * r + 0] * mo[0] + T12[4 * r + 1] * mo[1] + T12[4 * r + 2] * mo[2]);
 }
 
-}  // namespace
-
-extern "C" {
-
-void pfmpe_default_init_params(pfmpe_init_params* p) {
-  if (!p) return;
-  p->certainty_threshold = 1.0;   // README.md:245, launch file README.md:340
-  p->valid_corr_threshold = 0.5;  // README.md:249
-  p->n_particles = 0;
-  p->max_candidates = 1 << 20;
+// the lexicographic 3-subsets of M rows, packed a | b << 8 | d << 16 (stage 3's order, PE:1331)
+std::vector<int> lex_triples(int M) {
+  std::vector<int> trip;
+  for (int a = 0; a < M; ++a)
+    for (int b = a + 1; b < M; ++b)
+      for (int d = b + 1; d < M; ++d) trip.push_back(a | (b << 8) | (d << 16));
+  return trip;
 }
 
-int pfmpe_p3p_histogram(pfmpe_ctx* c, const double* blobs, int B, uint32_t* hist) {
-  if (!c) return PFMPE_E_ARG;
-  if (!blobs || !hist) return fail(c, PFMPE_E_ARG, "p3p_histogram: null blobs/hist");
-  if (!c->has_model) return fail(c, PFMPE_E_STATE, "p3p_histogram: set_model first");
-  if (c->M < 3) return fail(c, PFMPE_E_ARG, "p3p_histogram: needs M >= 3 markers");
-  if (B < 3) return fail(c, PFMPE_E_ARG, "p3p_histogram: needs B >= 3 blobs");
-  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, "p3p_histogram: B exceeds max_blobs");
-  RET(set_device(c));
-  c->timing_now = c->timing > 0;
-  const size_t ev_mark = c->ev_used;  // pending brackets of earlier frames
-  const int rc = run_histogram(c, blobs, B, hist);
-  c->timing_now = false;
-  if (rc != PFMPE_OK) c->ev_used = ev_mark;  // only this call's brackets are dropped (success harvested them all)
-  return rc;
-}
-
-int pfmpe_initialise(pfmpe_ctx* c, const double* blobs, int B, const pfmpe_init_params* prm, pfmpe_init_out* out,
-                     uint32_t* hist_out) {
-  if (!c) return PFMPE_E_ARG;
-  if (!out || (B > 0 && !blobs) || B < 0) return fail(c, PFMPE_E_ARG, "initialise: bad arguments");
-  if (!c->has_model) return fail(c, PFMPE_E_STATE, "initialise: set_model first");
-  if (c->M < 3) return fail(c, PFMPE_E_ARG, "initialise: needs M >= 3 markers");
-  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, "initialise: B exceeds max_blobs");
-  pfmpe_init_params p;
-  pfmpe_default_init_params(&p);
-  if (prm) p = *prm;
-  if (p.max_candidates <= 0) p.max_candidates = 1 << 20;
-  const int N = p.n_particles > 0 ? p.n_particles : (c->has_prior ? c->N : c->max_particles);
-  if (N > c->max_particles) return fail(c, PFMPE_E_CAP, "initialise: n_particles exceeds max_particles");
-  std::memset(out, 0, sizeof(*out));
-  out->first_match = -1;
+// The ordered bookkeeping of initialise / checkCorrespondences (PE:1425-1496, 1733-1760) over the candidates of one
+// context, for the single call and the batch alike: status / invs are stage 3's results for the candidates with M
+// rows, in candidate order; flag: the fail flag so far.  Fills out's found, flag_fail, n_estimates, first_match,
+// n_corr, corr and predicted_pose, and est: the stored P3P poses in store order (estimate k at slot N - k).
+void book_keeping(const pfmpe_ctx* c, const std::vector<std::vector<uint32_t>>& cands, const uint8_t* status,
+                  const double* invs, int N, const pfmpe_init_params& p, int flag, pfmpe_init_out* out,
+                  std::vector<double>& est) {
   const int M = c->M;
-  if (B < M) {  // PE:1507-1512: the PF initialisation needs every marker detected
-    out->flag_fail = 10;
-    return PFMPE_OK;
-  }
-  RET(set_device(c));
-  std::vector<uint32_t> hist((size_t)B * M);
-  c->timing_now = c->timing > 0;
-  int rc = run_histogram(c, blobs, B, hist.data());
-  if (rc != PFMPE_OK) {
-    c->timing_now = false;
-    return rc;
-  }
-  if (hist_out) std::memcpy(hist_out, hist.data(), hist.size() * sizeof(uint32_t));
-  uint64_t tot = 0;
-  for (uint32_t h : hist) tot += h;
-  out->hist_total = tot;
-  if (tot == 0) {
-    c->timing_now = false;
-    out->flag_fail = 12;
-    return PFMPE_OK;
-  }
-  std::vector<std::vector<uint32_t>> cands;
-  rc = candidates(c, B, M, hist.data(), p.max_candidates, cands);
-  if (rc != PFMPE_OK) {
-    c->timing_now = false;
-    return rc;
-  }
-  out->n_candidates = (int)cands.size();
-  int flag = cands.empty() ? 11 : -1;
-
-  // ---- stage 3 on the device: every candidate with M rows x every lexicographic 3-subset
   const int ncm = M * (M - 1) * (M - 2) / 6;
-  std::vector<int> full;  // indices of candidates with M rows (the others fail with flag 6, no P3P)
-  for (size_t i = 0; i < cands.size(); ++i)
-    if ((int)cands[i].size() == 2 * M) full.push_back((int)i);
-  std::vector<uint8_t> status((size_t)full.size() * ncm);
-  std::vector<double> invs((size_t)full.size() * ncm * 12);
-  if (!full.empty()) {
-    InitArgs ia = make_args(c, B);
-    ia.items = (int64_t)full.size() * ncm;
-    std::vector<int> ctab((size_t)full.size() * 2 * M);
-    for (size_t f = 0; f < full.size(); ++f)
-      for (int k = 0; k < 2 * M; ++k) ctab[f * 2 * M + k] = (int)cands[full[f]][k];
-    std::vector<int> trip;
-    for (int a = 0; a < M; ++a)
-      for (int b = a + 1; b < M; ++b)
-        for (int d = b + 1; d < M; ++d) trip.push_back(a | (b << 8) | (d << 16));
-    Arena ar;
-    const size_t o_blobs = ar.take<double>(2 * (size_t)B), o_iv = ar.take<double>(3 * (size_t)B);
-    const size_t o_c = ar.take<int>(ctab.size()), o_t = ar.take<int>(trip.size());
-    const size_t o_s = ar.take<uint8_t>(status.size()), o_i = ar.take<double>(invs.size());
-    rc = ensure_init(c, ar.off);
-    if (rc != PFMPE_OK) {
-      c->timing_now = false;
-      return rc;
-    }
-    unsigned char* d = c->d_init.get();
-    double* d_blobs = (double*)(d + o_blobs);
-    double* d_iv = (double*)(d + o_iv);
-    HIPCHK(c, hipMemcpyAsync(d_blobs, blobs, 2 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_c, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_t, trip.data(), trip.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_init_prep, dim3((B + 255) / 256), dim3(256), 0, c->stream, ia, d_blobs, d_iv);
-    HIPCHK(c, hipGetLastError());
-    const unsigned grid = (unsigned)((ia.items + kInitBlock - 1) / kInitBlock);
-    const double ct = p.certainty_threshold;
-    RET(launch(c, PFMPE_K_P3P_CHECK, [&] {
-      const int nu = M - 3;
-      if (nu <= 2)
-        hipLaunchKernelGGL((k_p3p_check<2>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct, d_blobs, d_iv,
-                           (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
-      else if (nu <= 9)
-        hipLaunchKernelGGL((k_p3p_check<9>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct, d_blobs, d_iv,
-                           (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
-      else
-        hipLaunchKernelGGL((k_p3p_check<kMaxMarkers - 3>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct,
-                           d_blobs, d_iv, (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
-    }));
-    HIPCHK(c, hipMemcpyAsync(status.data(), d + o_s, status.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(invs.data(), d + o_i, invs.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  if (c->timing_now) RET(harvest_timing(c));
-  c->timing_now = false;
-
-  // ---- the ordered bookkeeping of initialise / checkCorrespondences (PE:1425-1496, 1733-1760)
-  std::vector<double> est;  // stored P3P poses in store order (estimate k at slot N - k)
   int n_est = 1, found = 0;
   size_t fi = 0;
   for (size_t ci = 0; ci < cands.size(); ++ci) {
@@ -781,10 +1004,474 @@ int pfmpe_initialise(pfmpe_ctx* c, const double* blobs, int B, const pfmpe_init_
   out->found = found;
   out->n_estimates = n_est - 1;
   out->flag_fail = found ? 0 : flag;
-  if (!found) return PFMPE_OK;
+}
+
+// the effective parameters of a call: the defaults where prm is NULL, the default cap for max_candidates <= 0
+pfmpe_init_params effective_params(const pfmpe_init_params* prm) {
+  pfmpe_init_params p;
+  pfmpe_default_init_params(&p);
+  if (prm) p = *prm;
+  if (p.max_candidates <= 0) p.max_candidates = 1 << 20;
+  return p;
+}
+
+// ---------------------------------------------------------------- the batch (pfmpe_initialise_multi)
+// one stream of the batch on the host
+struct MultiStream {
+  pfmpe_ctx* c = nullptr;
+  const double* blobs = nullptr;
+  int B = 0, N = 0;
+  pfmpe_init_params p{};
+  pfmpe_init_out o{};                       // becomes out[s] when the whole batch has succeeded
+  std::vector<uint32_t> hist;               // stage 1 (B >= M only)
+  std::vector<std::vector<uint32_t>> cands;
+  std::vector<int> full;                    // candidates with M rows
+  int flag = -1;
+  size_t st_off = 0;                        // stage 3: this stream's first item in the batch's results
+  std::vector<double> est;
+};
+
+// a stage's upload image: the head, the descriptors, then whatever the stage appends; offsets are the arena's
+struct StageImage {
+  std::vector<unsigned char> bytes;
+  size_t o_head, o_desc;
+  Arena ar;
+  explicit StageImage(int S) {
+    o_head = ar.take<InitHead>(1);
+    o_desc = ar.take<InitDesc>(S);
+  }
+  InitHead* head() { return (InitHead*)(bytes.data() + o_head); }
+  InitDesc* desc() { return (InitDesc*)(bytes.data() + o_desc); }
+  // room for n elements of X in the upload part; the image grows to hold it
+  template <typename X>
+  size_t put(const X* src, size_t n) {
+    const size_t o = ar.take<X>(n);
+    bytes.resize(ar.off, 0);
+    if (n) std::memcpy(bytes.data() + o, src, n * sizeof(X));
+    return o;
+  }
+  void begin() { bytes.assign(ar.off, 0); }
+};
+
+// The leader's pinned read-back block, grown by half more than asked.  Pinned and kept: the check results of a batch
+// come back as one block, and with a fresh pageable vector per call a B = 50 batch of 8 was slower than 8 single
+// calls.
+int ensure_readback(pfmpe_ctx* c, size_t bytes) { return c->h_init.grow(c, bytes, bytes + bytes / 2); }
+
+// Stage 1 of the batch: the histograms of the streams with B >= M (at least one) into their MultiStream::hist.
+int multi_histograms(pfmpe_ctx* c0, std::vector<MultiStream>& st) {
+  const int S = (int)st.size();
+  int32_t Ms[kInitMaxStreams], Bs[kInitMaxStreams], per_bucket[3];
+  pfmpe_init_plan plan[kInitMaxStreams];
+  for (int s = 0; s < S; ++s) {
+    Ms[s] = st[s].c->M;
+    Bs[s] = st[s].B;
+  }
+  pfmpe_plan::init_plan(Ms, Bs, S, c0->num_cu, plan, per_bucket);
+  StageImage im(S);
+  im.begin();
+  // upload part: per stream the blobs, the x-sorted list and its indices; device part: image vectors, filter
+  // verdicts, and the histograms back to back (one memset, one read-back)
+  struct Off {
+    size_t blobs, sxy, sidx, iv, pass, hist;
+  };
+  std::vector<Off> off(S);
+  for (int s = 0; s < S; ++s) {
+    if (plan[s].items == 0) continue;
+    const int B = st[s].B;
+    const double* blobs = st[s].blobs;
+    // host-built x-sorted blob list for the pruned search, as run_histogram's
+    std::vector<int> order(B);
+    for (int i = 0; i < B; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return blobs[2 * x] < blobs[2 * y]; });
+    std::vector<double> sxy(2 * (size_t)B);
+    for (int i = 0; i < B; ++i) {
+      sxy[2 * i] = blobs[2 * order[i]];
+      sxy[2 * i + 1] = blobs[2 * order[i] + 1];
+    }
+    off[s].blobs = im.put(blobs, 2 * (size_t)B);
+    off[s].sxy = im.put(sxy.data(), sxy.size());
+    off[s].sidx = im.put(order.data(), (size_t)B);
+  }
+  const size_t upload = im.ar.off;
+  size_t hist_words = 0;
+  for (int s = 0; s < S; ++s) {
+    if (plan[s].items == 0) continue;
+    off[s].iv = im.ar.take<double>(3 * (size_t)st[s].B);
+    off[s].pass = im.ar.take<uint8_t>((size_t)(plan[s].items / (Ms[s] * (Ms[s] - 1) * (Ms[s] - 2))));
+    off[s].hist = hist_words;
+    hist_words += (size_t)st[s].B * Ms[s];
+  }
+  const size_t o_hist = im.ar.take<uint32_t>(hist_words);
+  RET(ensure_init(c0, im.ar.off));
+  RET(ensure_readback(c0, hist_words * sizeof(uint32_t)));
+  unsigned char* d = c0->d_init.get();
+  InitHead* hd = im.head();
+  InitDesc* ds = im.desc();
+  hd->S = S;
+  size_t lds[3] = {0, 0, 0};
+  for (int s = 0; s < S; ++s) {
+    hd->pre[0][s + 1] = hd->pre[0][s];
+    hd->pre[1][s + 1] = hd->pre[1][s];
+    if (plan[s].items == 0) continue;
+    const int B = st[s].B, M = Ms[s];
+    InitDesc& e = ds[s];
+    e.a = make_args(st[s].c, B);
+    e.a.items = plan[s].items;
+    e.blobs = (const double*)(d + off[s].blobs);
+    e.sxy = (const double*)(d + off[s].sxy);
+    e.sidx = (const int*)(d + off[s].sidx);
+    e.iv = (double*)(d + off[s].iv);
+    e.pass = d + off[s].pass;
+    e.hist = (uint32_t*)(d + o_hist) + off[s].hist;
+    e.first_block = plan[s].first_block;
+    e.blocks = plan[s].blocks;
+    e.lds_hist = plan[s].lds_hist;
+    hd->pre[0][s + 1] += B;
+    hd->pre[1][s + 1] += e.a.ncomb;
+    const int b = plan[s].bucket;
+    hd->hb_first[b][hd->hb_n[b]] = plan[s].first_block;
+    hd->hb_stream[b][hd->hb_n[b]] = s;
+    hd->hb_n[b] += 1;
+    const size_t hist_bytes = (size_t)B * M * sizeof(uint32_t);
+    lds[b] = std::max(lds[b], (size_t)128 + (size_t)B * 16 + (size_t)((B + 3) & ~3) * 4 + (e.lds_hist ? hist_bytes : 0));
+  }
+  for (int b = 0; b < 3; ++b) hd->hb_first[b][hd->hb_n[b]] = per_bucket[b];
+  const InitHead* d_hd = (const InitHead*)(d + im.o_head);
+  const InitDesc* d_ds = (const InitDesc*)(d + im.o_desc);
+  HIPCHK(c0, hipMemcpyAsync(d, im.bytes.data(), upload, hipMemcpyHostToDevice, c0->stream));
+  HIPCHK(c0, hipMemsetAsync(d + o_hist, 0, hist_words * sizeof(uint32_t), c0->stream));
+  hipLaunchKernelGGL(k_init_prep_multi, dim3((unsigned)((hd->pre[0][S] + 255) / 256)), dim3(256), 0, c0->stream, d_hd,
+                     d_ds);
+  HIPCHK(c0, hipGetLastError());
+  hipLaunchKernelGGL(k_p3p_filter_multi, dim3((unsigned)((hd->pre[1][S] + 255) / 256)), dim3(256), 0, c0->stream, d_hd,
+                     d_ds);
+  HIPCHK(c0, hipGetLastError());
+  RET(launch(c0, PFMPE_K_P3P_HIST, [&] {
+    if (per_bucket[0])
+      hipLaunchKernelGGL((k_p3p_hist_multi<2>), dim3(per_bucket[0]), dim3(kInitBlock), lds[0], c0->stream, d_hd, d_ds, 0);
+    if (per_bucket[1])
+      hipLaunchKernelGGL((k_p3p_hist_multi<9>), dim3(per_bucket[1]), dim3(kInitBlock), lds[1], c0->stream, d_hd, d_ds, 1);
+    if (per_bucket[2])
+      hipLaunchKernelGGL((k_p3p_hist_multi<kMaxMarkers - 3>), dim3(per_bucket[2]), dim3(kInitBlock), lds[2], c0->stream,
+                         d_hd, d_ds, 2);
+  }));
+  const uint32_t* all = (const uint32_t*)c0->h_init.get();
+  HIPCHK(c0, hipMemcpyAsync(c0->h_init.get(), d + o_hist, hist_words * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                            c0->stream));
+  HIPCHK(c0, hipStreamSynchronize(c0->stream));
+  if (c0->timing_now) RET(harvest_timing(c0));
+  for (int s = 0; s < S; ++s)
+    if (plan[s].items != 0) st[s].hist.assign(all + off[s].hist, all + off[s].hist + (size_t)st[s].B * Ms[s]);
+  return PFMPE_OK;
+}
+
+// Stage 3 of the batch: every candidate with M rows of every stream x every lexicographic 3-subset; the results in
+// candidate order, stream after stream (MultiStream::st_off), in the leader's read-back block (null without items).
+int multi_check(pfmpe_ctx* c0, std::vector<MultiStream>& st, const uint8_t** status, const double** invs) {
+  const int S = (int)st.size();
+  StageImage im(S);
+  im.begin();
+  struct Off {
+    size_t blobs, cand, trip, iv;
+  };
+  std::vector<Off> off(S);
+  size_t items = 0;
+  int bucket = 0;
+  for (int s = 0; s < S; ++s) {
+    MultiStream& m = st[s];
+    if (m.full.empty()) continue;
+    const int M = m.c->M;
+    std::vector<int> ctab(m.full.size() * 2 * M);
+    for (size_t f = 0; f < m.full.size(); ++f)
+      for (int k = 0; k < 2 * M; ++k) ctab[f * 2 * M + k] = (int)m.cands[m.full[f]][k];
+    const std::vector<int> trip = lex_triples(M);
+    off[s].blobs = im.put(m.blobs, 2 * (size_t)m.B);
+    off[s].cand = im.put(ctab.data(), ctab.size());
+    off[s].trip = im.put(trip.data(), trip.size());
+    m.st_off = items;
+    items += m.full.size() * trip.size();
+    bucket = std::max(bucket, pfmpe_plan::init_bucket(M));
+  }
+  *status = nullptr;
+  *invs = nullptr;
+  if (items == 0) return PFMPE_OK;
+  const size_t h_inv = (items + 255) & ~(size_t)255;  // read-back block: the status bytes, then the poses
+  RET(ensure_readback(c0, h_inv + items * 12 * sizeof(double)));
+  const size_t upload = im.ar.off;
+  for (int s = 0; s < S; ++s)
+    if (!st[s].full.empty()) off[s].iv = im.ar.take<double>(3 * (size_t)st[s].B);
+  const size_t o_s = im.ar.take<uint8_t>(items), o_i = im.ar.take<double>(items * 12);
+  RET(ensure_init(c0, im.ar.off));
+  unsigned char* d = c0->d_init.get();
+  InitHead* hd = im.head();
+  InitDesc* ds = im.desc();
+  hd->S = S;
+  for (int s = 0; s < S; ++s) {
+    const MultiStream& m = st[s];
+    hd->pre[0][s + 1] = hd->pre[0][s];
+    hd->pre[1][s + 1] = hd->pre[1][s];
+    if (m.full.empty()) continue;
+    InitDesc& e = ds[s];
+    e.a = make_args(m.c, m.B);
+    e.a.items = (int64_t)m.full.size() * e.a.ncomb_m;
+    e.certainty_threshold = m.p.certainty_threshold;
+    e.blobs = (const double*)(d + off[s].blobs);
+    e.iv = (double*)(d + off[s].iv);
+    e.cand = (const int*)(d + off[s].cand);
+    e.triples = (const int*)(d + off[s].trip);
+    e.status = d + o_s + m.st_off;
+    e.out_inv = (double*)(d + o_i) + m.st_off * 12;
+    hd->pre[0][s + 1] += m.B;
+    hd->pre[1][s + 1] += e.a.items;
+  }
+  const InitHead* d_hd = (const InitHead*)(d + im.o_head);
+  const InitDesc* d_ds = (const InitDesc*)(d + im.o_desc);
+  HIPCHK(c0, hipMemcpyAsync(d, im.bytes.data(), upload, hipMemcpyHostToDevice, c0->stream));
+  hipLaunchKernelGGL(k_init_prep_multi, dim3((unsigned)((hd->pre[0][S] + 255) / 256)), dim3(256), 0, c0->stream, d_hd,
+                     d_ds);
+  HIPCHK(c0, hipGetLastError());
+  const dim3 grid((unsigned)((items + kInitBlock - 1) / kInitBlock));
+  RET(launch(c0, PFMPE_K_P3P_CHECK, [&] {
+    if (bucket == 0)
+      hipLaunchKernelGGL((k_p3p_check_multi<2>), grid, dim3(kInitBlock), 0, c0->stream, d_hd, d_ds);
+    else if (bucket == 1)
+      hipLaunchKernelGGL((k_p3p_check_multi<9>), grid, dim3(kInitBlock), 0, c0->stream, d_hd, d_ds);
+    else
+      hipLaunchKernelGGL((k_p3p_check_multi<kMaxMarkers - 3>), grid, dim3(kInitBlock), 0, c0->stream, d_hd, d_ds);
+  }));
+  unsigned char* h = c0->h_init.get();
+  HIPCHK(c0, hipMemcpyAsync(h, d + o_s, items, hipMemcpyDeviceToHost, c0->stream));
+  HIPCHK(c0, hipMemcpyAsync(h + h_inv, d + o_i, items * 12 * sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+  HIPCHK(c0, hipStreamSynchronize(c0->stream));
+  *status = h;
+  *invs = (const double*)(h + h_inv);
+  return PFMPE_OK;
+}
+
+// Stage 4 of the batch: seed every found member's transfer block in one launch, import each on the leader's stream,
+// one synchronise.  The members' transfer blocks exist already (multi_run: nothing may fail between the first
+// import and the last for a reason other than the device).
+int multi_seed(pfmpe_ctx* c0, std::vector<MultiStream>& st) {
+  const int S = (int)st.size();
+  StageImage im(S);
+  im.begin();
+  std::vector<size_t> o_est(S, 0);
+  for (int s = 0; s < S; ++s)
+    if (st[s].o.found) o_est[s] = im.put(st[s].est.data(), st[s].est.size());
+  RET(ensure_init(c0, im.ar.off));
+  unsigned char* d = c0->d_init.get();
+  InitHead* hd = im.head();
+  InitDesc* ds = im.desc();
+  hd->S = S;
+  for (int s = 0; s < S; ++s) {
+    MultiStream& m = st[s];
+    hd->pre[0][s + 1] = hd->pre[0][s];
+    if (!m.o.found) continue;
+    InitDesc& e = ds[s];
+    e.est = (const double*)(d + o_est[s]);
+    e.poses = m.c->d_xfer.get();
+    e.K = m.o.n_estimates;
+    e.N = m.N;
+    e.identity0 = m.c->has_prior ? 0 : 1;
+    hd->pre[0][s + 1] += m.N;
+    // slot 0 keeps the resident set's slot 0 when K < N (identity when there is none: the seeding kernel's)
+    if (e.K < e.N && m.c->has_prior) RET(export_prior(m.c, 1, c0->stream, c0));
+  }
+  HIPCHK(c0, hipMemcpyAsync(d, im.bytes.data(), im.ar.off, hipMemcpyHostToDevice, c0->stream));
+  hipLaunchKernelGGL(k_init_seed_multi, dim3((unsigned)((hd->pre[0][S] + 255) / 256)), dim3(256), 0, c0->stream,
+                     (const InitHead*)(d + im.o_head), (const InitDesc*)(d + im.o_desc));
+  HIPCHK(c0, hipGetLastError());
+  for (int s = 0; s < S; ++s)
+    if (st[s].o.found)  // anchor (fp16 state): the first stored estimate
+      RET(import_enqueue(st[s].c, st[s].N, st[s].est.data(), c0->stream, c0));
+  HIPCHK(c0, hipStreamSynchronize(c0->stream));
+  for (int s = 0; s < S; ++s)
+    if (st[s].o.found) import_done(st[s].c, st[s].N);
+  return PFMPE_OK;
+}
+
+// the validated batch: stages 1 to 4 on the leader's stream, then out / the members' ordering state
+int multi_run(pfmpe_ctx* const* ctxs, std::vector<MultiStream>& st, pfmpe_init_out* out, uint32_t* const* hist_out) {
+  pfmpe_ctx* c0 = ctxs[0];
+  const int S = (int)st.size();
+  RET(set_device(c0));
+  // every member's work so far is ordered before the batch; a failure from here on gives the members their
+  // ordering state back (the leader's own was set by set_device)
+  OrderGuard members(ctxs, S);
+  RET(members.order(1, c0->stream, c0));
+  RET(multi_histograms(c0, st));
+  for (int s = 0; s < S; ++s)
+    if (hist_out && hist_out[s] && !st[s].hist.empty())
+      std::memcpy(hist_out[s], st[s].hist.data(), st[s].hist.size() * sizeof(uint32_t));
+  for (int s = 0; s < S; ++s) {
+    MultiStream& m = st[s];
+    if (m.hist.empty()) continue;  // B < M: flag 10
+    uint64_t tot = 0;
+    for (uint32_t h : m.hist) tot += h;
+    m.o.hist_total = tot;
+    if (tot == 0) {
+      m.o.flag_fail = 12;
+      continue;
+    }
+    RET(candidates(c0, "initialise_multi: stream " + std::to_string(s) + ": ", m.B, m.c->M, m.hist.data(),
+                   m.p.max_candidates, m.cands));
+    m.o.n_candidates = (int)m.cands.size();
+    m.flag = m.cands.empty() ? 11 : -1;
+    for (size_t i = 0; i < m.cands.size(); ++i)
+      if ((int)m.cands[i].size() == 2 * m.c->M) m.full.push_back((int)i);
+  }
+  const uint8_t* status = nullptr;
+  const double* invs = nullptr;
+  RET(multi_check(c0, st, &status, &invs));
+  if (c0->timing_now) RET(harvest_timing(c0));
+  c0->timing_now = false;
+  bool any_found = false;
+  for (int s = 0; s < S; ++s) {
+    MultiStream& m = st[s];
+    if (m.hist.empty() || m.o.hist_total == 0) continue;
+    book_keeping(m.c, m.cands, status + m.st_off, invs + m.st_off * 12, m.N, m.p, m.flag, &m.o, m.est);
+    if (m.o.found) {
+      any_found = true;
+      if (ensure_xfer(m.c) != PFMPE_OK)
+        return fail(c0, PFMPE_E_HIP, "initialise_multi: stream " + std::to_string(s) + ": " + m.c->err);
+    }
+  }
+  if (any_found) RET(multi_seed(c0, st));
+  members.commit();  // nothing of the batch is pending: no member needs a fence
+  for (int s = 0; s < S; ++s) out[s] = st[s].o;
+  return PFMPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pfmpe_default_init_params(pfmpe_init_params* p) {
+  if (!p) return;
+  p->certainty_threshold = 1.0;   // README.md:245, launch file README.md:340
+  p->valid_corr_threshold = 0.5;  // README.md:249
+  p->n_particles = 0;
+  p->max_candidates = 1 << 20;
+}
+
+int pfmpe_p3p_histogram(pfmpe_ctx* c, const double* blobs, int B, uint32_t* hist) {
+  if (!c) return PFMPE_E_ARG;
+  if (!blobs || !hist) return fail(c, PFMPE_E_ARG, "p3p_histogram: null blobs/hist");
+  if (!c->has_model) return fail(c, PFMPE_E_STATE, "p3p_histogram: set_model first");
+  if (c->M < 3) return fail(c, PFMPE_E_ARG, "p3p_histogram: needs M >= 3 markers");
+  if (B < 3) return fail(c, PFMPE_E_ARG, "p3p_histogram: needs B >= 3 blobs");
+  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, "p3p_histogram: B exceeds max_blobs");
+  RET(set_device(c));
+  c->timing_now = c->timing > 0;
+  const size_t ev_mark = c->ev_used;  // pending brackets of earlier frames
+  const int rc = run_histogram(c, blobs, B, hist);
+  c->timing_now = false;
+  if (rc != PFMPE_OK) c->ev_used = ev_mark;  // only this call's brackets are dropped (success harvested them all)
+  return rc;
+}
+
+int pfmpe_initialise(pfmpe_ctx* c, const double* blobs, int B, const pfmpe_init_params* prm, pfmpe_init_out* out,
+                     uint32_t* hist_out) {
+  if (!c) return PFMPE_E_ARG;
+  if (!out || (B > 0 && !blobs) || B < 0) return fail(c, PFMPE_E_ARG, "initialise: bad arguments");
+  if (!c->has_model) return fail(c, PFMPE_E_STATE, "initialise: set_model first");
+  if (c->M < 3) return fail(c, PFMPE_E_ARG, "initialise: needs M >= 3 markers");
+  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, "initialise: B exceeds max_blobs");
+  const pfmpe_init_params p = effective_params(prm);
+  const int N = p.n_particles > 0 ? p.n_particles : (c->has_prior ? c->N : c->max_particles);
+  if (N > c->max_particles) return fail(c, PFMPE_E_CAP, "initialise: n_particles exceeds max_particles");
+  std::memset(out, 0, sizeof(*out));
+  out->first_match = -1;
+  const int M = c->M;
+  if (B < M) {  // PE:1507-1512: the PF initialisation needs every marker detected
+    out->flag_fail = 10;
+    return PFMPE_OK;
+  }
+  RET(set_device(c));
+  std::vector<uint32_t> hist((size_t)B * M);
+  c->timing_now = c->timing > 0;
+  int rc = run_histogram(c, blobs, B, hist.data());
+  if (rc != PFMPE_OK) {
+    c->timing_now = false;
+    return rc;
+  }
+  if (hist_out) std::memcpy(hist_out, hist.data(), hist.size() * sizeof(uint32_t));
+  uint64_t tot = 0;
+  for (uint32_t h : hist) tot += h;
+  out->hist_total = tot;
+  if (tot == 0) {
+    c->timing_now = false;
+    out->flag_fail = 12;
+    return PFMPE_OK;
+  }
+  std::vector<std::vector<uint32_t>> cands;
+  rc = candidates(c, "initialise: ", B, M, hist.data(), p.max_candidates, cands);
+  if (rc != PFMPE_OK) {
+    c->timing_now = false;
+    return rc;
+  }
+  out->n_candidates = (int)cands.size();
+  int flag = cands.empty() ? 11 : -1;
+
+  // ---- stage 3 on the device: every candidate with M rows x every lexicographic 3-subset
+  const int ncm = M * (M - 1) * (M - 2) / 6;
+  std::vector<int> full;  // indices of candidates with M rows (the others fail with flag 6, no P3P)
+  for (size_t i = 0; i < cands.size(); ++i)
+    if ((int)cands[i].size() == 2 * M) full.push_back((int)i);
+  std::vector<uint8_t> status((size_t)full.size() * ncm);
+  std::vector<double> invs((size_t)full.size() * ncm * 12);
+  if (!full.empty()) {
+    InitArgs ia = make_args(c, B);
+    ia.items = (int64_t)full.size() * ncm;
+    std::vector<int> ctab((size_t)full.size() * 2 * M);
+    for (size_t f = 0; f < full.size(); ++f)
+      for (int k = 0; k < 2 * M; ++k) ctab[f * 2 * M + k] = (int)cands[full[f]][k];
+    const std::vector<int> trip = lex_triples(M);
+    Arena ar;
+    const size_t o_blobs = ar.take<double>(2 * (size_t)B), o_iv = ar.take<double>(3 * (size_t)B);
+    const size_t o_c = ar.take<int>(ctab.size()), o_t = ar.take<int>(trip.size());
+    const size_t o_s = ar.take<uint8_t>(status.size()), o_i = ar.take<double>(invs.size());
+    rc = ensure_init(c, ar.off);
+    if (rc != PFMPE_OK) {
+      c->timing_now = false;
+      return rc;
+    }
+    unsigned char* d = c->d_init.get();
+    double* d_blobs = (double*)(d + o_blobs);
+    double* d_iv = (double*)(d + o_iv);
+    HIPCHK(c, hipMemcpyAsync(d_blobs, blobs, 2 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_c, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + o_t, trip.data(), trip.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_init_prep, dim3((B + 255) / 256), dim3(256), 0, c->stream, ia, d_blobs, d_iv);
+    HIPCHK(c, hipGetLastError());
+    const unsigned grid = (unsigned)((ia.items + kInitBlock - 1) / kInitBlock);
+    const double ct = p.certainty_threshold;
+    RET(launch(c, PFMPE_K_P3P_CHECK, [&] {
+      const int nu = M - 3;
+      if (nu <= 2)
+        hipLaunchKernelGGL((k_p3p_check<2>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct, d_blobs, d_iv,
+                           (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
+      else if (nu <= 9)
+        hipLaunchKernelGGL((k_p3p_check<9>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct, d_blobs, d_iv,
+                           (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
+      else
+        hipLaunchKernelGGL((k_p3p_check<kMaxMarkers - 3>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct,
+                           d_blobs, d_iv, (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
+    }));
+    HIPCHK(c, hipMemcpyAsync(status.data(), d + o_s, status.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(invs.data(), d + o_i, invs.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (c->timing_now) RET(harvest_timing(c));
+  c->timing_now = false;
+
+  std::vector<double> est;  // stored P3P poses in store order (estimate k at slot N - k)
+  book_keeping(c, cands, status.data(), invs.data(), N, p, flag, out, est);
+  if (!out->found) return PFMPE_OK;
 
   // ---- seed the particle set: PoseParticle -> newPoseEstimation_Vec (PE:182-191)
-  const int K = n_est - 1;
+  const int K = out->n_estimates;
   RET(ensure_xfer(c));
   {
     Arena ar;
@@ -806,6 +1493,50 @@ int pfmpe_initialise(pfmpe_ctx* c, const double* blobs, int B, const pfmpe_init_
     RET(import_prior(c, N, est.data()));  // anchor (fp16 state): the first stored estimate
   }
   return PFMPE_OK;
+}
+
+int pfmpe_initialise_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_init_in* in, const pfmpe_init_params* prm,
+                           pfmpe_init_out* out, uint32_t* const* hist_out) {
+  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+  pfmpe_ctx* c0 = ctxs[0];
+  if (!in || !out) return fail(c0, PFMPE_E_ARG, "initialise_multi: null in/out");
+  if (S > PFMPE_INIT_MAX_STREAMS) return fail(c0, PFMPE_E_CAP, "initialise_multi: S exceeds PFMPE_INIT_MAX_STREAMS");
+  std::vector<MultiStream> st(S);
+  bool any = false;  // a stream that reaches the device
+  for (int s = 0; s < S; ++s) {
+    pfmpe_ctx* c = ctxs[s];
+    const std::string at = "initialise_multi: stream " + std::to_string(s) + ": ";
+    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
+    for (int e = 0; e < s; ++e)
+      if (ctxs[e] == c) return fail(c0, PFMPE_E_ARG, at + "context appears twice");
+    if (c->device != c0->device) return fail(c0, PFMPE_E_ARG, at + "device must match ctxs[0]");
+    if (in[s].B < 0 || (in[s].B > 0 && !in[s].blobs)) return fail(c0, PFMPE_E_ARG, at + "bad arguments");
+    if (!c->has_model) return fail(c0, PFMPE_E_STATE, at + "set_model first");
+    if (c->M < 3) return fail(c0, PFMPE_E_ARG, at + "needs M >= 3 markers");
+    if (in[s].B > c->max_blobs) return fail(c0, PFMPE_E_CAP, at + "B exceeds max_blobs");
+    MultiStream& m = st[s];
+    m.c = c;
+    m.blobs = in[s].blobs;
+    m.B = in[s].B;
+    m.p = effective_params(prm ? prm + s : nullptr);
+    m.N = m.p.n_particles > 0 ? m.p.n_particles : (c->has_prior ? c->N : c->max_particles);
+    if (m.N > c->max_particles) return fail(c0, PFMPE_E_CAP, at + "n_particles exceeds max_particles");
+    m.o.first_match = -1;
+    if (m.B < c->M)  // PE:1507-1512: the PF initialisation needs every marker detected
+      m.o.flag_fail = 10;
+    else
+      any = true;
+  }
+  if (!any) {  // as S single calls: nothing touches the device
+    for (int s = 0; s < S; ++s) out[s] = st[s].o;
+    return PFMPE_OK;
+  }
+  const size_t ev_mark = c0->ev_used;  // pending brackets of earlier frames
+  c0->timing_now = c0->timing > 0;
+  const int rc = multi_run(ctxs, st, out, hist_out);
+  c0->timing_now = false;
+  if (rc != PFMPE_OK && c0->ev_used > ev_mark) c0->ev_used = ev_mark;  // this call's unharvested brackets are dropped
+  return rc;
 }
 
 }  // extern "C"

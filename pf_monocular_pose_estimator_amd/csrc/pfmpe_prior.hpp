@@ -35,9 +35,11 @@ __global__ void k_export(const SP* __restrict__ st, double* __restrict__ poses, 
 
 namespace pfmpe_impl {
 
-// Install d_xfer's first N poses as the prior, stored in particle order: the import launch (anchor: the fp16
-// state's anchor pose), the hand-off state zeroed for the first frame, all waited for.
-inline int import_prior(pfmpe_ctx* c, int N, const double* anchor) {
+// Install d_xfer's first N poses as the prior, stored in particle order, in two steps.  import_enqueue: the import
+// launch (anchor: the fp16 state's anchor pose) and the hand-off state zeroed for the first frame, on stream `on`
+// (the context's own, or a batch leader's); errors are reported on `err`.  import_done: the context's bookkeeping,
+// once that work has been waited for.
+inline int import_enqueue(pfmpe_ctx* c, int N, const double* anchor, hipStream_t on, pfmpe_ctx* err) {
   std::memcpy(c->anchor[c->prior_idx], anchor, 12 * sizeof(double));
   c->prior_owner = -1;
   visit_state(c, [&](auto s) {
@@ -45,32 +47,41 @@ inline int import_prior(pfmpe_ctx* c, int N, const double* anchor) {
     using SP = typename decltype(s)::SP;
     Pose12<T> a;
     for (int q = 0; q < 12; ++q) a.v[q] = (T)anchor[q];
-    hipLaunchKernelGGL((k_import<T, SP>), dim3((N + 255) / 256), dim3(256), 0, c->stream, c->d_xfer.get(),
+    hipLaunchKernelGGL((k_import<T, SP>), dim3((N + 255) / 256), dim3(256), 0, on, c->d_xfer.get(),
                        (SP*)c->d_state[c->prior_idx].get(), N, c->ld, a);
   });
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemsetAsync(c->d_ctrl.get(), 0, sizeof(Ctrl), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_winkey.get(), 0, kWinBytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_counters.get(), 0, counters_bytes(c), c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(err, hipGetLastError());
+  HIPCHK(err, hipMemsetAsync(c->d_ctrl.get(), 0, sizeof(Ctrl), on));
+  HIPCHK(err, hipMemsetAsync(c->d_winkey.get(), 0, kWinBytes, on));
+  HIPCHK(err, hipMemsetAsync(c->d_counters.get(), 0, counters_bytes(c), on));
+  return PFMPE_OK;
+}
+inline void import_done(pfmpe_ctx* c, int N) {
   c->N = N;
   c->has_prior = true;
   c->has_last = false;
+}
+// both steps on the context's own stream, waited for
+inline int import_prior(pfmpe_ctx* c, int N, const double* anchor) {
+  RET(import_enqueue(c, N, anchor, c->stream, c));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  import_done(c, N);
   return PFMPE_OK;
 }
 
-// The prior's first `count` particles -> d_xfer (enqueued; through the owner indices of a deferred prior).
-inline int export_prior(pfmpe_ctx* c, int count) {
+// The prior's first `count` particles -> d_xfer (enqueued on `on`; through the owner indices of a deferred prior).
+inline int export_prior(pfmpe_ctx* c, int count, hipStream_t on, pfmpe_ctx* err) {
   visit_state(c, [&](auto s) {
     using T = typename decltype(s)::T;
     using SP = typename decltype(s)::SP;
     Pose12<T> a;
     for (int q = 0; q < 12; ++q) a.v[q] = (T)c->anchor[c->prior_idx][q];
-    hipLaunchKernelGGL((k_export<T, SP>), dim3((count + 255) / 256), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL((k_export<T, SP>), dim3((count + 255) / 256), dim3(256), 0, on,
                        (const SP*)c->d_state[c->prior_idx].get(), c->d_xfer.get(), count, c->ld, a, prior_owner_ptr(c));
   });
-  HIPCHK(c, hipGetLastError());
+  HIPCHK(err, hipGetLastError());
   return PFMPE_OK;
 }
+inline int export_prior(pfmpe_ctx* c, int count) { return export_prior(c, count, c->stream, c); }
 
 }  // namespace pfmpe_impl

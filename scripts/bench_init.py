@@ -4,6 +4,11 @@ Prints one JSON line: the histogram stage (k_p3p_hist, the hot part: C(B,3) x P(
 given (M, B) — device time from HIP events and wall time through the C-ABI — and the whole
 pfmpe_initialise on a realistic track-loss frame, each beside the CPU oracle (oracle/init_oracle.cpp,
 the reference's algorithm restated, 1 thread).
+
+--streams S prints another JSON line instead: pfmpe_initialise_multi over S contexts against S sequential
+pfmpe_initialise calls on the same contexts and inputs, on the track-loss frame (M = 5, B = 8,
+N = 1000) or at --B blobs: wall time of both (mean, min, max over the repetitions, two rounds of each) and the
+k_p3p_hist / k_p3p_check brackets of both.
 """
 import argparse
 import json
@@ -21,14 +26,100 @@ import pf_monocular_pose_estimator_amd as pf  # noqa: E402
 from pf_monocular_pose_estimator_amd import synthetic as syn  # noqa: E402
 
 
+def spread(xs):
+    return {"mean_us": float(np.mean(xs)) * 1e6, "min_us": float(np.min(xs)) * 1e6, "max_us": float(np.max(xs)) * 1e6}
+
+
+def streams(a):
+    """--streams S: pfmpe_initialise_multi over S contexts beside S sequential pfmpe_initialise calls on the same
+    contexts and inputs, in one process: wall time per repetition (timing off), then the k_p3p_hist / k_p3p_check
+    brackets of a second pass (timing on: the leader's for the batch, every context's summed for the loop)."""
+    S, M, N = a.streams, a.M, 1000
+    B = a.B if a.B is not None else M + 3  # the track-loss frame of DESIGN.md §4.7: every marker + 3 outliers
+    blobs = [syn.init_blobs(M, B - M, seed=s if B == M + 3 else 2 + s, noise_px=0.0 if B == M + 3 else 0.3)[0]
+             for s in range(S)]
+    engs = []
+    for _ in range(S):
+        e = pf.Engine(device=0, max_particles=N, state_dtype=pf.STATE_F64)
+        e.set_model(syn.markers_for(M), syn.K_README)
+        e.set_params(pf.default_params())
+        engs.append(e)
+    capped = [0, 0]
+
+    def batch():
+        try:
+            return [r[0]["found"] for r in pf.Engine.initialise_multi(engs, blobs, n_particles=N, want_hist=False)]
+        except pf.PFError as err:  # a candidate explosion (large B): stage 1 ran, which is what is timed there
+            if err.code != pf.E_CAP:
+                raise
+            capped[0] += 1
+            return None
+
+    def loop():
+        found = []
+        for e, b in zip(engs, blobs):
+            try:
+                found.append(e.initialise(b, n_particles=N)[0]["found"])
+            except pf.PFError as err:
+                if err.code != pf.E_CAP:
+                    raise
+                capped[1] += 1
+                found.append(None)
+        return found
+
+    def wall(fn):
+        ts = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return ts
+
+    for _ in range(3):
+        f_batch, f_loop = batch(), loop()
+    w_batch, w_loop = wall(batch), wall(loop)
+    w_batch2, w_loop2 = wall(batch), wall(loop)  # a second round of each: drift between the two shows up here
+    for e in engs:
+        e.set_option(pf.OPT_TIMING, 1)
+        e.reset_kernel_stats()
+    for _ in range(a.reps):
+        batch()
+    kb = engs[0].kernel_stats()
+    others = sum(v[0] for e in engs[1:] for v in e.kernel_stats().values())
+    for e in engs:
+        e.reset_kernel_stats()
+    for _ in range(a.reps):
+        loop()
+    kl = [e.kernel_stats() for e in engs]
+    res = {"metric": "pfmpe_initialise_multi against S sequential pfmpe_initialise calls, wall per frame of S objects",
+           "config": {"S": S, "M": M, "B": B, "N": N, "reps": a.reps},
+           "batch_wall": spread(w_batch + w_batch2), "loop_wall": spread(w_loop + w_loop2),
+           "batch_wall_rounds_us": [float(np.mean(w_batch)) * 1e6, float(np.mean(w_batch2)) * 1e6],
+           "loop_wall_rounds_us": [float(np.mean(w_loop)) * 1e6, float(np.mean(w_loop2)) * 1e6],
+           "batch_k_p3p_hist_us": kb["k_p3p_hist"][1] / max(kb["k_p3p_hist"][0], 1) * 1e3,
+           "batch_k_p3p_check_us": kb["k_p3p_check"][1] / max(kb["k_p3p_check"][0], 1) * 1e3,
+           "batch_brackets_per_rep": kb["k_p3p_hist"][0] / a.reps, "batch_launches_on_members": others,
+           "loop_k_p3p_hist_sum_us": sum(k["k_p3p_hist"][1] for k in kl) / a.reps * 1e3,
+           "loop_k_p3p_check_sum_us": sum(k["k_p3p_check"][1] for k in kl) / a.reps * 1e3,
+           "found_batch": f_batch, "found_loop": f_loop, "candidate_cap_hits": {"batch": capped[0], "loop": capped[1]}}
+    res["value"] = res["loop_wall"]["mean_us"] / res["batch_wall"]["mean_us"]
+    res["unit"] = "x (loop wall / batch wall)"
+    print(json.dumps(res))
+    for e in engs:
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--M", type=int, default=5)
-    ap.add_argument("--B", type=int, default=50)
+    ap.add_argument("--B", type=int, default=None, help="blobs (default 50; with --streams: M + 3)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--cpu", type=int, default=1, help="time the CPU oracle too (0 = skip)")
+    ap.add_argument("--streams", type=int, default=0, help="S > 0: time the batch call against S single calls")
     a = ap.parse_args()
-    M, B = a.M, a.B
+    if a.streams > 0:
+        return streams(a)
+    M, B = a.M, a.B if a.B is not None else 50
     blobs, _ = syn.init_blobs(M, B - M, seed=2, noise_px=0.3)
     eng = pf.Engine(device=0, max_particles=1000, state_dtype=pf.STATE_F64)
     eng.set_model(syn.markers_for(M), syn.K_README)
