@@ -242,12 +242,14 @@ typedef struct {
   uint64_t hist_total;      /* sum of the histogram                                                 */
 } pfmpe_init_out;
 void pfmpe_default_init_params(pfmpe_init_params* p);
-/* Stage 1 alone: hist (B x M uint32, row-major: hist[blob * M + marker]).  3 <= B <= max_blobs. */
+/* Stage 1 alone: hist (B x M uint32, row-major: hist[blob * M + marker]).  3 <= B <= max_blobs (B < M included,
+ * where pfmpe_initialise stops at flag 10): stage 1 of the batch below for one stream. */
 int pfmpe_p3p_histogram(pfmpe_ctx* ctx, const double* blobs, int B, uint32_t* hist);
 /* The whole initialise().  On success (out->found) the context's particle set becomes PoseParticle
  * (newPoseEstimation_Vec = PoseParticle, PE:191): slot N-k holds the k-th stored P3P pose (k = 1..K),
  * slots below repeat them with period K (the fill loop), and slot 0 keeps the resident set's slot 0
- * (identity if there is none) unless K >= N.  hist (optional, B x M) receives stage 1's histogram. */
+ * (identity if there is none) unless K >= N.  hist (optional, B x M) receives stage 1's histogram.  The call is
+ * pfmpe_initialise_multi (below) with S = 1: the same kernels and host stages, on ctx's stream and scratch. */
 int pfmpe_initialise(pfmpe_ctx* ctx, const double* blobs, int B, const pfmpe_init_params* params,
                      pfmpe_init_out* out, uint32_t* hist);
 
@@ -260,8 +262,8 @@ int pfmpe_initialise(pfmpe_ctx* ctx, const double* blobs, int B, const pfmpe_ini
  * B_s x M_s) belong to ctxs[s].  out[s], hist[s] and the particle set of ctxs[s] afterwards are what
  * pfmpe_initialise(ctxs[s], in[s].blobs, in[s].B, &params[s], &out[s], hist[s]) gives: out[s] byte for byte
  * (predicted_pose included), the histogram entry for entry, the seeded prior the same bits from
- * pfmpe_get_particles(ctxs[s], 1, ...); the counts are order-free integer sums of per-item decisions and the host
- * stages are the same code on the same inputs.  Per stream: M, the markers, K and params.tol (from the context), B,
+ * pfmpe_get_particles(ctxs[s], 1, ...): the single call is the batch of one, the counts are order-free integer sums
+ * of per-item decisions, and the host stages run per stream.  Per stream: M, the markers, K and params.tol (from the context), B,
  * every field of params[s], and N by the single call's rule.  Contexts of any state types may be mixed (the device
  * stages are fp64, only the final import is typed); they must be distinct and on one device.  ctxs[0] leads: the
  * batch runs on its stream and in its initialisation scratch (grown once per stage to the batch's size), fills its
@@ -288,8 +290,8 @@ int pfmpe_initialise_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_init_in* i
 
 /* host-only (no GPU, no context): the work mapping of the batch's histogram stage, which the call above launches
  * exactly.  Streams are grouped by the unused-marker bucket of their M (one launch per bucket present).  A stream
- * wants ceil(items / 256) blocks of 256 threads; a bucket's launch holds at most 8 * max(num_cu, 1) blocks, the single
- * call's cap; when the wants of a bucket exceed it, stream s gets floor(want_s * cap / wants) blocks, and one block
+ * wants ceil(items / 256) blocks of 256 threads; a bucket's launch holds at most 8 * max(num_cu, 1) blocks;
+ * when the wants of a bucket exceed it, stream s gets floor(want_s * cap / wants) blocks, and one block
  * where that is zero, so the launch exceeds the cap by at most one block per stream with work.  Block b (counted from
  * first_block) of a stream with `blocks` blocks visits the items b * 256 + t + k * blocks * 256 (thread t, round k).
  * blocks_per_bucket: the three launches' sizes (0: no launch).  PFMPE_E_ARG for a NULL pointer, S outside

@@ -173,8 +173,9 @@ struct pfmpe_ctx : CtxQueue {
   Buf<uint32_t> d_pairs; // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
   Buf<unsigned char> d_refine; // Gauss-Newton refinement scratch (RefineBuf layout, pfmpe_refine_*)
   Buf<unsigned char> d_init;       // initialisation scratch (pfmpe_init.hip), grown on demand
-  // pfmpe_initialise_multi (owned by the batch's first context): the pinned block its read-backs land in (every
-  // stream's histogram; every stream's check results), grown on demand
+  // the initialisation (owned by the batch's first context; pfmpe_initialise and pfmpe_p3p_histogram are batches of
+  // one): the pinned block its read-backs land in (every stream's histogram; every stream's check results), grown on
+  // demand
   Buf<unsigned char, Mem::Pinned> h_init;
   Buf<unsigned char> d_det;        // detector scratch (pfmpe_detect.hip), grown on demand
   Buf<uint8_t> d_img;              // staged camera image (pfmpe_stage_image), grown on demand

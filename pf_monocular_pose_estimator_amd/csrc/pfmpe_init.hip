@@ -1,16 +1,16 @@
 // pfmpe_init.hip — brute-force P3P (re)initialisation on the device, and its
-// C-ABI entry points pfmpe_p3p_histogram / pfmpe_initialise (include/pfmpe.h).
+// C-ABI entry points pfmpe_p3p_histogram / pfmpe_initialise / pfmpe_initialise_multi (include/pfmpe.h).
 //
 // Replaces PoseEstimator::initialise (pf_mpe_lib/src/pose_estimator.cpp:1503-1786, "PE") for the
 // particle-filter configuration.  Work split:
-//   device  k_init_prep   calculateImageVectors (PE:1072-1085), one thread per blob
-//           k_p3p_filter  the 3-blob spread filter (PE:1554-1581), one thread per combination
-//           k_p3p_hist    the histogram (PE:1543-1716): one thread per (combination, ordered marker
-//                         triple), P3P + 4 back projections, exact x-window pruning of the
-//                         nearest-projection search, LDS histogram flushed with integer atomics
-//           k_p3p_check   checkCorrespondences' P3P stage (PE:1331-1475), one thread per
-//                         (candidate correspondence vector, 3-subset)
-//           k_init_seed   the particle seeding + fill loop (PE:1429-1437, 1755-1760) into the state
+//   device  k_init_prep_multi   calculateImageVectors (PE:1072-1085), one thread per blob
+//           k_p3p_filter_multi  the 3-blob spread filter (PE:1554-1581), one thread per combination
+//           k_p3p_hist_multi    the histogram (PE:1543-1716): one thread per (combination, ordered marker
+//                               triple), P3P + 4 back projections, exact x-window pruning of the
+//                               nearest-projection search, LDS histogram flushed with integer atomics
+//           k_p3p_check_multi   checkCorrespondences' P3P stage (PE:1331-1475), one thread per
+//                               (candidate correspondence vector, 3-subset)
+//           k_init_seed_multi   the particle seeding + fill loop (PE:1429-1437, 1755-1760) into the state
 //   host    candidate vectors from the histogram (PE:1134-1288), the ordered bookkeeping of
 //           checkCorrespondences (flags, particle slots, mean re-projections, PE:1425-1496) and
 //           computeTransformation (PE:2139-2161)
@@ -18,9 +18,9 @@
 // and marker triples in any order; the reference's lexicographic order only matters for
 // checkCorrespondences (particle slot order), which keeps it.
 //
-// pfmpe_initialise_multi runs the same stages for S contexts as one batch: the *_multi kernels below share the
-// per-element bodies with the kernels above and are driven by per-stream descriptors in device memory; the host
-// stages are the same functions, called per stream (the work mapping of its histogram stage: pfmpe_init_plan.hpp).
+// There is one set of kernels and one host path: a batch of S contexts, driven by per-stream descriptors in device
+// memory, the host stages called per stream (the work mapping of the histogram stage: pfmpe_init_plan.hpp).
+// pfmpe_initialise is the batch of one; pfmpe_p3p_histogram is stage 1 of a batch of one.
 #include "pfmpe_init_plan.hpp"
 #include "pfmpe_prior.hpp"
 #include "pf_p3p.hpp"
@@ -105,12 +105,6 @@ __device__ __forceinline__ void prep_blob(const InitArgs& ia, const double* __re
   for (int k = 0; k < 3; ++k) iv[3 * i + k] = v[k] / n;
 }
 
-__global__ void k_init_prep(const InitArgs ia, const double* __restrict__ blobs, double* __restrict__ iv) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= ia.B) return;
-  prep_blob(ia, blobs, iv, i);
-}
-
 __device__ __forceinline__ double sqd(double ax, double ay, double bx, double by) {
   const double dx = ax - bx, dy = ay - by;
   return dx * dx + dy * dy;
@@ -136,22 +130,13 @@ __device__ __forceinline__ void filter_comb(int B, const double* __restrict__ bl
   pass[r] = ok ? 1 : 0;
 }
 
-__global__ void k_p3p_filter(const InitArgs ia, const double* __restrict__ blobs, uint8_t* __restrict__ pass) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= ia.ncomb) return;
-  filter_comb(ia.B, blobs, pass, r);
-}
-
-
 // Stage 1: one thread per (colex combination, ordered marker triple), grid-stride.  HLDS: histogram in
 // LDS (flushed once per block with integer atomics) or straight to global atomics for large B x M.
-// Dynamic LDS: sorted blob x, y (doubles), original index (int), then the LDS histogram.
+// The block's LDS carve: sorted blob x, y (doubles), original index (int), then the LDS histogram.
 //
-// hist_block: one block's share of one stream's histogram in the batch kernel (k_p3p_hist_multi): the items first,
-// first + stride, ... of ia.items; Kc = the camera matrix where the block keeps it (LDS), lds = the block's carve
-// (laid out as above), s_mk = its marker table.  The per-item body is k_p3p_hist's, statement for statement: the
-// single-stream kernel below keeps its own copy, because calling this function from it changed its register
-// allocation and schedule (scripts/device_code_diff.py), and its assembly is what DESIGN.md §4.7 measured.
+// hist_block: one block's share of one stream's histogram (k_p3p_hist_multi): the items first, first + stride, ...
+// of ia.items; Kc = the camera matrix where the block keeps it (LDS), lds = the block's carve (laid out as above),
+// s_mk = its marker table.
 template <int MAXU, bool HLDS>
 __device__ __forceinline__ void hist_block(const InitArgs& ia, const double* Kc, unsigned char* lds, double* s_mk,
                                            int64_t first, int64_t stride, const double* __restrict__ blobs,
@@ -261,125 +246,12 @@ __device__ __forceinline__ void hist_block(const InitArgs& ia, const double* Kc,
   }
 }
 
-template <int MAXU, bool HLDS>
-__global__ __launch_bounds__(kInitBlock, PFMPE_P3P_MINB) void k_p3p_hist(const InitArgs ia, const double* __restrict__ blobs,
-                                                          const double* __restrict__ iv,
-                                                          const double* __restrict__ sorted_xy,
-                                                          const int* __restrict__ sorted_idx,
-                                                          const uint8_t* __restrict__ pass,
-                                                          uint32_t* __restrict__ hist) {
-  extern __shared__ __align__(16) unsigned char lds[];
-  __shared__ double s_mk[kMaxMarkers * 3];
-  const int B = ia.B, M = ia.M;
-  double* sx = (double*)lds;
-  double* sy = sx + B;
-  int* sidx = (int*)(sy + B);
-  uint32_t* lh = (uint32_t*)(sidx + ((B + 3) & ~3));
-  for (int i = threadIdx.x; i < B; i += blockDim.x) {
-    sx[i] = sorted_xy[2 * i];
-    sy[i] = sorted_xy[2 * i + 1];
-    sidx[i] = sorted_idx[i];
-  }
-  for (int i = threadIdx.x; i < 3 * M; i += blockDim.x) s_mk[i] = ia.markers[i];
-  if (HLDS)
-    for (int i = threadIdx.x; i < B * M; i += blockDim.x) lh[i] = 0;
-  __syncthreads();
-  uint32_t* H = HLDS ? lh : hist;
-  const double tol = ia.tol, win = ia.win;
-  const int nuo = M - 3;
-
-  for (int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; item < ia.items;
-       item += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = item / ia.nperm;
-    const int p = (int)(item - r * ia.nperm);
-    if (!pass[r]) continue;
-    int sa[3];
-    unrank3(r, sa[0], sa[1], sa[2]);
-    int pm[3];
-    perm3(p, M, pm[0], pm[1], pm[2]);
-    double fv[3][3], wp[3][3];
-    for (int k = 0; k < 3; ++k)
-      for (int q = 0; q < 3; ++q) {
-        fv[k][q] = iv[3 * sa[k] + q];
-        wp[k][q] = s_mk[3 * pm[k] + q];
-      }
-    p3p::Setup st;
-    double roots[4];
-    if (!p3p::setup(fv, wp, st, roots)) continue;
-    int un[MAXU > 0 ? MAXU : 1];
-    unused_markers<MAXU>(pm[0], pm[1], pm[2], un);
-    const double dmx = (blobs[2 * sa[0]] + blobs[2 * sa[1]] + blobs[2 * sa[2]]) / 3;
-    const double dmy = (blobs[2 * sa[0] + 1] + blobs[2 * sa[1] + 1] + blobs[2 * sa[2] + 1]) / 3;
-    double prev[12];
-    for (int k = 0; k < 4; ++k) {
-      double sol[12];
-      p3p::solution(st, roots[k], sol);
-      bool repeated = false;  // (solutions(k) - solutions(k-1)).all() == 0: some entry unchanged
-      if (k > 0)
-        for (int q = 0; q < 12; ++q) repeated = repeated || (sol[q] - prev[q] == 0);
-      for (int q = 0; q < 12; ++q) prev[q] = sol[q];
-      if (repeated || !p3p::finite12(sol)) continue;
-      double inv[12];
-      p3p::inverse34(sol, inv);
-      double pu[MAXU > 0 ? MAXU : 1], pv[MAXU > 0 ? MAXU : 1];
-#pragma unroll
-      for (int m = 0; m < MAXU; ++m)
-        if (m < nuo) p3p::project(ia.K, inv, &s_mk[3 * un[m]], pu[m], pv[m]);
-      bool any = false;
-#pragma unroll
-      for (int m = 0; m < MAXU; ++m) {
-        if (m >= nuo) break;
-        const double u = pu[m];
-        if (!(fabs(u) < 1e300) || !(fabs(pv[m]) < 1e300)) continue;  // NaN / inf never wins a strict '<'
-        int lo = 0, hi = B;                                           // first sx >= u - win
-        const double xl = u - win, xh = u + win;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (sx[mid] < xl) lo = mid + 1;
-          else hi = mid;
-        }
-        for (int q = lo; q < B && sx[q] <= xh; ++q) {
-          const int bi = sidx[q];
-          if (bi == sa[0] || bi == sa[1] || bi == sa[2]) continue;
-          const double bx = sx[q], by = sy[q];
-          if (!(sqd(dmx, dmy, bx, by) < kThreshDist)) continue;
-          // calculateMinDistancesAndPairs (PE:2093-2137): nearest projection, strict '<' from +inf
-          double mind = INFINITY;
-          int pr = -1;
-#pragma unroll
-          for (int m2 = 0; m2 < MAXU; ++m2)
-            if (m2 < nuo) {
-              const double d = sqd(bx, by, pu[m2], pv[m2]);
-              if (d < mind) {
-                mind = d;
-                pr = m2;
-              }
-            }
-          if (pr != m || !(sqrt(mind) < tol)) continue;
-          if (!any) {
-            any = true;
-            for (int mm = 0; mm < 3; ++mm) atomicAdd(&H[sa[mm] * M + pm[mm]], 1u);
-          }
-          atomicAdd(&H[bi * M + un[m]], 1u);
-        }
-      }
-    }
-  }
-  if (HLDS) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < B * M; i += blockDim.x)
-      if (lh[i]) atomicAdd(&hist[i], lh[i]);
-  }
-}
-
 // Stage 3: checkCorrespondences' P3P part (PE:1331-1475) for candidate `ci`, lexicographic 3-subset q of
 // its M correspondence rows.  cand: per candidate 2*M ints (LED, detection), 1-based.
 // status: 0 = P3P failed (collinear), 1 = no solution within certainty_threshold, 2 = valid (inv = the
 // inverse of the smallest-error valid solution, top 3 rows).
 //
-// check_item: item `item` of one stream in the batch kernel (k_p3p_check_multi).  The body is k_p3p_check's,
-// statement for statement; as with hist_block the single-stream kernel keeps its own copy, since calling this
-// function from it changed its assembly.
+// check_item: item `item` of one stream (k_p3p_check_multi).
 template <int MAXU>
 __device__ __forceinline__ void check_item(const InitArgs& ia, double certainty_threshold,
                                            const double* __restrict__ blobs, const double* __restrict__ iv,
@@ -459,101 +331,10 @@ __device__ __forceinline__ void check_item(const InitArgs& ia, double certainty_
     for (int k = 0; k < 12; ++k) out_inv[item * 12 + k] = best[k];
 }
 
-template <int MAXU>
-__global__ __launch_bounds__(kInitBlock) void k_p3p_check(const InitArgs ia, double certainty_threshold,
-                                                           const double* __restrict__ blobs,
-                                                           const double* __restrict__ iv,
-                                                           const int* __restrict__ cand,
-                                                           const int* __restrict__ triples,
-                                                           uint8_t* __restrict__ status, double* __restrict__ out_inv) {
-  const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= ia.items) return;
-  const int ci = (int)(item / ia.ncomb_m);
-  const int q = (int)(item - (int64_t)ci * ia.ncomb_m);
-  const int M = ia.M;
-  const int* cp = cand + (int64_t)ci * 2 * M;
-  const int t = triples[q];
-  const int s[3] = {t & 0xff, (t >> 8) & 0xff, (t >> 16) & 0xff};
-  double fv[3][3], wp[3][3];
-  for (int k = 0; k < 3; ++k)
-    for (int d = 0; d < 3; ++d) {
-      wp[k][d] = ia.markers[3 * (cp[2 * s[k]] - 1) + d];
-      fv[k][d] = iv[3 * (cp[2 * s[k] + 1] - 1) + d];
-    }
-  int un[MAXU > 0 ? MAXU : 1];
-  unused_markers<MAXU>(s[0], s[1], s[2], un);
-  const int nu = M - 3;
-  p3p::Setup st;
-  double roots[4];
-  if (!p3p::setup(fv, wp, st, roots)) {
-    status[item] = 0;
-    return;
-  }
-  const double tol2 = ia.tol * ia.tol;  // pow(tol, 2) folds to tol * tol
-  double min_err = INFINITY;
-  double best[12];
-  bool any_valid = false;
-  for (int j = 0; j < 4; ++j) {
-    double sol[12];
-    p3p::solution(st, roots[j], sol);
-    if (!p3p::finite12(sol)) continue;
-    double inv[12];
-    p3p::inverse34(sol, inv);
-    // calculateSquaredReprojectionErrorAndCertainty (PE:1087-1132): index-paired squared distances,
-    // then up to min(size) extractions of Eigen's minCoeff (first minimum, from coeff(0)) while <= tol^2
-    double dist[MAXU > 0 ? MAXU : 1];
-#pragma unroll
-    for (int a = 0; a < MAXU; ++a)
-      if (a < nu) {
-        double u, v;
-        p3p::project(ia.K, inv, &ia.markers[3 * (cp[2 * un[a]] - 1)], u, v);
-        const int bi = cp[2 * un[a] + 1] - 1;
-        dist[a] = sqd(blobs[2 * bi], blobs[2 * bi + 1], u, v);
-      }
-    double sq_err = 0;
-    int ncorr = 0;
-    for (int it = 0; it < nu; ++it) {
-      double mv = dist[0];
-      int r = 0;
-#pragma unroll
-      for (int a = 1; a < MAXU; ++a)
-        if (a < nu && dist[a] < mv) {
-          mv = dist[a];
-          r = a;
-        }
-      if (!(mv <= tol2)) break;
-      sq_err += mv;
-      ncorr++;
-#pragma unroll
-      for (int a = 0; a < MAXU; ++a)
-        if (a == r) dist[a] = INFINITY;
-    }
-    const double certainty = (double)ncorr / (double)nu;
-    if (certainty >= certainty_threshold) {
-      any_valid = true;
-      if (sq_err < min_err) {
-        min_err = sq_err;
-        for (int k = 0; k < 12; ++k) best[k] = inv[k];
-      }
-    }
-  }
-  status[item] = any_valid ? 2 : 1;
-  if (any_valid)
-    for (int k = 0; k < 12; ++k) out_inv[item * 12 + k] = best[k];
-}
-
-// Stage 4: PoseParticle after initialise (PE:1429-1437 stores, PE:1755-1760 fill): slot s >= 1 takes
-// estimate ((N - s - 1) mod K) + 1 (1-based, estimate k sits at slot N - k); slot 0 only when K >= N.
-__global__ void k_init_seed(const double* __restrict__ est, int K, int N, double* __restrict__ poses) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= N || (s == 0 && K < N)) return;
-  const int e = (N - s - 1) % K;  // 0-based estimate
-  for (int q = 0; q < 12; ++q) poses[12 * (int64_t)s + q] = est[12 * (int64_t)e + q];
-}
-
-// ---------------------------------------------------------------- the batch (pfmpe_initialise_multi)
-// S streams share each stage's launches.  A stage's descriptors (one InitDesc per stream, in device memory: S x 0.6 KB
-// do not belong in kernel arguments) and its head go up with the stage's one upload.  The flat kernels (prep, filter,
+// ---------------------------------------------------------------- the kernels: a batch of S streams
+// S streams (one for pfmpe_initialise and pfmpe_p3p_histogram) share each stage's launches.  A stage's descriptors
+// (one InitDesc per stream, in device memory: S x 0.6 KB do not belong in kernel arguments) and its head go up with
+// the stage's one upload.  The flat kernels (prep, filter,
 // check, seed) run over the concatenation of the streams' elements and find the stream of an element in a prefix
 // table of the head; a histogram block finds its stream from the plan's first_block.
 constexpr int kInitMaxStreams = PFMPE_INIT_MAX_STREAMS;
@@ -615,8 +396,8 @@ __global__ void k_p3p_filter_multi(const InitHead* __restrict__ hd, const InitDe
 
 // Stage 1 of the batch, one launch per unused-marker bucket present.  Block -> stream by a binary search over the
 // launch's first blocks (uniform: scalar code, once per block); then the block is block (blockIdx - first_block) of
-// `blocks` of a single-stream grid over that stream's items.  Dynamic LDS: K (16 doubles), then the single kernel's
-// carve for this stream; the launch is sized for its largest stream.
+// the `blocks` that stride over that stream's items.  Dynamic LDS: K (16 doubles), then hist_block's carve for this
+// stream; the launch is sized for its largest stream.
 template <int MAXU>
 __global__ __launch_bounds__(kInitBlock, PFMPE_P3P_MINB) void k_p3p_hist_multi(const InitHead* __restrict__ hd,
                                                                                 const InitDesc* __restrict__ descs,
@@ -655,7 +436,9 @@ __global__ __launch_bounds__(kInitBlock) void k_p3p_check_multi(const InitHead* 
                    g - hd->pre[1][s]);
 }
 
-// Stage 4 of the batch: k_init_seed over the slots of every found stream, each into its member's transfer block.
+// Stage 4 of the batch: PoseParticle after initialise (PE:1429-1437 stores, PE:1755-1760 fill) over the slots of every
+// found stream, each into its member's transfer block: slot s >= 1 takes estimate ((N - s - 1) mod K) + 1 (1-based,
+// estimate k sits at slot N - k); slot 0 only when K >= N.
 __global__ void k_init_seed_multi(const InitHead* __restrict__ hd, const InitDesc* __restrict__ descs) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int S = hd->S;
@@ -702,71 +485,6 @@ InitArgs make_args(const pfmpe_ctx* c, int B) {
   ia.ncomb_m = c->M * (c->M - 1) * (c->M - 2) / 6;
   ia.ncomb = (int64_t)B * (B - 1) * (B - 2) / 6;
   return ia;
-}
-
-template <int MAXU>
-void launch_hist(pfmpe_ctx* c, const InitArgs& ia, bool hlds, size_t lds, int grid, const double* blobs,
-                 const double* iv, const double* sxy, const int* sidx, const uint8_t* pass, uint32_t* hist) {
-  if (hlds)
-    hipLaunchKernelGGL((k_p3p_hist<MAXU, true>), dim3(grid), dim3(kInitBlock), lds, c->stream, ia, blobs, iv, sxy,
-                       sidx, pass, hist);
-  else
-    hipLaunchKernelGGL((k_p3p_hist<MAXU, false>), dim3(grid), dim3(kInitBlock), lds, c->stream, ia, blobs, iv, sxy,
-                       sidx, pass, hist);
-}
-
-// stage 1 on the device; hist (B x M) lands in host memory
-int run_histogram(pfmpe_ctx* c, const double* blobs, int B, uint32_t* hist) {
-  InitArgs ia = make_args(c, B);
-  ia.items = ia.ncomb * ia.nperm;
-  // host-built x-sorted blob list for the pruned search (a data-structure build, like the PF blob table)
-  std::vector<int> order(B);
-  for (int i = 0; i < B; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return blobs[2 * x] < blobs[2 * y]; });
-  std::vector<double> sxy(2 * (size_t)B);
-  for (int i = 0; i < B; ++i) {
-    sxy[2 * i] = blobs[2 * order[i]];
-    sxy[2 * i + 1] = blobs[2 * order[i] + 1];
-  }
-  Arena ar;
-  const size_t o_blobs = ar.take<double>(2 * (size_t)B), o_iv = ar.take<double>(3 * (size_t)B);
-  const size_t o_sxy = ar.take<double>(2 * (size_t)B), o_sidx = ar.take<int>(B);
-  const size_t o_pass = ar.take<uint8_t>((size_t)ia.ncomb), o_hist = ar.take<uint32_t>((size_t)B * c->M);
-  RET(ensure_init(c, ar.off));
-  unsigned char* d = c->d_init.get();
-  double* d_blobs = (double*)(d + o_blobs);
-  double* d_iv = (double*)(d + o_iv);
-  double* d_sxy = (double*)(d + o_sxy);
-  int* d_sidx = (int*)(d + o_sidx);
-  uint8_t* d_pass = d + o_pass;
-  uint32_t* d_hist = (uint32_t*)(d + o_hist);
-  HIPCHK(c, hipMemcpyAsync(d_blobs, blobs, 2 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_sxy, sxy.data(), sxy.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_sidx, order.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(d_hist, 0, (size_t)B * c->M * sizeof(uint32_t), c->stream));
-  hipLaunchKernelGGL(k_init_prep, dim3((B + 255) / 256), dim3(256), 0, c->stream, ia, d_blobs, d_iv);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_p3p_filter, dim3((unsigned)((ia.ncomb + 255) / 256)), dim3(256), 0, c->stream, ia, d_blobs,
-                     d_pass);
-  HIPCHK(c, hipGetLastError());
-  const size_t hist_bytes = (size_t)B * c->M * sizeof(uint32_t);
-  const bool hlds = hist_bytes <= 32 * 1024;
-  const size_t lds = (size_t)B * 16 + (size_t)((B + 3) & ~3) * 4 + (hlds ? hist_bytes : 0);
-  const int64_t want = (ia.items + kInitBlock - 1) / kInitBlock;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)std::max(c->num_cu, 1) * 8));
-  RET(launch(c, PFMPE_K_P3P_HIST, [&] {
-    const int nu = c->M - 3;
-    if (nu <= 2)
-      launch_hist<2>(c, ia, hlds, lds, grid, d_blobs, d_iv, d_sxy, d_sidx, d_pass, d_hist);
-    else if (nu <= 9)
-      launch_hist<9>(c, ia, hlds, lds, grid, d_blobs, d_iv, d_sxy, d_sidx, d_pass, d_hist);
-    else
-      launch_hist<kMaxMarkers - 3>(c, ia, hlds, lds, grid, d_blobs, d_iv, d_sxy, d_sidx, d_pass, d_hist);
-  }));
-  HIPCHK(c, hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->timing_now) RET(harvest_timing(c));
-  return PFMPE_OK;
 }
 
 // correspondencesFromHistogram (PE:1134-1288) with bInitialisation = true: candidate (LED, detection)
@@ -944,9 +662,9 @@ std::vector<int> lex_triples(int M) {
 }
 
 // The ordered bookkeeping of initialise / checkCorrespondences (PE:1425-1496, 1733-1760) over the candidates of one
-// context, for the single call and the batch alike: status / invs are stage 3's results for the candidates with M
-// rows, in candidate order; flag: the fail flag so far.  Fills out's found, flag_fail, n_estimates, first_match,
-// n_corr, corr and predicted_pose, and est: the stored P3P poses in store order (estimate k at slot N - k).
+// context: status / invs are stage 3's results for the candidates with M rows, in candidate order; flag: the fail
+// flag so far.  Fills out's found, flag_fail, n_estimates, first_match, n_corr, corr and predicted_pose, and est: the
+// stored P3P poses in store order (estimate k at slot N - k).
 void book_keeping(const pfmpe_ctx* c, const std::vector<std::vector<uint32_t>>& cands, const uint8_t* status,
                   const double* invs, int N, const pfmpe_init_params& p, int flag, pfmpe_init_out* out,
                   std::vector<double>& est) {
@@ -1015,10 +733,11 @@ pfmpe_init_params effective_params(const pfmpe_init_params* prm) {
   return p;
 }
 
-// ---------------------------------------------------------------- the batch (pfmpe_initialise_multi)
+// ---------------------------------------------------------------- the batch
 // one stream of the batch on the host
 struct MultiStream {
   pfmpe_ctx* c = nullptr;
+  std::string at;                           // what this stream's error texts begin with
   const double* blobs = nullptr;
   int B = 0, N = 0;
   pfmpe_init_params p{};
@@ -1054,12 +773,13 @@ struct StageImage {
 };
 
 // The leader's pinned read-back block, grown by half more than asked.  Pinned and kept: the check results of a batch
-// come back as one block, and with a fresh pageable vector per call a B = 50 batch of 8 was slower than 8 single
-// calls.
+// come back as one block, and with a fresh pageable vector per call a B = 50 batch of 8 took twice the time
+// (DESIGN.md §4.7a).
 int ensure_readback(pfmpe_ctx* c, size_t bytes) { return c->h_init.grow(c, bytes, bytes + bytes / 2); }
 
 // Stage 1 of the batch: the histograms of the streams with B >= M (at least one) into their MultiStream::hist.
-int multi_histograms(pfmpe_ctx* c0, std::vector<MultiStream>& st) {
+// hist_only (pfmpe_p3p_histogram): of the streams with 3 <= B < M as well.
+int multi_histograms(pfmpe_ctx* c0, std::vector<MultiStream>& st, bool hist_only) {
   const int S = (int)st.size();
   int32_t Ms[kInitMaxStreams], Bs[kInitMaxStreams], per_bucket[3];
   pfmpe_init_plan plan[kInitMaxStreams];
@@ -1067,7 +787,7 @@ int multi_histograms(pfmpe_ctx* c0, std::vector<MultiStream>& st) {
     Ms[s] = st[s].c->M;
     Bs[s] = st[s].B;
   }
-  pfmpe_plan::init_plan(Ms, Bs, S, c0->num_cu, plan, per_bucket);
+  pfmpe_plan::init_plan(Ms, Bs, S, c0->num_cu, plan, per_bucket, hist_only);
   StageImage im(S);
   im.begin();
   // upload part: per stream the blobs, the x-sorted list and its indices; device part: image vectors, filter
@@ -1080,7 +800,7 @@ int multi_histograms(pfmpe_ctx* c0, std::vector<MultiStream>& st) {
     if (plan[s].items == 0) continue;
     const int B = st[s].B;
     const double* blobs = st[s].blobs;
-    // host-built x-sorted blob list for the pruned search, as run_histogram's
+    // host-built x-sorted blob list for the pruned search (a data-structure build, like the PF blob table)
     std::vector<int> order(B);
     for (int i = 0; i < B; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return blobs[2 * x] < blobs[2 * y]; });
@@ -1291,8 +1011,10 @@ int multi_seed(pfmpe_ctx* c0, std::vector<MultiStream>& st) {
   return PFMPE_OK;
 }
 
-// the validated batch: stages 1 to 4 on the leader's stream, then out / the members' ordering state
-int multi_run(pfmpe_ctx* const* ctxs, std::vector<MultiStream>& st, pfmpe_init_out* out, uint32_t* const* hist_out) {
+// The validated batch: stages 1 to 4 on the leader's stream, then out / the members' ordering state.  single: the
+// batch of one of pfmpe_initialise, which reports a failed allocation of its transfer block as it is.
+int multi_run(pfmpe_ctx* const* ctxs, std::vector<MultiStream>& st, pfmpe_init_out* out, uint32_t* const* hist_out,
+              bool single) {
   pfmpe_ctx* c0 = ctxs[0];
   const int S = (int)st.size();
   RET(set_device(c0));
@@ -1300,7 +1022,7 @@ int multi_run(pfmpe_ctx* const* ctxs, std::vector<MultiStream>& st, pfmpe_init_o
   // ordering state back (the leader's own was set by set_device)
   OrderGuard members(ctxs, S);
   RET(members.order(1, c0->stream, c0));
-  RET(multi_histograms(c0, st));
+  RET(multi_histograms(c0, st, false));
   for (int s = 0; s < S; ++s)
     if (hist_out && hist_out[s] && !st[s].hist.empty())
       std::memcpy(hist_out[s], st[s].hist.data(), st[s].hist.size() * sizeof(uint32_t));
@@ -1314,8 +1036,7 @@ int multi_run(pfmpe_ctx* const* ctxs, std::vector<MultiStream>& st, pfmpe_init_o
       m.o.flag_fail = 12;
       continue;
     }
-    RET(candidates(c0, "initialise_multi: stream " + std::to_string(s) + ": ", m.B, m.c->M, m.hist.data(),
-                   m.p.max_candidates, m.cands));
+    RET(candidates(c0, m.at, m.B, m.c->M, m.hist.data(), m.p.max_candidates, m.cands));
     m.o.n_candidates = (int)m.cands.size();
     m.flag = m.cands.empty() ? 11 : -1;
     for (size_t i = 0; i < m.cands.size(); ++i)
@@ -1333,14 +1054,46 @@ int multi_run(pfmpe_ctx* const* ctxs, std::vector<MultiStream>& st, pfmpe_init_o
     book_keeping(m.c, m.cands, status + m.st_off, invs + m.st_off * 12, m.N, m.p, m.flag, &m.o, m.est);
     if (m.o.found) {
       any_found = true;
-      if (ensure_xfer(m.c) != PFMPE_OK)
-        return fail(c0, PFMPE_E_HIP, "initialise_multi: stream " + std::to_string(s) + ": " + m.c->err);
+      if (const int rc = ensure_xfer(m.c)) return single ? rc : fail(c0, PFMPE_E_HIP, m.at + m.c->err);
     }
   }
   if (any_found) RET(multi_seed(c0, st));
   members.commit();  // nothing of the batch is pending: no member needs a fence
   for (int s = 0; s < S; ++s) out[s] = st[s].o;
   return PFMPE_OK;
+}
+
+// The checks of one stream's arguments, for the single call and the batch alike, into m; an error is reported on
+// `rep` with the text `at` + ...  A stream with B < M gets flag 10 and never reaches the device (PE:1507-1512: the PF
+// initialisation needs every marker detected).
+int validate_stream(pfmpe_ctx* rep, const std::string& at, pfmpe_ctx* c, const double* blobs, int B,
+                    const pfmpe_init_params* prm, MultiStream& m) {
+  if (B < 0 || (B > 0 && !blobs)) return fail(rep, PFMPE_E_ARG, at + "bad arguments");
+  if (!c->has_model) return fail(rep, PFMPE_E_STATE, at + "set_model first");
+  if (c->M < 3) return fail(rep, PFMPE_E_ARG, at + "needs M >= 3 markers");
+  if (B > c->max_blobs) return fail(rep, PFMPE_E_CAP, at + "B exceeds max_blobs");
+  m.c = c;
+  m.at = at;
+  m.blobs = blobs;
+  m.B = B;
+  m.p = effective_params(prm);
+  m.N = m.p.n_particles > 0 ? m.p.n_particles : (c->has_prior ? c->N : c->max_particles);
+  if (m.N > c->max_particles) return fail(rep, PFMPE_E_CAP, at + "n_particles exceeds max_particles");
+  m.o.first_match = -1;
+  if (B < c->M) m.o.flag_fail = 10;
+  return PFMPE_OK;
+}
+
+// fn with the timing brackets of c (the leader) on; a failure drops the brackets this call left unharvested, the
+// pending ones of earlier frames stay
+template <typename F>
+int timed(pfmpe_ctx* c, F&& fn) {
+  const size_t ev_mark = c->ev_used;
+  c->timing_now = c->timing > 0;
+  const int rc = fn();
+  c->timing_now = false;
+  if (rc != PFMPE_OK && c->ev_used > ev_mark) c->ev_used = ev_mark;
+  return rc;
 }
 
 }  // namespace
@@ -1355,6 +1108,7 @@ void pfmpe_default_init_params(pfmpe_init_params* p) {
   p->max_candidates = 1 << 20;
 }
 
+// stage 1 of a batch of one; unlike pfmpe_initialise it computes the histogram for 3 <= B < M too
 int pfmpe_p3p_histogram(pfmpe_ctx* c, const double* blobs, int B, uint32_t* hist) {
   if (!c) return PFMPE_E_ARG;
   if (!blobs || !hist) return fail(c, PFMPE_E_ARG, "p3p_histogram: null blobs/hist");
@@ -1363,136 +1117,27 @@ int pfmpe_p3p_histogram(pfmpe_ctx* c, const double* blobs, int B, uint32_t* hist
   if (B < 3) return fail(c, PFMPE_E_ARG, "p3p_histogram: needs B >= 3 blobs");
   if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, "p3p_histogram: B exceeds max_blobs");
   RET(set_device(c));
-  c->timing_now = c->timing > 0;
-  const size_t ev_mark = c->ev_used;  // pending brackets of earlier frames
-  const int rc = run_histogram(c, blobs, B, hist);
-  c->timing_now = false;
-  if (rc != PFMPE_OK) c->ev_used = ev_mark;  // only this call's brackets are dropped (success harvested them all)
-  return rc;
+  std::vector<MultiStream> st(1);
+  st[0].c = c;
+  st[0].blobs = blobs;
+  st[0].B = B;
+  RET(timed(c, [&] { return multi_histograms(c, st, true); }));
+  std::memcpy(hist, st[0].hist.data(), st[0].hist.size() * sizeof(uint32_t));
+  return PFMPE_OK;
 }
 
+// the batch of one
 int pfmpe_initialise(pfmpe_ctx* c, const double* blobs, int B, const pfmpe_init_params* prm, pfmpe_init_out* out,
                      uint32_t* hist_out) {
   if (!c) return PFMPE_E_ARG;
-  if (!out || (B > 0 && !blobs) || B < 0) return fail(c, PFMPE_E_ARG, "initialise: bad arguments");
-  if (!c->has_model) return fail(c, PFMPE_E_STATE, "initialise: set_model first");
-  if (c->M < 3) return fail(c, PFMPE_E_ARG, "initialise: needs M >= 3 markers");
-  if (B > c->max_blobs) return fail(c, PFMPE_E_CAP, "initialise: B exceeds max_blobs");
-  const pfmpe_init_params p = effective_params(prm);
-  const int N = p.n_particles > 0 ? p.n_particles : (c->has_prior ? c->N : c->max_particles);
-  if (N > c->max_particles) return fail(c, PFMPE_E_CAP, "initialise: n_particles exceeds max_particles");
-  std::memset(out, 0, sizeof(*out));
-  out->first_match = -1;
-  const int M = c->M;
-  if (B < M) {  // PE:1507-1512: the PF initialisation needs every marker detected
-    out->flag_fail = 10;
+  if (!out) return fail(c, PFMPE_E_ARG, "initialise: bad arguments");
+  std::vector<MultiStream> st(1);
+  RET(validate_stream(c, "initialise: ", c, blobs, B, prm, st[0]));
+  if (B < c->M) {  // nothing touches the device
+    *out = st[0].o;
     return PFMPE_OK;
   }
-  RET(set_device(c));
-  std::vector<uint32_t> hist((size_t)B * M);
-  c->timing_now = c->timing > 0;
-  int rc = run_histogram(c, blobs, B, hist.data());
-  if (rc != PFMPE_OK) {
-    c->timing_now = false;
-    return rc;
-  }
-  if (hist_out) std::memcpy(hist_out, hist.data(), hist.size() * sizeof(uint32_t));
-  uint64_t tot = 0;
-  for (uint32_t h : hist) tot += h;
-  out->hist_total = tot;
-  if (tot == 0) {
-    c->timing_now = false;
-    out->flag_fail = 12;
-    return PFMPE_OK;
-  }
-  std::vector<std::vector<uint32_t>> cands;
-  rc = candidates(c, "initialise: ", B, M, hist.data(), p.max_candidates, cands);
-  if (rc != PFMPE_OK) {
-    c->timing_now = false;
-    return rc;
-  }
-  out->n_candidates = (int)cands.size();
-  int flag = cands.empty() ? 11 : -1;
-
-  // ---- stage 3 on the device: every candidate with M rows x every lexicographic 3-subset
-  const int ncm = M * (M - 1) * (M - 2) / 6;
-  std::vector<int> full;  // indices of candidates with M rows (the others fail with flag 6, no P3P)
-  for (size_t i = 0; i < cands.size(); ++i)
-    if ((int)cands[i].size() == 2 * M) full.push_back((int)i);
-  std::vector<uint8_t> status((size_t)full.size() * ncm);
-  std::vector<double> invs((size_t)full.size() * ncm * 12);
-  if (!full.empty()) {
-    InitArgs ia = make_args(c, B);
-    ia.items = (int64_t)full.size() * ncm;
-    std::vector<int> ctab((size_t)full.size() * 2 * M);
-    for (size_t f = 0; f < full.size(); ++f)
-      for (int k = 0; k < 2 * M; ++k) ctab[f * 2 * M + k] = (int)cands[full[f]][k];
-    const std::vector<int> trip = lex_triples(M);
-    Arena ar;
-    const size_t o_blobs = ar.take<double>(2 * (size_t)B), o_iv = ar.take<double>(3 * (size_t)B);
-    const size_t o_c = ar.take<int>(ctab.size()), o_t = ar.take<int>(trip.size());
-    const size_t o_s = ar.take<uint8_t>(status.size()), o_i = ar.take<double>(invs.size());
-    rc = ensure_init(c, ar.off);
-    if (rc != PFMPE_OK) {
-      c->timing_now = false;
-      return rc;
-    }
-    unsigned char* d = c->d_init.get();
-    double* d_blobs = (double*)(d + o_blobs);
-    double* d_iv = (double*)(d + o_iv);
-    HIPCHK(c, hipMemcpyAsync(d_blobs, blobs, 2 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_c, ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + o_t, trip.data(), trip.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_init_prep, dim3((B + 255) / 256), dim3(256), 0, c->stream, ia, d_blobs, d_iv);
-    HIPCHK(c, hipGetLastError());
-    const unsigned grid = (unsigned)((ia.items + kInitBlock - 1) / kInitBlock);
-    const double ct = p.certainty_threshold;
-    RET(launch(c, PFMPE_K_P3P_CHECK, [&] {
-      const int nu = M - 3;
-      if (nu <= 2)
-        hipLaunchKernelGGL((k_p3p_check<2>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct, d_blobs, d_iv,
-                           (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
-      else if (nu <= 9)
-        hipLaunchKernelGGL((k_p3p_check<9>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct, d_blobs, d_iv,
-                           (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
-      else
-        hipLaunchKernelGGL((k_p3p_check<kMaxMarkers - 3>), dim3(grid), dim3(kInitBlock), 0, c->stream, ia, ct,
-                           d_blobs, d_iv, (const int*)(d + o_c), (const int*)(d + o_t), d + o_s, (double*)(d + o_i));
-    }));
-    HIPCHK(c, hipMemcpyAsync(status.data(), d + o_s, status.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(invs.data(), d + o_i, invs.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  if (c->timing_now) RET(harvest_timing(c));
-  c->timing_now = false;
-
-  std::vector<double> est;  // stored P3P poses in store order (estimate k at slot N - k)
-  book_keeping(c, cands, status.data(), invs.data(), N, p, flag, out, est);
-  if (!out->found) return PFMPE_OK;
-
-  // ---- seed the particle set: PoseParticle -> newPoseEstimation_Vec (PE:182-191)
-  const int K = out->n_estimates;
-  RET(ensure_xfer(c));
-  {
-    Arena ar;
-    const size_t o_e = ar.take<double>(est.size());
-    RET(ensure_init(c, ar.off));
-    HIPCHK(c, hipMemcpyAsync(c->d_init.get() + o_e, est.data(), est.size() * sizeof(double), hipMemcpyHostToDevice,
-                             c->stream));
-    if (K < N) {  // slot 0 keeps the resident set's slot 0 (identity when there is none)
-      if (c->has_prior) {
-        RET(export_prior(c, 1));
-      } else {
-        static const double I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-        HIPCHK(c, hipMemcpyAsync(c->d_xfer.get(), I12, sizeof(I12), hipMemcpyHostToDevice, c->stream));
-      }
-    }
-    hipLaunchKernelGGL(k_init_seed, dim3((N + 255) / 256), dim3(256), 0, c->stream, (const double*)(c->d_init.get() + o_e),
-                       K, N, c->d_xfer.get());
-    HIPCHK(c, hipGetLastError());
-    RET(import_prior(c, N, est.data()));  // anchor (fp16 state): the first stored estimate
-  }
-  return PFMPE_OK;
+  return timed(c, [&] { return multi_run(&c, st, out, &hist_out, true); });
 }
 
 int pfmpe_initialise_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_init_in* in, const pfmpe_init_params* prm,
@@ -1510,33 +1155,14 @@ int pfmpe_initialise_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_init_in* i
     for (int e = 0; e < s; ++e)
       if (ctxs[e] == c) return fail(c0, PFMPE_E_ARG, at + "context appears twice");
     if (c->device != c0->device) return fail(c0, PFMPE_E_ARG, at + "device must match ctxs[0]");
-    if (in[s].B < 0 || (in[s].B > 0 && !in[s].blobs)) return fail(c0, PFMPE_E_ARG, at + "bad arguments");
-    if (!c->has_model) return fail(c0, PFMPE_E_STATE, at + "set_model first");
-    if (c->M < 3) return fail(c0, PFMPE_E_ARG, at + "needs M >= 3 markers");
-    if (in[s].B > c->max_blobs) return fail(c0, PFMPE_E_CAP, at + "B exceeds max_blobs");
-    MultiStream& m = st[s];
-    m.c = c;
-    m.blobs = in[s].blobs;
-    m.B = in[s].B;
-    m.p = effective_params(prm ? prm + s : nullptr);
-    m.N = m.p.n_particles > 0 ? m.p.n_particles : (c->has_prior ? c->N : c->max_particles);
-    if (m.N > c->max_particles) return fail(c0, PFMPE_E_CAP, at + "n_particles exceeds max_particles");
-    m.o.first_match = -1;
-    if (m.B < c->M)  // PE:1507-1512: the PF initialisation needs every marker detected
-      m.o.flag_fail = 10;
-    else
-      any = true;
+    RET(validate_stream(c0, at, c, in[s].blobs, in[s].B, prm ? prm + s : nullptr, st[s]));
+    any = any || in[s].B >= c->M;
   }
-  if (!any) {  // as S single calls: nothing touches the device
+  if (!any) {  // nothing touches the device
     for (int s = 0; s < S; ++s) out[s] = st[s].o;
     return PFMPE_OK;
   }
-  const size_t ev_mark = c0->ev_used;  // pending brackets of earlier frames
-  c0->timing_now = c0->timing > 0;
-  const int rc = multi_run(ctxs, st, out, hist_out);
-  c0->timing_now = false;
-  if (rc != PFMPE_OK && c0->ev_used > ev_mark) c0->ev_used = ev_mark;  // this call's unharvested brackets are dropped
-  return rc;
+  return timed(c0, [&] { return multi_run(ctxs, st, out, hist_out, false); });
 }
 
 }  // extern "C"

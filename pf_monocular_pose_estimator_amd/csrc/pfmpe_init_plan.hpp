@@ -10,29 +10,30 @@
 namespace pfmpe_plan {
 
 constexpr int kInitBlockThreads = 256;       // threads of a histogram block (one item each per round)
-constexpr int kInitBlocksPerCu = 8;          // a launch's block cap per CU, the single call's
+constexpr int kInitBlocksPerCu = 8;          // a launch's block cap per CU
 constexpr int64_t kInitLdsHistBytes = 32 * 1024;  // largest histogram kept in LDS
 
 // the unused-marker bucket of M markers: the kernels' MAXU is 2, 9, PFMPE_MAX_MARKERS - 3
 inline int init_bucket(int M) { return M - 3 <= 2 ? 0 : M - 3 <= 9 ? 1 : 2; }
 
-// (3-blob combination, ordered 3-marker triple) items of a stream; 0 when the call stops at "too few blobs"
-inline int64_t init_items(int M, int B) {
-  if (B < M || B < 3) return 0;
+// (3-blob combination, ordered 3-marker triple) items of a stream; 0 when the call stops at "too few blobs".
+// hist_only: the stream of pfmpe_p3p_histogram, which computes the histogram for 3 <= B < M too.
+inline int64_t init_items(int M, int B, bool hist_only = false) {
+  if ((B < M && !hist_only) || B < 3) return 0;
   return (int64_t)B * (B - 1) * (B - 2) / 6 * ((int64_t)M * (M - 1) * (M - 2));
 }
 
 // The plan of S streams (M[s] markers, B[s] blobs, validated by the caller) on a device of num_cu CUs.  Per bucket:
 // a stream wants ceil(items / 256) blocks; when the wants exceed the cap of 8 * max(num_cu, 1) blocks, a stream gets
 // floor(want * cap / wants) blocks, and one block where that is zero (so the launch exceeds the cap by at most one
-// block per stream with work); first_block is the running sum in ascending stream index.
+// block per stream with work); first_block is the running sum in ascending stream index.  hist_only: init_items'.
 inline void init_plan(const int32_t* M, const int32_t* B, int S, int num_cu, pfmpe_init_plan* plan,
-                      int32_t* blocks_per_bucket) {
+                      int32_t* blocks_per_bucket, bool hist_only = false) {
   const int64_t cap = (int64_t)kInitBlocksPerCu * std::max(num_cu, 1);
   int64_t wants[3] = {0, 0, 0};
   for (int s = 0; s < S; ++s) {
     pfmpe_init_plan& p = plan[s];
-    p.items = init_items(M[s], B[s]);
+    p.items = init_items(M[s], B[s], hist_only);
     p.bucket = init_bucket(M[s]);
     p.lds_hist = (int64_t)B[s] * M[s] * 4 <= kInitLdsHistBytes ? 1 : 0;
     wants[p.bucket] += (p.items + kInitBlockThreads - 1) / kInitBlockThreads;

@@ -8,7 +8,12 @@ the reference's algorithm restated, 1 thread).
 --streams S prints another JSON line instead: pfmpe_initialise_multi over S contexts against S sequential
 pfmpe_initialise calls on the same contexts and inputs, on the track-loss frame (M = 5, B = 8,
 N = 1000) or at --B blobs: wall time of both (mean, min, max over the repetitions, two rounds of each) and the
-k_p3p_hist / k_p3p_check brackets of both.
+k_p3p_hist / k_p3p_check brackets of both.  pfmpe_initialise is the batch of one, so the loop column runs the same
+kernels as the batch column; it stays because it measures what S blocking calls cost (3 x S synchronises, S uploads
+per stage) against one batch.
+
+Without --streams the line also carries the medians of the two wall times and the k_p3p_hist / k_p3p_check brackets
+of the pfmpe_initialise calls alone.
 """
 import argparse
 import json
@@ -128,23 +133,31 @@ def main():
         eng.p3p_histogram(blobs)
     eng.set_option(pf.OPT_TIMING, 1)
     eng.reset_kernel_stats()
-    t0 = time.perf_counter()
+    walls = []
     for _ in range(a.reps):
+        t0 = time.perf_counter()
         h = eng.p3p_histogram(blobs)
-    wall = (time.perf_counter() - t0) / a.reps
+        walls.append(time.perf_counter() - t0)
+    wall = float(np.mean(walls))
     n, ms = eng.kernel_stats()["k_p3p_hist"]
     dev = ms / max(n, 1) / 1e3
     items = comb(B, 3) * M * (M - 1) * (M - 2)
     res = {"metric": "P3P initialisation histogram: (3-blob combination x ordered 3-marker) P3P solves/s",
            "value": items / dev, "unit": "P3P solves/s", "config": {"M": M, "B": B, "items": items},
-           "k_p3p_hist_us": dev * 1e6, "wall_us": wall * 1e6, "hist_total": int(h.sum()), "dtype": "f64"}
+           "k_p3p_hist_us": dev * 1e6, "wall_us": wall * 1e6, "wall_median_us": float(np.median(walls)) * 1e6, "hist_total": int(h.sum()), "dtype": "f64"}
     # full initialise on a realistic frame (all markers + 3 outliers)
     fb, _ = syn.init_blobs(M, 3, seed=0)
     eng.reset_kernel_stats()
-    t0 = time.perf_counter()
+    walls = []
     for _ in range(a.reps):
+        t0 = time.perf_counter()
         out, _ = eng.initialise(fb, n_particles=1000)
-    res["initialise_wall_us"] = (time.perf_counter() - t0) / a.reps * 1e6
+        walls.append(time.perf_counter() - t0)
+    res["initialise_wall_us"] = float(np.mean(walls)) * 1e6
+    res["initialise_wall_median_us"] = float(np.median(walls)) * 1e6
+    for k, (n, ms) in eng.kernel_stats().items():  # the brackets of the initialise calls alone (timing is on)
+        if k in ("k_p3p_hist", "k_p3p_check"):
+            res[f"initialise_{k}_us"] = ms / max(n, 1) * 1e3
     res["initialise_found"] = out["found"]
     if a.cpu:
         from oracle import pforacle as orc

@@ -56,6 +56,27 @@ def test_histogram_matches_oracle(case):
     eng.close()
 
 
+def test_histogram_global_atomics_path():
+    """B x M x 4 bytes > 32 KB: the histogram does not fit in LDS and the block counts straight into global memory.
+    M = 12 and the smallest such B, 683.  The 12 markers and 3 outliers lie in the image, the other 668 blobs on a
+    line 1001 px apart, so only the C(15,3) combinations within the image pass the spread filter: the oracle takes
+    about 4 s for the 5.3e7 combinations, the device a fraction of that."""
+    M, B = 12, 683
+    near, _ = syn.init_blobs(M, 3, seed=3)
+    blobs = np.vstack([near, [[2000.0 + 1001.0 * k, 240.0] for k in range(B - len(near))]])
+    assert B * M * 4 > 32 * 1024 >= (B - 1) * M * 4
+    eng = engine(M)
+    h_gpu = eng.p3p_histogram(blobs).astype(np.int64)
+    h_ref, lo, hi, unbounded = orc.init_histogram_bounds(syn.markers_for(M), K, blobs, tol=5.0)
+    h_ref, lo, hi = h_ref.astype(np.int64), lo.astype(np.int64), hi.astype(np.int64)
+    assert h_gpu.sum() > 0 and not h_gpu[len(near):].any()
+    assert (h_gpu >= lo).all(), np.argwhere(h_gpu < lo)[:10]
+    excess = np.maximum(h_gpu - hi, 0).sum()
+    assert excess <= unbounded * (3 + M), (excess, unbounded)
+    assert np.abs(h_gpu - h_ref).sum() <= max(4, 0.005 * h_ref.sum()), (np.abs(h_gpu - h_ref).sum(), h_ref.sum())
+    eng.close()
+
+
 @pytest.mark.parametrize("state", ["f64", "f32", "f16"])
 @pytest.mark.parametrize("case", CASES[:4], ids=lambda c: f"M{c[0]}_s{c[3]}")
 def test_initialise_matches_oracle(case, state):

@@ -3,7 +3,10 @@
 The bar is the single call: out, the histogram and the seeded particle set of every stream equal what
 pfmpe_initialise gives a twin engine with the same inputs, bit for bit (array_equal): the histogram counts are
 order-free integer sums of per-item decisions taken by the same per-item code, and the host stages are the same
-functions on the same inputs.  Parity of the single call with the oracle is tests/test_gpu_init.py's subject.
+functions on the same inputs.  pfmpe_initialise is the batch of one, so the twins run the same kernels: these
+comparisons show that the streams of a batch do not disturb each other (prefix tables, block plans, mixed buckets and
+state types), not that the kernels are right.  That rests on the oracle: tests/test_gpu_init.py for the single call,
+test_batch_matches_oracle here for a batch.
 """
 import ctypes as C
 
@@ -12,6 +15,7 @@ import pytest
 
 import pf_monocular_pose_estimator_amd as pf
 from pf_monocular_pose_estimator_amd import synthetic as syn
+from oracle import pforacle as orc
 
 pytestmark = pytest.mark.gpu
 K = syn.K_README
@@ -100,6 +104,67 @@ def test_one_stream_equals_the_single_call():
     assert np.array_equal(h, h_ref)
     assert np.array_equal(a.get_particles(1), b.get_particles(1))
     close_all([a, b])
+
+
+def histogram_bars(h_gpu, M, blobs):
+    """tests/test_gpu_init.py::test_histogram_matches_oracle's bars on one histogram; returns the oracle's."""
+    h_gpu = h_gpu.astype(np.int64)
+    h_ref, lo, hi, unbounded = orc.init_histogram_bounds(markers_of(M), K, blobs, tol=5.0)
+    h_ref, lo, hi = h_ref.astype(np.int64), lo.astype(np.int64), hi.astype(np.int64)
+    assert (h_gpu >= lo).all(), np.argwhere(h_gpu < lo)[:10]
+    excess = np.maximum(h_gpu - hi, 0).sum()
+    assert excess <= unbounded * (3 + M), (excess, unbounded)
+    assert np.abs(h_gpu - h_ref).sum() <= max(4, 0.005 * h_ref.sum()), (np.abs(h_gpu - h_ref).sum(), h_ref.sum())
+    return h_ref
+
+
+def test_batch_matches_oracle():
+    """The batch against the oracle, which runs none of its code: tests/test_gpu_init.py's bars, per stream
+    (test_initialise_matches_oracle's on out and the seeded set, test_histogram_matches_oracle's on the histogram)."""
+    cases = [CASES[0], CASES[2], CASES[3]]
+    states = [("f64", F64), ("f32", F32), ("f16", F16)]
+    inputs = [syn.init_blobs(c[0], c[1], c[3], noise_px=c[4], near=c[2]) for c in cases]
+    blobs = [b for b, _ in inputs]
+    engs = [engine(c[0], st) for c, (_, st) in zip(cases, states)]
+    got = pf.Engine.initialise_multi(engs, blobs, n_particles=N)
+    for s, (case, (name, _)) in enumerate(zip(cases, states)):
+        M, near = case[0], case[2]
+        out, h = got[s]
+        assert h.sum() > 0
+        histogram_bars(h, M, blobs[s])
+        ref, _, parts = orc.initialise(markers_of(M), K, blobs[s], N, hist=h)
+        for k in OUT_KEYS:
+            assert out[k] == ref[k], (s, k, out[k], ref[k])
+        assert np.array_equal(out["pairs"], ref["pairs"])
+        assert out["found"] == 1
+        np.testing.assert_allclose(out["predicted_pose"], ref["predicted_pose"], rtol=0, atol=1e-9)
+        if near == 0:  # near-blob outliers can make the reference itself pick a wrong first match
+            assert np.abs(syn.to44(out["predicted_pose"]) - inputs[s][1]).max() < 3e-2
+        tol = {"f64": 1e-12, "f32": 4e-7, "f16": 1e-3}[name]
+        np.testing.assert_allclose(engs[s].get_particles(1), parts, rtol=0, atol=tol)
+    close_all(engs)
+
+
+def test_histogram_only_below_M():
+    """pfmpe_p3p_histogram computes the histogram for 3 <= B < M, where pfmpe_initialise stops at flag 10 and the
+    public plan has no items: B = 3 (one combination, the smallest grid) and B = 4 (240 items, a partly filled
+    block) at M = 5.  No combination can pass the >= 5-blob filter, so no floating-point decision is taken and the
+    histogram is the oracle's entry for entry (all zero, by the oracle's word)."""
+    M = 5
+    b5 = case_blobs((M, 0, 0, 0, 0.0))
+    eng = engine(M)
+    for B in (3, 4):
+        h = eng.p3p_histogram(b5[:B])
+        assert h.shape == (B, M)
+        h_ref = histogram_bars(h, M, b5[:B])
+        assert np.array_equal(h.astype(np.int64), h_ref)
+        assert pf.host_init_plan([M], [B], 256)[0][0]["items"] == 0  # the public plan follows pfmpe_initialise
+    eng.set_prior(some_prior())
+    before = eng.get_particles(1)
+    out, _ = eng.initialise(b5[:4], n_particles=N)
+    assert out["found"] == 0 and out["flag_fail"] == 10
+    assert np.array_equal(eng.get_particles(1), before)
+    eng.close()
 
 
 def run_batch(engs, blobs, **kw):
