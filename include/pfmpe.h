@@ -623,6 +623,63 @@ int pfmpe_refine_poses(pfmpe_ctx* ctx, const pfmpe_assoc_in* blobs, const pfmpe_
  * N, rows / cov (may be NULL) cover particles first .. first + count - 1 */
 int pfmpe_refine_cloud(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* blobs, const pfmpe_refine_params* params,
                        int64_t first, int32_t count, pfmpe_refine_out* out, pfmpe_refine_row* rows, double* cov);
+#define PFMPE_REFINE_MAX_STREAMS 64
+#define PFMPE_REFINE_MULTI_MAX_HYPOTHESES 65536   /* all streams together: one chunk */
+#define PFMPE_REFINE_DESC_BYTES 48                /* a stream's descriptor in the upload buffer (the plan below) */
+
+/* pfmpe_refine_poses for S streams as one batch (the numUAV loop's optimisePose, PE:89: the winner of every accepted
+ * object of a frame): one upload of one packed buffer, one Gauss-Newton launch over all hypotheses, one launch that
+ * folds every stream's summary, one read-back and one synchronise, where S single calls make S of each sequence.
+ * out[s], rows[s] and cov[s] are byte for byte what
+ *   pfmpe_refine_poses(ctxs[s], &in[s].blobs, &params[s], in[s].poses, in[s].corr, in[s].K, &out[s], rows[s], cov[s])
+ * writes (out[s].n = K_s, best an index within the stream, the zeroed best_row / best_cov when no hypothesis is
+ * eligible, the empty summary for K_s = 0): a lane runs the same function on the same numbers, every summed quantity
+ * is an integer and the best key is a total order.  Per stream: M, the markers and K (from its context), its blob
+ * list and B, K_s and every field of params[s] (params = NULL: the defaults for all, else S records).  rows = NULL or
+ * rows[s] = NULL, cov = NULL or cov[s] = NULL: not wanted, else K_s rows / K_s x 36.
+ * Contexts of any state types may be mixed; they must be on one device; a context may appear more than once (two blob
+ * lists of one camera).  The call reads only a member's model and the host copy of its blob bank: no member's device
+ * state is read or written, so nothing is ordered with the members' own streams.  ctxs[0] leads: the batch runs on
+ * its stream, in a scratch buffer and a pinned staging block it owns (grown on demand, never shrunk), and it receives
+ * the error text.  Blocking; not timed by PFMPE_OPT_TIMING.
+ * Everything is checked before anything is staged or launched; on an error out, rows and cov are untouched and no
+ * context changes: PFMPE_E_ARG (S < 1, NULL ctxs / in / out / ctxs[s], a device mismatch, K_s < 0, NULL poses / corr
+ * with K_s > 0, B < 0, NULL blobs with B > 0 and no bank frame, a bank frame out of range, an LED or blob index out of
+ * range, a non-finite start pose, bad params[s]), PFMPE_E_CAP (S > PFMPE_REFINE_MAX_STREAMS, B_s > max_blobs of
+ * ctxs[s], K_s > max_particles of ctxs[s], the sum of K_s above PFMPE_REFINE_MULTI_MAX_HYPOTHESES), PFMPE_E_STATE (a
+ * stream without a model); the text, "refine_multi: stream <s>: ...", is the last-error text of ctxs[0].  With
+ * ctxs = NULL or ctxs[0] = NULL: PFMPE_E_ARG, no text. */
+typedef struct {
+  pfmpe_assoc_in blobs;   /* this stream's blob list: host pointer + B, or a frame of ITS context's staged bank */
+  const double* poses;    /* K x 12 start poses; may be NULL when K == 0 */
+  const uint32_t* corr;   /* K x 2*PFMPE_MAX_MARKERS pair rows, as pfmpe_frame_out.corr; may be NULL when K == 0 */
+  int32_t K;              /* hypotheses of this stream; 0 is valid (the object was not accepted this frame) */
+  int32_t pad;
+} pfmpe_refine_in;        /* 40 bytes */
+int pfmpe_refine_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_refine_in* in, const pfmpe_refine_params* params,
+                       pfmpe_refine_out* out, pfmpe_refine_row* const* rows, double* const* cov);
+
+/* host-only (no GPU, no context): the packed upload buffer of the batch, which the call above stages exactly.  With
+ * H = sum of K the buffer holds, each region 16-byte aligned, disjoint from the others and inside [0, upload_bytes):
+ * S descriptors of PFMPE_REFINE_DESC_BYTES, the stream index of every hypothesis (H int32), the start poses
+ * (H x 12 doubles), the pair rows (H x 2*PFMPE_MAX_MARKERS words), and per stream its model (PFMPE_MAX_MARKERS x 3
+ * doubles of markers, then the 9 of K) and its blobs (2 * B doubles).  The layout depends on K, B and S alone.
+ * download_bytes: the summaries (S), rows (H) and covariances (H x 36) the device writes behind the upload.
+ * PFMPE_E_ARG for a NULL pointer, S < 1, K < 0 or B < 0; PFMPE_E_CAP for S > PFMPE_REFINE_MAX_STREAMS,
+ * B > PFMPE_MAX_BLOBS or H > PFMPE_REFINE_MULTI_MAX_HYPOTHESES; the outputs are untouched then. */
+typedef struct {
+  int64_t first;         /* index of the stream's first hypothesis in the batch: prefix sum of K */
+  int64_t model_offset;  /* byte offset in the upload buffer of its markers (PFMPE_MAX_MARKERS x 3 doubles) + K (9) */
+  int64_t blobs_offset;  /* byte offset of its 2 * B doubles (any valid offset when B == 0) */
+} pfmpe_refine_plan;     /* 24 bytes */
+typedef struct {
+  int64_t hypotheses;                                   /* sum of K */
+  int64_t desc_offset, stream_of_offset, poses_offset, corr_offset;  /* S descriptors; H int32; H x 12 doubles; H x 32 words */
+  int64_t upload_bytes, download_bytes;
+} pfmpe_refine_plan_total;                              /* 56 bytes */
+int pfmpe_host_refine_plan(const int32_t* K, const int32_t* B, int S, pfmpe_refine_plan* plan,
+                           pfmpe_refine_plan_total* total);
+
 /* host-only: the same __host__ __device__ code for one hypothesis (no GPU, no context).  corr: n_rows rows (any
  * count).  PFMPE_E_ARG for a NULL pointer, M < 1, B < 0, n_rows < 0, a bad index, a non-finite start pose or bad
  * parameters, as above.  params may be NULL, cov36 may be NULL. */

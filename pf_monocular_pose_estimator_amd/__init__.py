@@ -21,6 +21,8 @@ from ._capi import (  # noqa: F401
     ROI_MAX_STREAMS, RoiIn, RoiOut, host_predict_roi,
     DETECT_MAX_IMAGES, DIAG_DET_COPY, DetectImage, DetectCrop, host_detect_plan, host_detect_pack,
     INIT_MAX_STREAMS, INFO_NUM_CU, InitIn, InitPlan, InitParams, InitOut, host_init_plan,
+    REFINE_MAX_STREAMS, REFINE_MULTI_MAX_HYPOTHESES, REFINE_DESC_BYTES, RefineIn, RefinePlan, RefinePlanTotal,
+    host_refine_plan,
 )
 
 __all__ = [

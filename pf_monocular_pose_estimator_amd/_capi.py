@@ -57,11 +57,15 @@ EXPORTED_SYMBOLS = (
     "pfmpe_predict_roi_multi", "pfmpe_host_predict_roi",
     "pfmpe_find_leds_streams", "pfmpe_host_detect_plan", "pfmpe_host_detect_pack",
     "pfmpe_initialise_multi", "pfmpe_host_init_plan",
+    "pfmpe_refine_multi", "pfmpe_host_refine_plan",
 )
 DETECT_MAX_ROIS = 64
 DETECT_MAX_IMAGES = 64
 ROI_MAX_STREAMS = 64
 INIT_MAX_STREAMS = 64
+REFINE_MAX_STREAMS = 64
+REFINE_MULTI_MAX_HYPOTHESES = 65536
+REFINE_DESC_BYTES = 48
 
 
 class Params(C.Structure):
@@ -237,6 +241,27 @@ class RefineOut(C.Structure):
         return d
 
 
+class RefineIn(C.Structure):
+    _fields_ = [("blobs", AssocIn), ("poses", C.POINTER(C.c_double)), ("corr", C.POINTER(C.c_uint32)),
+                ("K", C.c_int32), ("pad", C.c_int32)]
+
+
+class RefinePlan(C.Structure):
+    _fields_ = [("first", C.c_int64), ("model_offset", C.c_int64), ("blobs_offset", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RefinePlanTotal(C.Structure):
+    _fields_ = [("hypotheses", C.c_int64), ("desc_offset", C.c_int64), ("stream_of_offset", C.c_int64),
+                ("poses_offset", C.c_int64), ("corr_offset", C.c_int64), ("upload_bytes", C.c_int64),
+                ("download_bytes", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -289,6 +314,10 @@ def load() -> C.CDLL:
                                    C.POINTER(RefineOut), P, dp]),
         "pfmpe_host_optimise_pose": (I, [dp, I, dp, dp, I, C.POINTER(C.c_uint32), I, C.POINTER(RefineParams), dp,
                                          C.POINTER(RefineRow), dp]),
+        "pfmpe_refine_multi": (I, [C.POINTER(P), I, C.POINTER(RefineIn), C.POINTER(RefineParams), C.POINTER(RefineOut),
+                                   C.POINTER(P), C.POINTER(dp)]),
+        "pfmpe_host_refine_plan": (I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, C.POINTER(RefinePlan),
+                                       C.POINTER(RefinePlanTotal)]),
         "pfmpe_predict_roi": (I, [P, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
         "pfmpe_predict_roi_multi": (I, [C.POINTER(P), I, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
         "pfmpe_host_predict_roi": (I, [dp, I, dp, dp, I64, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
@@ -825,6 +854,66 @@ class Engine:
             C.byref(out), rows.ctypes.data_as(C.c_void_p) if n else None, _dptr(cov) if (want_cov and n) else None))
         return self._refine_result(out, rows, cov)
 
+    @staticmethod
+    def refine_multi(engines, poses_list, pairs_list, blobs_list=None, bank_frames=None, params=None,
+                     want_rows: bool = True, want_cov: bool = False) -> list:
+        """Gauss-Newton of the hypotheses of every engine as ONE batch on the device (pfmpe_refine_multi): poses_list[s]
+        (K_s x 12, K_s may be 0) and pairs_list[s] (K_s x MAX_MARKERS x 2) belong to engines[s], with the blob list
+        blobs_list[s] or the frame bank_frames[s] (>= 0) of that engine's staged bank.  An engine may appear more than
+        once.  params: None (the defaults), one RefineParams for all, or one per engine.  Returns one dict per stream
+        in the shape refine_poses returns ("rows" with want_rows, "cov" with want_cov)."""
+        S = len(engines)
+        if S == 0 or S != len(poses_list) or S != len(pairs_list):
+            raise ValueError("refine_multi: one pose set and one pair set per engine")
+        if blobs_list is None:
+            blobs_list = [None] * S
+        if bank_frames is None:
+            bank_frames = [-1] * S
+        if len(blobs_list) != S or len(bank_frames) != S:
+            raise ValueError("refine_multi: one blob list / bank frame per engine")
+        lib = engines[0].lib
+        ctxs = (C.c_void_p * S)(*[e.ctx.value for e in engines])
+        ins, outs = (RefineIn * S)(), (RefineOut * S)()
+        keep, rows, covs = [], [], []
+        for s in range(S):
+            ai, kb = Engine._assoc_in(blobs_list[s], int(bank_frames[s]))
+            pr = np.ascontiguousarray(pairs_list[s], dtype=np.uint32).reshape(-1, MAX_MARKERS, 2)
+            k = pr.shape[0]
+            po = np.asarray(poses_list[s], dtype=np.float64)
+            if po.shape[-2:] == (4, 4):
+                po = po[..., :3, :]
+            po = np.ascontiguousarray(po.reshape(-1, 12))
+            if po.shape[0] != k:
+                raise ValueError("refine_multi: one pair table per pose")
+            keep.append((kb, pr, po))
+            ins[s].blobs = ai
+            ins[s].poses = _dptr(po) if k else C.POINTER(C.c_double)()
+            ins[s].corr = pr.ctypes.data_as(C.POINTER(C.c_uint32)) if k else C.POINTER(C.c_uint32)()
+            ins[s].K = k
+            rows.append(np.zeros(k, dtype=REFINE_ROW_DTYPE) if want_rows else None)
+            covs.append(np.zeros((k, 6, 6), dtype=np.float64) if want_cov else None)
+        ps = None
+        if params is not None:
+            ps = (RefineParams * S)()
+            for s in range(S):
+                src = params[s] if isinstance(params, (list, tuple)) else params
+                ps[s].max_iter, ps[s].revert_on_divergence, ps[s].converged = (src.max_iter, src.revert_on_divergence,
+                                                                               src.converged)
+        rp = (C.c_void_p * S)(*[r.ctypes.data if (r is not None and len(r)) else None for r in rows]) if want_rows else None
+        cp = None
+        if want_cov:
+            cp = (C.POINTER(C.c_double) * S)(*[_dptr(c) if len(c) else C.POINTER(C.c_double)() for c in covs])
+        engines[0]._chk(lib.pfmpe_refine_multi(ctxs, S, ins, ps, outs, rp, cp))
+        res = []
+        for s in range(S):
+            d = outs[s].as_dict()
+            if want_rows:
+                d["rows"] = rows[s]
+            if want_cov:
+                d["cov"] = covs[s]
+            res.append(d)
+        return res
+
     def kernel_stats(self) -> dict:
         res = {}
         for k in range(K_COUNT):
@@ -1074,6 +1163,23 @@ def host_init_plan(M, B, num_cu: int) -> tuple:
     if rc != OK:
         raise PFError(rc, "pfmpe_host_init_plan")
     return [plan[s].as_dict() for s in range(S)], list(per_bucket)
+
+
+def host_refine_plan(K, B) -> tuple:
+    """pfmpe_host_refine_plan: the packed upload buffer of a refine_multi batch.  K, B: hypotheses and blobs per stream.
+    Returns (one dict per stream: first, model_offset, blobs_offset; the totals as a dict)."""
+    k = np.ascontiguousarray(K, dtype=np.int32).reshape(-1)
+    b = np.ascontiguousarray(B, dtype=np.int32).reshape(-1)
+    if k.shape != b.shape:
+        raise ValueError("host_refine_plan: one K and one B per stream")
+    S = int(k.shape[0])
+    plan = (RefinePlan * max(S, 1))()
+    total = RefinePlanTotal()
+    i32 = C.POINTER(C.c_int32)
+    rc = load().pfmpe_host_refine_plan(k.ctypes.data_as(i32), b.ctypes.data_as(i32), S, plan, C.byref(total))
+    if rc != OK:
+        raise PFError(rc, "pfmpe_host_refine_plan")
+    return [plan[s].as_dict() for s in range(S)], total.as_dict()
 
 
 def host_grow_roi(roi, margin: int, image_w: int, image_h: int) -> tuple:

@@ -172,6 +172,10 @@ struct pfmpe_ctx : CtxQueue {
   Buf<uint32_t> d_assoc; // association votes: M x B bins + the pair-count bins (pfmpe_assoc_stats)
   Buf<uint32_t> d_pairs; // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
   Buf<unsigned char> d_refine; // Gauss-Newton refinement scratch (RefineBuf layout, pfmpe_refine_*)
+  // pfmpe_refine_multi (owned by the batch's first context): the packed upload followed by the batch's summaries,
+  // rows and covariances, and the pinned block the upload is built in and the results land in; grown on demand
+  Buf<unsigned char> d_refm;
+  Buf<unsigned char, Mem::Pinned> h_refm;
   Buf<unsigned char> d_init;       // initialisation scratch (pfmpe_init.hip), grown on demand
   // the initialisation (owned by the batch's first context; pfmpe_initialise and pfmpe_p3p_histogram are batches of
   // one): the pinned block its read-backs land in (every stream's histogram; every stream's check results), grown on
@@ -615,6 +619,30 @@ static_assert(sizeof(pfmpe_refine_row) == 128 && sizeof(pfmpe_refine_out) <= Ref
 int refine_launch(pfmpe_ctx* c, const pfmpe_refine_params& prm, const double* poses, const uint32_t* corr, int64_t base,
                   int count, int cap, bool begin);
 
+// The batch (pfmpe_refine_multi): the leader's d_refm holds the packed upload of pfmpe_refine_plan.hpp (`up`), and
+// behind it what the device writes: S summaries, H rows, H covariances, read back as one block.  All pointers are
+// into d_refm.  (RefineDesc: pfmpe_refine_plan.hpp, included by the two units that use it.)
+}  // namespace pfmpe_impl
+namespace pfmpe_plan {
+struct RefineDesc;
+}
+namespace pfmpe_impl {
+using pfmpe_plan::RefineDesc;
+struct RefineMultiArgs {
+  const unsigned char* up;   // the upload: the descriptors' model_offset / blobs_offset count from here
+  const RefineDesc* desc;    // S
+  const int32_t* stream_of;  // H: the stream of hypothesis h
+  const double* poses;       // H x 12
+  const uint32_t* corr;      // H x 2 * kMaxMarkers
+  pfmpe_refine_out* out;     // S
+  pfmpe_refine_row* rows;    // H
+  double* cov;               // H x 36
+  int32_t H, pad;
+};
+// k_refine_multi over the H hypotheses (skipped when H = 0), then k_refine_fold_multi, one wave per stream, on the
+// leader's stream.
+int refine_multi_launch(pfmpe_ctx* c0, const RefineMultiArgs& ma, int S);
+
 // ---------------------------------------------------------------------- shared preambles of the entry points
 // the transfer buffer (N x 12 doubles), written and read inside one blocking call by every user
 inline int ensure_xfer(pfmpe_ctx* c) { return c->d_xfer.ensure(c, (size_t)c->max_particles * 12 * sizeof(double)); }
@@ -626,21 +654,26 @@ inline int ensure_pairs(pfmpe_ctx* c) {
 }
 
 // Which blobs a pfmpe_assoc_in means: the caller's, or a frame of the staged bank (the host copy kept for
-// rebuilds).  Checks the request (texts begin with `who`); *blobs / *B are the resolved list.
-inline int resolve_blobs(pfmpe_ctx* c, const std::string& who, const pfmpe_assoc_in* in, const double** blobs, int* B) {
-  if (in->B < 0) return fail(c, PFMPE_E_ARG, who + ": B < 0");
+// rebuilds).  Checks the request (texts begin with `who`, reported on `err`: c itself unless a batch's leader is
+// given); *blobs / *B are the resolved list.
+inline int resolve_blobs(const pfmpe_ctx* c, const std::string& who, const pfmpe_assoc_in* in, const double** blobs, int* B,
+                         pfmpe_ctx* err) {
+  if (in->B < 0) return fail(err, PFMPE_E_ARG, who + ": B < 0");
   *blobs = in->blobs;
   *B = in->B;
   if (in->bank_frame >= 0) {
     if (c->bank_offsets.empty() || in->bank_frame >= (int)c->bank_offsets.size() - 1)
-      return fail(c, PFMPE_E_ARG, who + ": bank_frame out of range");
+      return fail(err, PFMPE_E_ARG, who + ": bank_frame out of range");
     *B = c->bank_offsets[in->bank_frame + 1] - c->bank_offsets[in->bank_frame];
     *blobs = c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame];
   } else if (*B > 0 && !*blobs) {
-    return fail(c, PFMPE_E_ARG, who + ": null blobs");
+    return fail(err, PFMPE_E_ARG, who + ": null blobs");
   }
-  if (*B > c->max_blobs) return fail(c, PFMPE_E_CAP, who + ": B exceeds max_blobs");
+  if (*B > c->max_blobs) return fail(err, PFMPE_E_CAP, who + ": B exceeds max_blobs");
   return PFMPE_OK;
+}
+inline int resolve_blobs(pfmpe_ctx* c, const std::string& who, const pfmpe_assoc_in* in, const double** blobs, int* B) {
+  return resolve_blobs(c, who, in, blobs, B, c);
 }
 
 // The members of a batch (pfmpe_step_multi, pfmpe_predict_roi_multi): none null, none twice, and each agreeing

@@ -8,6 +8,7 @@
 #include "pf_likelihood.hpp"
 #include "pf_roi.hpp"
 #include "pfmpe_prior.hpp"
+#include "pfmpe_refine_plan.hpp"
 
 using namespace pfmpe_impl;
 
@@ -1114,6 +1115,110 @@ int pfmpe_refine_cloud(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, const 
     RET(refine_fetch(c, cap, (int)(lo - done), (int)(hi - done), rows, cov, lo - first));
   }
   return refine_finish(c, N, out);
+}
+
+// pfmpe_refine_poses of S streams as one batch on ctxs[0]'s stream: the per-stream checks of the single call, the
+// upload of pfmpe_refine_plan.hpp built in the leader's pinned block, one copy up, two launches, one copy down, one
+// synchronise, and the results scattered to the caller's arrays.
+int pfmpe_refine_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_refine_in* in, const pfmpe_refine_params* params,
+                       pfmpe_refine_out* out, pfmpe_refine_row* const* rows, double* const* cov) {
+  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+  pfmpe_ctx* c0 = ctxs[0];
+  if (!in || !out) return fail(c0, PFMPE_E_ARG, "refine_multi: null in/out");
+  if (S > PFMPE_REFINE_MAX_STREAMS) return fail(c0, PFMPE_E_CAP, "refine_multi: S exceeds PFMPE_REFINE_MAX_STREAMS");
+  struct Stream {
+    const double* blobs;
+    int B;
+    pfmpe_refine_params prm;
+  };
+  std::vector<Stream> st(S);
+  int32_t Ks[PFMPE_REFINE_MAX_STREAMS], Bs[PFMPE_REFINE_MAX_STREAMS];
+  int64_t H = 0;
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = ctxs[s];
+    const pfmpe_refine_in& q = in[s];
+    const std::string at = "refine_multi: stream " + std::to_string(s) + ": ";
+    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
+    if (c->device != c0->device) return fail(c0, PFMPE_E_ARG, at + "device must match ctxs[0]");
+    pfmpe_default_refine_params(&st[s].prm);
+    if (params) st[s].prm = params[s];
+    if (q.K < 0 || (q.K > 0 && (!q.poses || !q.corr))) return fail(c0, PFMPE_E_ARG, at + "bad arguments");
+    if (!refine_params_ok(st[s].prm)) return fail(c0, PFMPE_E_ARG, at + "bad parameters");
+    RET(resolve_blobs(c, at + "blobs", &q.blobs, &st[s].blobs, &st[s].B, c0));
+    if (q.K > c->max_particles) return fail(c0, PFMPE_E_CAP, at + "K exceeds max_particles");
+    if (!c->has_model) return fail(c0, PFMPE_E_STATE, at + "set_model first");
+    if (q.K > 0 && !refine_corr_ok(q.corr, (size_t)q.K * kMaxMarkers, c->M, st[s].B))
+      return fail(c0, PFMPE_E_ARG, at + "LED or blob index out of range");
+    if (q.K > 0 && !refine_poses_finite(q.poses, (size_t)q.K)) return fail(c0, PFMPE_E_ARG, at + "non-finite start pose");
+    Ks[s] = q.K;
+    Bs[s] = st[s].B;
+    H += q.K;
+    if (H > PFMPE_REFINE_MULTI_MAX_HYPOTHESES)
+      return fail(c0, PFMPE_E_CAP, at + "the batch exceeds PFMPE_REFINE_MULTI_MAX_HYPOTHESES hypotheses");
+  }
+  static_assert(PFMPE_REFINE_MULTI_MAX_HYPOTHESES <= kPairsChunk, "one launch without a grid stride");
+  pfmpe_refine_plan plan[PFMPE_REFINE_MAX_STREAMS];
+  pfmpe_refine_plan_total tot;
+  pfmpe_plan::refine_plan(Ks, Bs, S, plan, &tot);
+  RET(set_device(c0));
+  // the device block: the upload, then summaries, rows and covariances; the pinned block mirrors it
+  const size_t up = (size_t)tot.upload_bytes, down = (size_t)tot.download_bytes, all = up + down;
+  RET(c0->d_refm.grow(c0, all, all + all / 2));
+  RET(c0->h_refm.grow(c0, all, all + all / 2));
+  unsigned char* h = c0->h_refm.get();
+  unsigned char* d = c0->d_refm.get();
+  std::memset(h, 0, up);  // the gaps between regions and unused marker slots: the same bytes for the same plan
+  RefineDesc* ds = (RefineDesc*)(h + tot.desc_offset);
+  int32_t* stream_of = (int32_t*)(h + tot.stream_of_offset);
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = ctxs[s];
+    const size_t K = (size_t)Ks[s], first = (size_t)plan[s].first;
+    ds[s].model_offset = plan[s].model_offset;
+    ds[s].blobs_offset = plan[s].blobs_offset;
+    ds[s].first = plan[s].first;
+    ds[s].count = Ks[s];
+    ds[s].max_iter = st[s].prm.max_iter;
+    ds[s].revert = st[s].prm.revert_on_divergence ? 1 : 0;
+    ds[s].converged = st[s].prm.converged;
+    for (size_t i = 0; i < K; ++i) stream_of[first + i] = s;
+    if (K > 0) {
+      std::memcpy(h + tot.poses_offset + first * 12 * sizeof(double), in[s].poses, K * 12 * sizeof(double));
+      std::memcpy(h + tot.corr_offset + first * kPairRow * sizeof(uint32_t), in[s].corr, K * kPairRow * sizeof(uint32_t));
+    }
+    std::memcpy(h + plan[s].model_offset, c->markers, sizeof(c->markers));
+    std::memcpy(h + plan[s].model_offset + sizeof(c->markers), c->K, sizeof(c->K));
+    if (st[s].B > 0) std::memcpy(h + plan[s].blobs_offset, st[s].blobs, 2 * (size_t)st[s].B * sizeof(double));
+  }
+  RefineMultiArgs ma{};
+  ma.up = d;
+  ma.desc = (const RefineDesc*)(d + tot.desc_offset);
+  ma.stream_of = (const int32_t*)(d + tot.stream_of_offset);
+  ma.poses = (const double*)(d + tot.poses_offset);
+  ma.corr = (const uint32_t*)(d + tot.corr_offset);
+  const size_t o_rows = up + (size_t)S * sizeof(pfmpe_refine_out), o_cov = o_rows + (size_t)H * sizeof(pfmpe_refine_row);
+  ma.out = (pfmpe_refine_out*)(d + up);
+  ma.rows = (pfmpe_refine_row*)(d + o_rows);
+  ma.cov = (double*)(d + o_cov);
+  ma.H = (int32_t)H;
+  // what comes back: the summaries, then the rows and the covariances as far as somebody wants them
+  bool want_rows = false, want_cov = false;
+  for (int s = 0; s < S; ++s) {
+    want_rows = want_rows || (rows && rows[s] && Ks[s] > 0);
+    want_cov = want_cov || (cov && cov[s] && Ks[s] > 0);
+  }
+  const size_t back = want_cov ? down : want_rows ? o_cov - up : o_rows - up;
+  HIPCHK(c0, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, c0->stream));
+  RET(refine_multi_launch(c0, ma, S));
+  HIPCHK(c0, hipMemcpyAsync(h + up, d + up, back, hipMemcpyDeviceToHost, c0->stream));
+  HIPCHK(c0, hipStreamSynchronize(c0->stream));
+  std::memcpy(out, h + up, (size_t)S * sizeof(pfmpe_refine_out));
+  for (int s = 0; s < S; ++s) {
+    const size_t K = (size_t)Ks[s], first = (size_t)plan[s].first;
+    if (K == 0) continue;
+    if (rows && rows[s]) std::memcpy(rows[s], h + o_rows + first * sizeof(pfmpe_refine_row), K * sizeof(pfmpe_refine_row));
+    if (cov && cov[s]) std::memcpy(cov[s], h + o_cov + first * 36 * sizeof(double), K * 36 * sizeof(double));
+  }
+  return PFMPE_OK;
 }
 
 int pfmpe_host_optimise_pose(const double* markers_xyz, int M, const double* K, const double* blobs, int B,

@@ -1,9 +1,10 @@
-// pfmpe_refine.hip — k_refine / k_refine_fold (pfmpe_refine_poses / pfmpe_refine_cloud) and their launch: Gauss-Newton
-// (pf_gn.hpp) of one hypothesis per lane, fp64 for every state type, and the call's summary.  A TU of its own so it
-// builds beside the others.
+// pfmpe_refine.hip — k_refine / k_refine_fold (pfmpe_refine_poses / pfmpe_refine_cloud), k_refine_multi /
+// k_refine_fold_multi (pfmpe_refine_multi) and their launches: Gauss-Newton (pf_gn.hpp) of one hypothesis per lane,
+// fp64 for every state type, and the call's summary.  A TU of its own so it builds beside the others.
 #include "pf_gn.hpp"
 #include "pf_wave.hpp"
 #include "pfmpe_ctx.hpp"
+#include "pfmpe_refine_plan.hpp"
 
 namespace pfmpe_impl {
 
@@ -147,7 +148,81 @@ __global__ __launch_bounds__(kWave) void k_refine_fold(const RefinePart* __restr
   }
 }
 static_assert(sizeof(pfmpe_refine_row) / sizeof(double) + 36 <= kWave, "k_refine_fold copies a word per lane");
+
+// The batch (pfmpe_refine_multi): one lane per hypothesis of all streams together, no grid stride (H <= kPairsChunk).
+// Lane h looks up its stream and that stream's descriptor, so the model pointers and the parameters are per-lane values
+// (a wave of the usual batch, one hypothesis per stream, holds 64 streams); the arithmetic is k_refine's, the same
+// gn_optimise on the same numbers.  The summaries are k_refine_fold_multi's: nothing is reduced here.
+__global__ __launch_bounds__(kBlock) void k_refine_multi(const RefineMultiArgs ma) {
+  const int h = blockIdx.x * kBlock + threadIdx.x;
+  if (h >= ma.H) return;
+  const RefineDesc d = ma.desc[ma.stream_of[h]];
+  const double* markers = (const double*)(ma.up + d.model_offset);
+  pfmpe_refine_row r;
+  gn_optimise(markers, markers + 3 * kMaxMarkers, (const double*)(ma.up + d.blobs_offset),
+              ma.corr + (size_t)h * (2 * kMaxMarkers), kMaxMarkers, d.max_iter, d.revert, d.converged,
+              ma.poses + 12 * (size_t)h, r, ma.cov + 36 * (size_t)h);
+  ma.rows[h] = r;
+}
+
+// One wave per stream: lane l takes rows first + l, + 64, ... of its stream, forms k_refine's per-lane partial of each
+// (best: the index within the stream), and the wave's merge is the stream's summary; then the best row and covariance
+// are copied, or zeros, as k_refine_fold does for `begin`.  Sums of integers and a total order: the summary is the
+// single call's whatever the shape of the reduction.
+__global__ __launch_bounds__(kWave) void k_refine_fold_multi(const RefineMultiArgs ma) {
+  const RefineDesc d = ma.desc[blockIdx.x];
+  const pfmpe_refine_row* rows = ma.rows + d.first;
+  const double* cov = ma.cov + 36 * d.first;
+  pfmpe_refine_out* out = ma.out + blockIdx.x;
+  RefinePart p = part_zero();
+  for (int i = threadIdx.x; i < d.count; i += kWave) {
+    const pfmpe_refine_row& r = rows[i];
+    RefinePart h = part_zero();
+    h.n_with = r.n_pairs > 0 ? 1 : 0;
+    h.n_conv = r.status == PFMPE_REFINE_CONVERGED ? 1 : 0;
+    h.n_kept = r.status == PFMPE_REFINE_CAP_KEPT ? 1 : 0;
+    h.n_rev = r.status == PFMPE_REFINE_CAP_REVERTED ? 1 : 0;
+    h.it_total = r.iters;
+    h.it_max = r.iters;
+    if (gn_eligible(r)) {
+      h.best_np = r.n_pairs;
+      h.best_rms = r.rms_after;
+      h.best = i;
+    }
+    part_merge(p, h);
+  }
+  part_wave_merge(p);
+  if (threadIdx.x == 0) {
+    out->n = d.count;
+    out->n_with_pairs = p.n_with;
+    out->n_converged = p.n_conv;
+    out->n_cap_kept = p.n_kept;
+    out->n_cap_reverted = p.n_rev;
+    out->iters_total = p.it_total;
+    out->iters_max = p.it_max;
+    out->pad = 0;
+    out->best = p.best;
+  }
+  constexpr int kRowWords = (int)(sizeof(pfmpe_refine_row) / sizeof(double));
+  double* brow = (double*)&out->best_row;
+  const int q = threadIdx.x;
+  if (p.best >= 0) {
+    if (q < kRowWords) brow[q] = ((const double*)(rows + p.best))[q];
+    else if (q < kRowWords + 36) out->best_cov[q - kRowWords] = cov[36 * p.best + (q - kRowWords)];
+  } else {
+    if (q < kRowWords) brow[q] = 0.0;
+    else if (q < kRowWords + 36) out->best_cov[q - kRowWords] = 0.0;
+  }
+}
 }  // namespace
+
+int refine_multi_launch(pfmpe_ctx* c0, const RefineMultiArgs& ma, int S) {
+  const int nblk = (ma.H + kBlock - 1) / kBlock;
+  if (nblk > 0) hipLaunchKernelGGL(k_refine_multi, dim3(nblk), dim3(kBlock), 0, c0->stream, ma);
+  hipLaunchKernelGGL(k_refine_fold_multi, dim3(S), dim3(kWave), 0, c0->stream, ma);
+  HIPCHK(c0, hipGetLastError());
+  return PFMPE_OK;
+}
 
 int refine_launch(pfmpe_ctx* c, const pfmpe_refine_params& prm, const double* poses, const uint32_t* corr, int64_t base,
                   int count, int cap, bool begin) {
