@@ -60,10 +60,12 @@ FrameArgsT<T> build_args(const pfmpe_ctx* c, const pfmpe_frame_in* in) {
   fa.force_iters = in->force_iters;
   {  // fp32: every angle draw of the frame within kSmallAngle -> the short sincos polynomials (wave-uniform)
     const int cap = iter_cap(fa);
-    const double gmax = 1.0 + p.growth * (double)((cap - 1) / 10);
+    // the noise factor 1 + growth * (iter / 10) is linear in the growth step, so its largest magnitude is at the
+    // first iteration (1; the largest with a negative growth) or at the last
+    const double gmax = std::max(1.0, std::abs(1.0 + p.growth * (double)((cap - 1) / 10)));
     double amax = 0.0;
     for (int q = 0; q < 3; ++q) amax = std::max(amax, std::max(std::abs(fa.dlo[q]), std::abs(fa.dhi[q])));
-    fa.small_angles = (sizeof(T) == 4 && amax * std::abs(gmax) <= 0.999 * (double)kSmallAngle) ? 1 : 0;
+    fa.small_angles = (sizeof(T) == 4 && amax * gmax <= 0.999 * (double)kSmallAngle) ? 1 : 0;
   }
   fa.k_upper = (fa.K[3] == (T)0 && fa.K[6] == (T)0 && fa.K[7] == (T)0 && fa.K[8] == (T)1) ? 1 : 0;
   fa.tol = (T)p.tol;

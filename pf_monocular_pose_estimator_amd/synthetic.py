@@ -149,14 +149,19 @@ CONFIGS = {
 }
 
 
+def markers_16() -> np.ndarray:
+    """Sixteen LEDs: the 12-LED object plus four more on its faces."""
+    extra = np.array([[0.05, 0.0, 0.04], [-0.05, 0.02, -0.03], [0.0, 0.06, 0.02], [0.02, -0.05, -0.05]])
+    return np.vstack([markers_12(), extra])
+
+
 def markers_for(M: int) -> np.ndarray:
-    if M == 5:
-        return MARKERS_5.copy()
-    if M == 12:
-        return markers_12()
+    """M rows: of the README five for M <= 5, else of the 16-LED set (whose first 12 are markers_12())."""
+    if M < 0 or M > 16:
+        raise ValueError(f"markers_for: no {M}-LED model (0..16)")
     if M <= 5:
         return MARKERS_5[:M].copy()
-    return markers_12()[:M].copy()
+    return markers_16()[:M].copy()
 
 
 def blobs_for_frame(cfg: StreamConfig, T: np.ndarray, frame: int, markers: np.ndarray) -> np.ndarray:

@@ -28,10 +28,7 @@ TAU = 1e-3
 MM = pf.MAX_MARKERS
 
 
-def markers_16():
-    """Sixteen LEDs: the 12-LED object plus four more on its faces."""
-    extra = np.array([[0.05, 0.0, 0.04], [-0.05, 0.02, -0.03], [0.0, 0.06, 0.02], [0.02, -0.05, -0.05]])
-    return np.vstack([syn.markers_12(), extra])
+markers_16 = syn.markers_16
 
 
 @functools.lru_cache(maxsize=None)

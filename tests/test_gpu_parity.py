@@ -39,7 +39,9 @@ def orc_params_from(prm):
 
 
 def step_both(eng, prm, markers, K, prior, cur, pred, predm, blobs, seed, frame_idx, it=2, dt=0.02,
-              force_iters=0, cam=None, downgrade=None):
+              force_iters=0, cam=None, downgrade=None, ref=None):
+    """One engine step and the oracle's step of the same inputs.  ref: the (out, arrays) pair orc.pf_step returned
+    for exactly these inputs, where several engine shapes are held against one oracle run."""
     fr = eng.make_frame(cur, pred, predm, blobs=blobs, dt=dt, seed=seed, frame_idx=frame_idx, it_since_init=it,
                         force_iters=force_iters, cam_move_inv=cam)
     out = eng.step(fr).as_dict()
@@ -47,6 +49,8 @@ def step_both(eng, prm, markers, K, prior, cur, pred, predm, blobs, seed, frame_
     if out["resampled"]:
         gpu["counts"] = eng.get_counts()
         gpu["resampled"] = eng.get_particles(1)
+    if ref is not None:
+        return out, gpu, ref[0], ref[1]
     ref, arr = orc.pf_step(markers, K, orc_params_from(prm), prior, cur, pred, predm, blobs, it_since_init=it, dt=dt,
                            seed=seed, frame_idx=frame_idx, force_iters=force_iters, cam_move_inv=cam,
                            downgrade=downgrade)
@@ -238,6 +242,36 @@ def rotation_angle(R1, R2):
     return float(2.0 * np.arcsin(min(1.0, d / (2.0 * np.sqrt(2.0)))))
 
 
+def check_fp32_frame(out, gpu, ref, arr, N, rng_mode, seed, frame_idx, markers, K, blobs, prm, downgrade=None,
+                     refine=True):
+    """One fp32 frame against the oracle's step from the same prior (the rules of test_fp32_tolerance's docstring).
+    Returns 1 when the refined-pose criterion was applied (refine, and the two winners carry the same pairs)."""
+    assert out["accepted"] == ref["accepted"]
+    assert out["iters"] == ref["iters"]
+    dw = np.abs(gpu["weights"] - arr["weights"])
+    assert np.sum(dw > 2e-3) <= max(3, N // 1000), np.sort(dw)[-10:]
+    dp = np.abs(gpu["propagated"] - arr["propagated"])
+    assert dp[:, [0, 1, 2, 4, 5, 6, 8, 9, 10]].max() < 1e-5 and dp[:, [3, 7, 11]].max() < 1e-5
+    if not out["resampled"]:
+        return 0
+    c = gpu["counts"].astype(np.int64)
+    c_ref, _ = orc.stratified_resample(gpu["weights"], rng_mode, seed, frame_idx, out["iters"])
+    assert np.sum(c != c_ref) <= 2, np.where(c != c_ref)[0][:10]
+    w = out["winner_idx"]
+    assert c[w] == c.max() and np.argmax(c) == w
+    np.testing.assert_allclose(out["winner_pose"], gpu["propagated"][w], atol=1e-6)
+    proj = np.array([orc.project(K, gpu["propagated"][w], X) for X in markers])
+    _, pairs = orc.likelihood(proj, blobs, prm.tol, prm.tol_pf, downgrade)
+    assert np.array_equal(out["pairs"], pairs)
+    if not refine or not np.array_equal(out["pairs"], ref["pairs"]):
+        return 0
+    pg, _, _ = orc.optimise_pose(markers, K, blobs, out["pairs"], out["winner_pose"])
+    pr, _, _ = orc.optimise_pose(markers, K, blobs, ref["pairs"], ref["winner_pose"])
+    assert np.abs(pg[[3, 7, 11]] - pr[[3, 7, 11]]).max() < 1e-4
+    assert rotation_angle(syn.to44(pg)[:3, :3], syn.to44(pr)[:3, :3]) < 1e-3
+    return 1
+
+
 @pytest.mark.parametrize("rng", ["ref", "philox"])
 @pytest.mark.parametrize("N,M,B,heavy", [(20000, 5, 50, False), (8192, 12, 200, True)])
 def test_fp32_tolerance(rng, N, M, B, heavy):
@@ -258,28 +292,7 @@ def test_fp32_tolerance(rng, N, M, B, heavy):
         seed = 50 + fr.index
         out, gpu, ref, arr = step_both(eng, prm, st.markers, st.K, prior_used, fr.current_pose, fr.predicted_pose,
                                        fr.prediction, fr.blobs, seed=seed, frame_idx=fr.index)
-        assert out["accepted"] == ref["accepted"]
-        assert out["iters"] == ref["iters"]
-        dw = np.abs(gpu["weights"] - arr["weights"])
-        assert np.sum(dw > 2e-3) <= max(3, N // 1000), np.sort(dw)[-10:]
-        dp = np.abs(gpu["propagated"] - arr["propagated"])
-        assert dp[:, [0, 1, 2, 4, 5, 6, 8, 9, 10]].max() < 1e-5 and dp[:, [3, 7, 11]].max() < 1e-5
-        if out["resampled"]:
-            c = gpu["counts"].astype(np.int64)
-            c_ref, _ = orc.stratified_resample(gpu["weights"], RNG[rng], seed, fr.index, out["iters"])
-            assert np.sum(c != c_ref) <= 2, np.where(c != c_ref)[0][:10]
-            w = out["winner_idx"]
-            assert c[w] == c.max() and np.argmax(c) == w
-            np.testing.assert_allclose(out["winner_pose"], gpu["propagated"][w], atol=1e-6)
-            proj = np.array([orc.project(st.K, gpu["propagated"][w], X) for X in st.markers])
-            _, pairs = orc.likelihood(proj, fr.blobs, prm.tol, prm.tol_pf)
-            assert np.array_equal(out["pairs"], pairs)
-            if np.array_equal(out["pairs"], ref["pairs"]):
-                pg, _, _ = orc.optimise_pose(st.markers, st.K, fr.blobs, out["pairs"], out["winner_pose"])
-                pr, _, _ = orc.optimise_pose(st.markers, st.K, fr.blobs, ref["pairs"], ref["winner_pose"])
-                assert np.abs(pg[[3, 7, 11]] - pr[[3, 7, 11]]).max() < 1e-4
-                assert rotation_angle(syn.to44(pg)[:3, :3], syn.to44(pr)[:3, :3]) < 1e-3
-                compared += 1
+        compared += check_fp32_frame(out, gpu, ref, arr, N, RNG[rng], seed, fr.index, st.markers, st.K, fr.blobs, prm)
     # the pose criterion must actually have been applied (not vacuously skipped on differing winners)
     assert compared >= n_frames - 1, compared
     eng.close()
