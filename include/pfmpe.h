@@ -314,7 +314,9 @@ int pfmpe_host_init_plan(const int32_t* M, const int32_t* B, int S, int num_cu, 
  * CHAIN_APPROX_NONE) with 2.4's zeroed 1-pixel frame, contourArea / boundingRect / moments, the blob
  * size-aspect-circularity filter, the centre + ROI offset (cv::Point2f) and undistortPoints(K, D, P = K).
  * K is the context's model K.  Output: image_points_ (undistorted px, findContours order) and the
- * distorted centres (distorted_detection_centers_).  image = NULL uses the staged image. */
+ * distorted centres (distorted_detection_centers_).  image = NULL uses the staged image.  blobs: max_out x 2
+ * doubles, distorted: max_out x 2 floats (may be NULL); min(n, max_out, PFMPE_MAX_BLOBS) rows are written and
+ * nothing else of the arrays is touched. */
 typedef struct {
   int32_t threshold_value;          /* detection_threshold_value_ (threshold_value, README default 240) */
   int32_t active_markers;           /* 1: THRESH_TOZERO, 0: THRESH_BINARY_INV (LD:56-59)               */
@@ -327,9 +329,10 @@ typedef struct {
   int32_t roi_x, roi_y, roi_w, roi_h; /* region_of_interest_; roi_w / roi_h < 0 = the whole image   */
 } pfmpe_detect_params;
 typedef struct {
-  int32_t n;                        /* detections (all of them; min(n, max_out) written)              */
-  int32_t n_components;             /* 8-connected components (contours) examined                     */
-  int32_t overflow;                 /* more than 8192 components: the rest were not examined          */
+  int32_t n;                        /* detections (all of them; min(n, max_out, PFMPE_MAX_BLOBS) written) */
+  int32_t n_components;             /* 8-connected components (contours) found, all of them           */
+  int32_t overflow;                 /* more than 8192 components: 8192 of them were examined (which   */
+                                    /* ones is unspecified); n counts the detections among those      */
   int32_t pad;
 } pfmpe_detect_out;
 void pfmpe_default_detect_params(pfmpe_detect_params* p);

@@ -23,7 +23,8 @@
 //      integer `rect.width / 2`                                                                LD:86-108
 //    * cv::undistortPoints(K, D, noArray(), P = K): 5 fixed iterations of the plumb_bob inverse, then
 //      P (cvUndistortPoints)                                                                   LD:192-209
-//  Parity status: PARITY UNPINNED (no OpenCV here, no reference fixtures).  Not restated: components
+//  Parity status: PARITY UNPINNED (no OpenCV here, no reference fixtures); the mask and the component count are
+//  held to a numpy restatement written by other means (tests/detect_cases.py).  Not restated: components
 //  nested inside another component's hole (RETR_EXTERNAL drops them; this restatement keeps them),
 //  the exposure-time control (LD:122-160, a camera side effect) and the simulated occlusions / false
 //  detections (LD:170-183, test hooks off by default).
@@ -129,9 +130,11 @@ typedef struct {
 // be NULL).
 // Output: up to max_out detections in findContours order: distorted (float, full-image px) and
 // undistorted (double(float)) centres; returns the count, or < 0 on bad arguments.
-int orc_find_leds(const uint8_t* image, int width, int height, int pitch, const OrcDetectParams* p, const double* K,
-                  const double* D, int max_out, float* distorted, double* undistorted, double* areas,
-                  uint8_t* mask_out) {
+// stats (may be NULL): [0] the 8-connected components found (contours, before the filter), [1] the points of the
+// longest contour.
+int orc_find_leds_stats(const uint8_t* image, int width, int height, int pitch, const OrcDetectParams* p,
+                        const double* K, const double* D, int max_out, float* distorted, double* undistorted,
+                        double* areas, uint8_t* mask_out, int* stats) {
   if (!image || !p || width < 1 || height < 1 || pitch < width) return -1;
   const int rx = p->roi_x, ry = p->roi_y, W = p->roi_w, H = p->roi_h;
   if (rx < 0 || ry < 0 || W < 1 || H < 1 || rx + W > width || ry + H > height) return -1;
@@ -196,6 +199,11 @@ int orc_find_leds(const uint8_t* image, int width, int height, int pitch, const 
       found.push_back(fetch_contour(m, W, x, y));
     }
   std::reverse(found.begin(), found.end());
+  if (stats) {
+    stats[0] = (int)found.size();
+    stats[1] = 0;
+    for (const Contour& c : found) stats[1] = std::max(stats[1], (int)c.x.size());
+  }
   // per contour: area, bounding rect, moments, filter (LD:86-108); undistort (LD:192-209)
   const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
   const double ifx = 1. / fx, ify = 1. / fy;
@@ -263,6 +271,13 @@ int orc_find_leds(const uint8_t* image, int width, int height, int pitch, const 
     ++out;
   }
   return out;
+}
+
+int orc_find_leds(const uint8_t* image, int width, int height, int pitch, const OrcDetectParams* p, const double* K,
+                  const double* D, int max_out, float* distorted, double* undistorted, double* areas,
+                  uint8_t* mask_out) {
+  return orc_find_leds_stats(image, width, height, pitch, p, K, D, max_out, distorted, undistorted, areas, mask_out,
+                             nullptr);
 }
 
 }  // extern "C"

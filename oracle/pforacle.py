@@ -145,6 +145,8 @@ def load() -> C.CDLL:
     lib.orc_find_leds.restype = C.c_int
     lib.orc_find_leds.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.POINTER(OrcDetectParams), dp, dp,
                                   C.c_int, C.POINTER(C.c_float), dp, dp, C.POINTER(C.c_uint8)]
+    lib.orc_find_leds_stats.restype = C.c_int
+    lib.orc_find_leds_stats.argtypes = lib.orc_find_leds.argtypes + [C.POINTER(C.c_int)]
     lib.orc_initialise.restype = C.c_int
     lib.orc_initialise.argtypes = [C.c_int, dp, dp, C.c_int, dp, C.POINTER(OrcInitParams), C.c_int, u32p, u32p,
                                    dp, C.POINTER(OrcInitOut)]
@@ -424,8 +426,10 @@ def initialise(markers, K, blobs, n_particles, particles=None, tol=5.0, certaint
 # ------------------------------------------------------------------ LED detector (LEDDetector::findLeds)
 def find_leds(image, K, D, threshold_value=240, gaussian_sigma=0.6, min_blob_area=20, max_blob_area=160,
               max_width_height_distortion=0.7, max_circular_distortion=0.7, active_markers=True, roi=None,
-              max_out=1024, want_mask=False):
-    """-> (undistorted B x 2, distorted B x 2 float32, areas B, mask or None)."""
+              max_out=1024, want_mask=False, want_stats=False):
+    """-> (undistorted B x 2, distorted B x 2 float32, areas B, mask or None); with want_stats a fifth item, the
+    dict {n: detections before max_out cuts them, n_components: 8-connected components (contours) before the filter,
+    longest_contour: points of the longest contour}."""
     img = np.ascontiguousarray(image, dtype=np.uint8)
     h, w = img.shape
     rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
@@ -435,11 +439,14 @@ def find_leds(image, K, D, threshold_value=240, gaussian_sigma=0.6, min_blob_are
     dist = np.zeros((max_out, 2), dtype=np.float32)
     areas = np.zeros(max_out)
     mask = np.zeros((rh, rw), dtype=np.uint8) if want_mask else None
-    n = load().orc_find_leds(img.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, img.strides[0], C.byref(prm),
-                             _p(_d(K).reshape(9)), _p(_d(D).reshape(5)), max_out,
-                             dist.ctypes.data_as(C.POINTER(C.c_float)), _p(und), _p(areas),
-                             mask.ctypes.data_as(C.POINTER(C.c_uint8)) if want_mask else None)
-    if n < 0:
+    stats = (C.c_int * 2)()
+    n_all = load().orc_find_leds_stats(img.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, img.strides[0], C.byref(prm),
+                                       _p(_d(K).reshape(9)), _p(_d(D).reshape(5)), max_out,
+                                       dist.ctypes.data_as(C.POINTER(C.c_float)), _p(und), _p(areas),
+                                       mask.ctypes.data_as(C.POINTER(C.c_uint8)) if want_mask else None, stats)
+    if n_all < 0:
         raise ValueError("orc_find_leds: bad arguments")
-    n = min(n, max_out)
+    n = min(n_all, max_out)
+    if want_stats:
+        return und[:n], dist[:n], areas[:n], mask, {"n": n_all, "n_components": stats[0], "longest_contour": stats[1]}
     return und[:n], dist[:n], areas[:n], mask

@@ -648,7 +648,7 @@ class Engine:
             pitch = w
         self._chk(self.lib.pfmpe_find_leds(self.ctx, ip, w, h, pitch, C.byref(p), _dptr(blobs),
                                            dist.ctypes.data_as(C.POINTER(C.c_float)), max_out, C.byref(out)))
-        n = min(out.n, max_out)
+        n = min(out.n, max_out, MAX_BLOBS)  # the rows the call wrote
         return blobs[:n].copy(), dist[:n].copy(), {"n": out.n, "n_components": out.n_components,
                                                     "overflow": out.overflow}
 
@@ -683,7 +683,7 @@ class Engine:
                                                  dist.ctypes.data_as(C.POINTER(C.c_float)), max_out, outs))
         res = []
         for r in range(R):
-            n = min(outs[r].n, max_out)
+            n = min(outs[r].n, max_out, MAX_BLOBS)  # the rows the call wrote
             res.append((blobs[r, :n].copy(), dist[r, :n].copy(),
                         {"n": outs[r].n, "n_components": outs[r].n_components, "overflow": outs[r].overflow}))
         return res
@@ -718,7 +718,7 @@ class Engine:
         del keep
         res = []
         for r in range(R):
-            n = min(outs[r].n, max_out)
+            n = min(outs[r].n, max_out, MAX_BLOBS)  # the rows the call wrote
             res.append((blobs[r, :n].copy(), dist[r, :n].copy(),
                         {"n": outs[r].n, "n_components": outs[r].n_components, "overflow": outs[r].overflow}))
         return res
