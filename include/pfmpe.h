@@ -690,6 +690,40 @@ int pfmpe_host_optimise_pose(const double* markers_xyz, int M, const double* K, 
                              const uint32_t* corr, int n_rows, const pfmpe_refine_params* params, const double* pose12,
                              pfmpe_refine_row* row, double* cov36);
 
+/* The step and the refinement of its winner in one blocking call: every accepted frame of the reference ends with
+ * optimisePose on the step's winner (PE:687-690), which pfmpe_step followed by pfmpe_refine_poses does with two host
+ * round trips.  Here a one-wave kernel (k_step_tail) runs behind every launch that can finish the frame, on the
+ * frame's stream: it takes the winner pose and its pair row from the frame record where the device left it, runs the
+ * Gauss-Newton of pfmpe_refine_poses on them and publishes the result as the step publishes its record; the host
+ * waits once.  The fp64 blobs (the caller's list, or the bank frame's host copy), the model and the parameters are
+ * staged in a mapped pinned block of the context (grown on demand, never shrunk) that the host writes once per call;
+ * no copy command is issued.
+ * Defined by equivalence: `out` and the context's state afterwards are those of pfmpe_step(ctx, in, out).  With
+ * out->flag_fail == PFMPE_FLAG_ACCEPTED and a finite winner pose, gn, row and cov36 are byte for byte what
+ *   pfmpe_refine_poses(ctx, {in->blobs, in->B, in->bank_frame}, params, out->winner_pose, out->corr, 1, gn, row, cov36)
+ * writes; otherwise (a rejected frame, a non-finite winner pose) gn is that call's K = 0 summary (n = 0, best = -1,
+ * zeroed best_row and best_cov) and row and cov36 are not written.  row and cov36 may be NULL; params NULL: the
+ * defaults.  params is checked by pfmpe_refine_poses' rules, and `in` by pfmpe_step's, before anything is staged or
+ * launched: on an error no context changes.  With PFMPE_OPT_TIMING the tail is one more PFMPE_K_AUX bracket (on a
+ * one-launch frame: the tail alone).
+ * A tail that finds no finished record of its frame is never an error: the call then refines through
+ * pfmpe_refine_poses' own path, returns the same bytes and counts it in PFMPE_INFO_TAIL_FALLBACKS. */
+int pfmpe_step_refine(pfmpe_ctx* ctx, const pfmpe_frame_in* in, const pfmpe_refine_params* params,
+                      pfmpe_frame_out* out, pfmpe_refine_out* gn, pfmpe_refine_row* row, double* cov36);
+/* The batch: pfmpe_step_multi with every stream's tail in one launch per round, one wave per stream.  Stream s gets
+ * exactly what pfmpe_step_refine(ctxs[s], &in[s], &params[s], &out[s], &gn[s], &rows[s], &cov[36 * s]) gives (params
+ * NULL or S records, rows NULL or S rows, cov NULL or S x 36 doubles; the row and the covariance of a stream that is
+ * not refined are not written).  Limits, member rules, ordering and errors are pfmpe_step_multi's, the texts begin
+ * "step_refine_multi: stream <s>: "; ctxs[0] leads and owns the staging block. */
+int pfmpe_step_refine_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, const pfmpe_refine_params* params,
+                            pfmpe_frame_out* out, pfmpe_refine_out* gn, pfmpe_refine_row* rows, double* cov);
+/* host-only (no GPU, no context): the tail's own __host__ __device__ code for a caller-given finished frame, blobs
+ * B x 2.  PFMPE_E_ARG for a NULL pointer (row, cov36 and params may be NULL), M outside 1..PFMPE_MAX_MARKERS, B < 0,
+ * bad parameters, or an index of frame->corr out of range in a frame that is refined. */
+int pfmpe_host_step_tail(const double* markers_xyz, int M, const double* K, const double* blobs, int B,
+                         const pfmpe_frame_out* frame, const pfmpe_refine_params* params, pfmpe_refine_out* gn,
+                         pfmpe_refine_row* row, double* cov36);
+
 /* Engine options (value semantics in brackets; defaults first):
  *   PFMPE_OPT_RECORD_COUNTS [0|1]  keep counterMeas on device for pfmpe_get_counts
  *   PFMPE_OPT_PRUNE         [1|0]  exact x-window blob pruning in the likelihood (0 = scan all B blobs)
@@ -737,7 +771,8 @@ enum { PFMPE_INFO_FUSED = 1,            /* current one-launch mode (0/1/2; 0 aft
        PFMPE_INFO_LAST_GRID = 7,        /* 1: the last frame's blob table searched its cell grid; 0: the
                                          * x-buckets (no grid for this table or its window; fp64)    */
        PFMPE_INFO_LAST_RESAMPLE = 8,    /* PFMPE_RESAMPLE_* of the last two-launch resampling (-1: none) */
-       PFMPE_INFO_NUM_CU = 9 };         /* compute units of the context's device (pfmpe_host_init_plan's num_cu) */
+       PFMPE_INFO_NUM_CU = 9,           /* compute units of the context's device (pfmpe_host_init_plan's num_cu) */
+       PFMPE_INFO_TAIL_FALLBACKS = 10 };/* pfmpe_step_refine(_multi) frames of this context refined by the recovery path */
 /* The two-launch shape's weighing pass: one block per 256 particles (k_propagate_weigh), or
  * resident blocks streaming over them with the next block's state prefetched (k_weigh_stream + k_group +
  * k_top), or the streaming pass with two particles per lane in packed fp32 (k_weigh_pk: 5 markers, fp32 / fp16

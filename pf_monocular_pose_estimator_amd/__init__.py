@@ -23,6 +23,7 @@ from ._capi import (  # noqa: F401
     INIT_MAX_STREAMS, INFO_NUM_CU, InitIn, InitPlan, InitParams, InitOut, host_init_plan,
     REFINE_MAX_STREAMS, REFINE_MULTI_MAX_HYPOTHESES, REFINE_DESC_BYTES, RefineIn, RefinePlan, RefinePlanTotal,
     host_refine_plan,
+    DIAG_TAIL_MISS, INFO_TAIL_FALLBACKS, host_step_tail,
 )
 
 __all__ = [

@@ -27,11 +27,12 @@ DIAG_LAG_LOADS, DIAG_ABANDON, DIAG_NO_STREAM, DIAG_FORCE_STREAM, DIAG_SERIAL_TOP
 DIAG_NO_PK, DIAG_CORRUPT_DESC, DIAG_NO_DEFER, DIAG_BLOCK_RESAMPLE, DIAG_MIN_SIDE = 4096, 8192, 16384, 32768, 65536
 DIAG_ABANDON_FINISH = 131072
 DIAG_DET_COPY = 524288  # find_leds_streams: the crops go up by one async copy command instead of the pull kernel (A/B)
+DIAG_TAIL_MISS = 1 << 20  # step_refine(_multi): the tail reports "record not ready" (the recovery path)
 DIAG_ASSOC_DIRECT = 262144  # assoc_stats: every vote straight into the device table (the path of tables too large for LDS)
 OPT_DEFER_RESAMPLE = 9
 SHAPE_TWO_LAUNCH, SHAPE_FRAME, SHAPE_FRAME2 = 0, 1, 2
 INFO_FUSED, INFO_FUSED_FALLBACKS, INFO_LAST_SHAPE, INFO_GUARD_SKIPS, INFO_N, INFO_LAST_WEIGH_PASS = 1, 2, 3, 4, 5, 6
-INFO_LAST_GRID, INFO_LAST_RESAMPLE, INFO_NUM_CU = 7, 8, 9
+INFO_LAST_GRID, INFO_LAST_RESAMPLE, INFO_NUM_CU, INFO_TAIL_FALLBACKS = 7, 8, 9, 10
 WEIGH_BLOCKS, WEIGH_STREAM, WEIGH_PK = 0, 1, 2
 RESAMPLE_BLOCKS, RESAMPLE_OWNERS = 0, 1
 CLOUD_WEIGHTED, CLOUD_POSTERIOR = 0, 1
@@ -58,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "pfmpe_find_leds_streams", "pfmpe_host_detect_plan", "pfmpe_host_detect_pack",
     "pfmpe_initialise_multi", "pfmpe_host_init_plan",
     "pfmpe_refine_multi", "pfmpe_host_refine_plan",
+    "pfmpe_step_refine", "pfmpe_step_refine_multi", "pfmpe_host_step_tail",
 )
 DETECT_MAX_ROIS = 64
 DETECT_MAX_IMAGES = 64
@@ -318,6 +320,12 @@ def load() -> C.CDLL:
                                    C.POINTER(P), C.POINTER(dp)]),
         "pfmpe_host_refine_plan": (I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, C.POINTER(RefinePlan),
                                        C.POINTER(RefinePlanTotal)]),
+        "pfmpe_step_refine": (I, [P, C.POINTER(FrameIn), C.POINTER(RefineParams), C.POINTER(FrameOut),
+                                  C.POINTER(RefineOut), C.POINTER(RefineRow), dp]),
+        "pfmpe_step_refine_multi": (I, [C.POINTER(P), I, C.POINTER(FrameIn), C.POINTER(RefineParams), C.POINTER(FrameOut),
+                                        C.POINTER(RefineOut), C.POINTER(RefineRow), dp]),
+        "pfmpe_host_step_tail": (I, [dp, I, dp, dp, I, C.POINTER(FrameOut), C.POINTER(RefineParams), C.POINTER(RefineOut),
+                                     C.POINTER(RefineRow), dp]),
         "pfmpe_predict_roi": (I, [P, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
         "pfmpe_predict_roi_multi": (I, [C.POINTER(P), I, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
         "pfmpe_host_predict_roi": (I, [dp, I, dp, dp, I64, C.POINTER(RoiIn), C.POINTER(RoiOut)]),
@@ -513,6 +521,52 @@ class Engine:
         for e, o in zip(engines, outs):
             e._last_out = o
         return outs
+
+    def step_refine(self, frame: FrameIn, params=None, want_row: bool = False, row=None, cov=None):
+        """The step and the Gauss-Newton refinement of its winner in one blocking call (pfmpe_step_refine): what
+        step(frame) followed by refine_poses of out.winner_pose / out.corr gives, with one wait.  Returns
+        (FrameOut, RefineOut, row, cov): row (a RefineRow) and cov (36 doubles) with want_row, or the caller's own
+        `row` / `cov` buffers, which a frame that is not refined leaves as they were; else None."""
+        out, gn = FrameOut(), RefineOut()
+        if want_row and row is None:
+            row = RefineRow()
+        if want_row and cov is None:
+            cov = np.zeros(36, dtype=np.float64)
+        self._chk(self.lib.pfmpe_step_refine(
+            self.ctx, C.byref(frame), C.byref(params) if params is not None else None, C.byref(out), C.byref(gn),
+            C.byref(row) if row is not None else None, _dptr(cov) if cov is not None else None))
+        self._last_out = out
+        return out, gn, row, cov
+
+    @staticmethod
+    def step_refine_multi(engines, frames, params=None, want_rows: bool = False, rows=None, cov=None):
+        """One frame of each engine with its winner's refinement as ONE batch (pfmpe_step_refine_multi): stream s gets
+        what engines[s].step_refine(frames[s], params[s]) gives.  params: None, one RefineParams for all, or one per
+        engine.  Returns (outs, gns, rows, cov): lists of FrameOut and RefineOut, and with want_rows (or the caller's
+        own buffers) a (RefineRow * S) array and an (S, 36) array, else None."""
+        S = len(engines)
+        if S != len(frames) or S == 0:
+            raise ValueError("step_refine_multi: one frame per engine")
+        ctxs = (C.c_void_p * S)(*[e.ctx.value for e in engines])
+        arr_in = (FrameIn * S)(*frames)
+        arr_out, arr_gn = (FrameOut * S)(), (RefineOut * S)()
+        ps = None
+        if params is not None:
+            ps = (RefineParams * S)()
+            for s in range(S):
+                src = params[s] if isinstance(params, (list, tuple)) else params
+                ps[s].max_iter, ps[s].revert_on_divergence, ps[s].converged = (src.max_iter, src.revert_on_divergence,
+                                                                               src.converged)
+        if want_rows and rows is None:
+            rows = (RefineRow * S)()
+        if want_rows and cov is None:
+            cov = np.zeros((S, 36), dtype=np.float64)
+        engines[0]._chk(engines[0].lib.pfmpe_step_refine_multi(
+            ctxs, S, arr_in, ps, arr_out, arr_gn, rows, _dptr(cov) if cov is not None else None))
+        outs = list(arr_out)
+        for e, o in zip(engines, outs):
+            e._last_out = o
+        return outs, list(arr_gn), rows, cov
 
     @staticmethod
     def make_roi_in(prediction, predicted_pose, D, image_w, image_h, border, cam_move_inv=None) -> RoiIn:
@@ -1056,6 +1110,24 @@ def host_optimise_pose(markers, K, blobs, pairs, pose, params=None):
     if rc != OK:
         raise PFError(rc, "host_optimise_pose: bad arguments")
     return np.frombuffer(bytes(row), dtype=REFINE_ROW_DTYPE)[0].copy(), cov
+
+
+def host_step_tail(markers, K, blobs, frame: FrameOut, params=None, row=None, cov=None):
+    """The step's tail on the host (pfmpe_host_step_tail; no GPU): what step_refine publishes for the finished frame
+    `frame` against the blob list `blobs`.  Returns (RefineOut, row, cov); the caller's own `row` / `cov` buffers are
+    left as they were when the frame is not refined."""
+    m = np.ascontiguousarray(markers, dtype=np.float64).reshape(-1, 3)
+    k = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+    b = np.ascontiguousarray(blobs if blobs is not None else np.zeros((0, 2)), dtype=np.float64).reshape(-1, 2)
+    gn = RefineOut()
+    row = RefineRow() if row is None else row
+    cov = np.zeros(36, dtype=np.float64) if cov is None else cov
+    rc = load().pfmpe_host_step_tail(_dptr(m), m.shape[0], _dptr(k), _dptr(b) if b.shape[0] else None, b.shape[0],
+                                     C.byref(frame), C.byref(params) if params is not None else None, C.byref(gn),
+                                     C.byref(row), _dptr(cov))
+    if rc != OK:
+        raise PFError(rc, "pfmpe_host_step_tail: bad arguments")
+    return gn, row, cov
 
 
 def host_assoc_summary(votes) -> dict:

@@ -201,8 +201,9 @@ enum : int {
                               // k_resample_owners' wave per 256 (A/B, identity tests)
   kDiagAssocDirect = 262144,  // pfmpe_assoc_stats: every vote straight into the device table even when the bins fit
                               // in LDS (tests: both voting paths on one input)
-  kDiagDetCopy = 524288       // pfmpe_find_leds_streams: the crops go up by one async copy command instead of the
+  kDiagDetCopy = 524288,      // pfmpe_find_leds_streams: the crops go up by one async copy command instead of the
                               // pull kernel k_detm_pull (A/B)
+  kDiagTailMiss = 1 << 20     // pfmpe_step_refine(_multi): the tail reports "record not ready" (the recovery test)
 };
 
 // flat hand-off (k_frame2, pf_kernels.hpp): the sizes of its sharded arrival counters

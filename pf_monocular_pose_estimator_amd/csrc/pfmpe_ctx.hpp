@@ -176,6 +176,14 @@ struct pfmpe_ctx : CtxQueue {
   // rows and covariances, and the pinned block the upload is built in and the results land in; grown on demand
   Buf<unsigned char> d_refm;
   Buf<unsigned char, Mem::Pinned> h_refm;
+  // pfmpe_step_refine / pfmpe_step_refine_multi (owned by the call's context / the batch's first context): the mapped
+  // pinned block of pf_tail.hpp, which the host writes once per call and k_step_tail reads and publishes into (the
+  // descriptors, every stream's tail record, every stream's fp64 model and blobs); grown on demand, never shrunk.
+  // tail_S: streams of the fused call now running on this context's stream (0: none, no tail is launched).
+  Buf<unsigned char, Mem::Mapped> h_tail;
+  int tail_S = 0;
+  int32_t tail_seq0 = 0;           // a single call: the context's sequence number when the call began
+  int64_t tail_fallbacks = 0;      // PFMPE_INFO_TAIL_FALLBACKS
   Buf<unsigned char> d_init;       // initialisation scratch (pfmpe_init.hip), grown on demand
   // the initialisation (owned by the batch's first context; pfmpe_initialise and pfmpe_p3p_histogram are batches of
   // one): the pinned block its read-backs land in (every stream's histogram; every stream's check results), grown on
@@ -642,6 +650,14 @@ struct RefineMultiArgs {
 // k_refine_multi over the H hypotheses (skipped when H = 0), then k_refine_fold_multi, one wave per stream, on the
 // leader's stream.
 int refine_multi_launch(pfmpe_ctx* c0, const RefineMultiArgs& ma, int S);
+
+// k_step_tail (pfmpe_refine.hip) for the c->tail_S streams staged in c->h_tail, on c's stream, bracketed as
+// PFMPE_K_AUX: each stream's wave looks for the finished record of frame sequence seq0 + delta.
+int tail_launch(pfmpe_ctx* c, int32_t delta);
+// behind a launch that can finish context c's own frame (nothing unless a pfmpe_step_refine is running)
+inline int tail_after(pfmpe_ctx* c) {
+  return c->tail_S ? tail_launch(c, (c->seq - c->tail_seq0) & 0x3fffffff) : (int)PFMPE_OK;
+}
 
 // ---------------------------------------------------------------------- shared preambles of the entry points
 // the transfer buffer (N x 12 doubles), written and read inside one blocking call by every user

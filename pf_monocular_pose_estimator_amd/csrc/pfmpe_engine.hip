@@ -7,6 +7,7 @@
 #include "pf_gn.hpp"
 #include "pf_likelihood.hpp"
 #include "pf_roi.hpp"
+#include "pf_tail.hpp"
 #include "pfmpe_prior.hpp"
 #include "pfmpe_refine_plan.hpp"
 
@@ -399,8 +400,8 @@ int pfmpe_stage_blob_bank(pfmpe_ctx* c, const double* blobs, const int32_t* offs
   return build_bank(c);
 }
 
-int pfmpe_step(pfmpe_ctx* c, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
-  RET(check_step(c, in, out));
+// pfmpe_step behind its checks (also pfmpe_step_refine's frame)
+static int step_run(pfmpe_ctx* c, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
   RET(set_device(c));
   const unsigned char* table = c->d_table.get();
   const int B = in->B;
@@ -427,18 +428,29 @@ int pfmpe_step(pfmpe_ctx* c, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
   return PFMPE_OK;
 }
 
-int pfmpe_step_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
+int pfmpe_step(pfmpe_ctx* c, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
+  RET(check_step(c, in, out));
+  return step_run(c, in, out);
+}
+
+// pfmpe_step_multi's checks under the entry point's name `who` (also pfmpe_step_refine_multi's), and the batch behind
+// them
+static int step_multi_check(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, pfmpe_frame_out* out,
+                            const std::string& who) {
   if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
   pfmpe_ctx* c0 = ctxs[0];
-  if (!in || !out) return fail(c0, PFMPE_E_ARG, "step_multi: null in/out");
-  if (S > 65535) return fail(c0, PFMPE_E_CAP, "step_multi: at most 65535 streams per batch");
-  RET(check_members(
-      ctxs, S, "step_multi", "device, state type, RNG mode and pruning",
+  if (!in || !out) return fail(c0, PFMPE_E_ARG, who + ": null in/out");
+  if (S > 65535) return fail(c0, PFMPE_E_CAP, who + ": at most 65535 streams per batch");
+  return check_members(
+      ctxs, S, who.c_str(), "device, state type, RNG mode and pruning",
       [&](const pfmpe_ctx* c) { return c->params.rng_mode == c0->params.rng_mode && c->prune == c0->prune; },
       [&](int s, const std::string& at) {
         const int rc = check_step(ctxs[s], &in[s], &out[s]);
         return rc == PFMPE_OK ? rc : fail(c0, rc, at + ctxs[s]->err);  // the per-stream code (E_ARG / E_CAP / E_STATE)
-      }));
+      });
+}
+static int step_multi_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
+  pfmpe_ctx* c0 = ctxs[0];
   c0->mt_enter = now_ns();
   RET(set_device(c0));
   c0->timing_now = c0->timing > 0 && (c0->timing_frame++ % c0->timing) == 0;  // batches timed on the leader
@@ -459,6 +471,11 @@ int pfmpe_step_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, pf
   c0->mt_ns[3] += now_ns() - t_r;
   c0->mt_batches += 1;
   return PFMPE_OK;
+}
+
+int pfmpe_step_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, pfmpe_frame_out* out) {
+  RET(step_multi_check(ctxs, S, in, out, "step_multi"));
+  return step_multi_run(ctxs, S, in, out);
 }
 
 int pfmpe_step_multi_batch(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, int n, pfmpe_frame_out* out,
@@ -1238,6 +1255,238 @@ int pfmpe_host_optimise_pose(const double* markers_xyz, int M, const double* K, 
   return PFMPE_OK;
 }
 
+// ---- the step with its refinement (pf_tail.hpp; k_step_tail in pfmpe_refine.hip)
+namespace {
+// pfmpe_refine_poses' summary of one hypothesis from its row and covariance (k_refine + k_refine_fold for K = 1)
+void tail_summary(const pfmpe_refine_row& r, const double* cov, pfmpe_refine_out* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->n = 1;
+  o->n_with_pairs = r.n_pairs > 0 ? 1 : 0;
+  o->n_converged = r.status == PFMPE_REFINE_CONVERGED ? 1 : 0;
+  o->n_cap_kept = r.status == PFMPE_REFINE_CAP_KEPT ? 1 : 0;
+  o->n_cap_reverted = r.status == PFMPE_REFINE_CAP_REVERTED ? 1 : 0;
+  o->iters_total = r.iters;
+  o->iters_max = r.iters;
+  o->best = -1;
+  if (gn_eligible(r)) {
+    o->best = 0;
+    o->best_row = r;
+    std::memcpy(o->best_cov, cov, sizeof(o->best_cov));
+  }
+}
+// its K = 0 summary
+void tail_empty(pfmpe_refine_out* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->best = -1;
+}
+
+// The staging block of S streams: the descriptors, the tail records, then every stream's model and blobs.
+struct TailLayout {
+  size_t rec_off, in_off;
+  static size_t align(size_t x) { return (x + 255) / 256 * 256; }
+  explicit TailLayout(int S) : rec_off(align((size_t)S * sizeof(TailDesc))), in_off(rec_off + (size_t)S * sizeof(TailRec)) {}
+  static size_t stream_bytes(int B) { return align(kTailModelBytes + 2 * (size_t)B * sizeof(double)); }
+};
+struct TailStream {
+  const pfmpe_ctx* c;
+  const double* blobs;  // the caller's list, or the bank frame's host copy
+  int B;
+  pfmpe_refine_params prm;
+};
+// the step's blobs in fp64 (check_step has validated the request)
+void tail_blobs(const pfmpe_ctx* c, const pfmpe_frame_in* in, TailStream* st) {
+  st->c = c;
+  st->B = in->B;
+  st->blobs = in->bank_frame >= 0 ? c->bank_blobs.data() + 2 * (size_t)c->bank_offsets[in->bank_frame] : in->blobs;
+}
+// Written once per call, before the first launch: every record's granules zeroed (no word of an earlier call carries
+// a tag this call waits for), the descriptors, the models and the blobs.  Nothing of an earlier call is pending on
+// the leader's stream (the calls are blocking; a failed frame drained it).
+int tail_stage(pfmpe_ctx* c0, const std::vector<TailStream>& st) {
+  const int S = (int)st.size();
+  const TailLayout L(S);
+  size_t need = L.in_off;
+  for (const TailStream& t : st) need += TailLayout::stream_bytes(t.B);
+  if (need > UINT32_MAX) return fail(c0, PFMPE_E_CAP, "step_refine: the staging block exceeds 4 GiB");
+  RET(c0->h_tail.grow(c0, need, need + need / 2));
+  unsigned char* h = c0->h_tail.get();
+  unsigned char* d = c0->h_tail.dev();
+  std::memset(h + L.rec_off, 0, (size_t)S * sizeof(TailRec));
+  size_t off = L.in_off;
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = st[s].c;
+    TailDesc x{};
+    x.rec = ((const RecOut*)c->h_rec.dev())->g;
+    x.out = ((TailRec*)(d + L.rec_off) + s)->g;
+    x.model_off = (uint32_t)off;
+    x.blobs_off = (uint32_t)(off + kTailModelBytes);
+    x.seq0 = c->seq;
+    x.M = c->M;
+    x.B = st[s].B;
+    x.max_iter = st[s].prm.max_iter;
+    x.revert = st[s].prm.revert_on_divergence ? 1 : 0;
+    x.converged = st[s].prm.converged;
+    std::memcpy(h + (size_t)s * sizeof(TailDesc), &x, sizeof(x));
+    std::memcpy(h + off, c->markers, sizeof(c->markers));
+    std::memcpy(h + off + sizeof(c->markers), c->K, sizeof(c->K));
+    if (st[s].B > 0) std::memcpy(h + x.blobs_off, st[s].blobs, 2 * (size_t)st[s].B * sizeof(double));
+    off += TailLayout::stream_bytes(st[s].B);
+  }
+  __atomic_thread_fence(__ATOMIC_RELEASE);
+  return PFMPE_OK;
+}
+static_assert(sizeof(((pfmpe_ctx*)nullptr)->markers) + sizeof(((pfmpe_ctx*)nullptr)->K) <= kTailModelBytes, "tail model");
+
+// Stream s's tail record of frame sequence `want`, awaited like the frame record (wait_frame): a bounded spin on the
+// tags with the hipStreamQuery backstop.  Returns the record's state with row / cov unpacked for kTailRefined;
+// kTailNotReady also when the stream is idle (or in error) without a record.
+uint32_t tail_wait(pfmpe_ctx* c0, int S, int s, int32_t want, pfmpe_refine_row* row, double* cov) {
+  volatile const uint64_t* g = ((const TailRec*)(c0->h_tail.get() + TailLayout(S).rec_off) + s)->g;
+  auto take = [&](uint32_t* state) {
+    const uint32_t t = (uint32_t)(g[0] >> 32);
+    if (t == 0u || (int32_t)(t >> 2) != want) return false;
+    *state = t & 3u;
+    if (*state != kTailRefined) return true;
+    for (int k = kTailWords - 1; k > 0; --k)
+      if ((uint32_t)(g[k] >> 32) != t) return false;
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    uint32_t w[kTailWords];
+    for (int k = 0; k < kTailWords; ++k) w[k] = (uint32_t)g[k];
+    std::memcpy(row, w + 1, sizeof(*row));
+    std::memcpy(cov, w + 1 + kTailRowWords, 36 * sizeof(double));
+    return true;
+  };
+  uint32_t state = kTailNotReady;
+  int64_t next_query = 0;
+  for (uint64_t spin = 0;; ++spin) {
+    if (take(&state)) return state;
+    if ((spin & 63u) != 63u) {
+      __builtin_ia32_pause();
+      continue;
+    }
+    const int64_t t = now_ns();
+    if (next_query == 0) next_query = t + kQueryAfterNs;
+    if (t >= next_query) {
+      next_query = t + kQueryAfterNs;
+      if (hipStreamQuery(c0->stream) != hipErrorNotReady) return take(&state) ? state : (uint32_t)kTailNotReady;
+    }
+    __builtin_ia32_pause();
+  }
+}
+
+// One stream's results from its tail record; the recovery path (never an error of its own, never a retry) when the
+// record is "not ready" or absent: the host-driven refinement of the frame's winner, the same bytes.
+int tail_collect(pfmpe_ctx* c0, int S, int s, pfmpe_ctx* c, const TailStream& st, const pfmpe_frame_out* out,
+                 pfmpe_refine_out* gn, pfmpe_refine_row* row, double* cov36) {
+  pfmpe_refine_row r;
+  double cov[36];
+  const uint32_t state = tail_wait(c0, S, s, c->seq, &r, cov);
+  if (state == kTailRefined) {
+    tail_summary(r, cov, gn);
+    if (row) *row = r;
+    if (cov36) std::memcpy(cov36, cov, sizeof(cov));
+    return PFMPE_OK;
+  }
+  if (state == kTailEmpty) {
+    tail_empty(gn);
+    return PFMPE_OK;
+  }
+  c->tail_fallbacks += 1;
+  if (!tail_wanted(out->flag_fail, out->winner_pose)) {
+    tail_empty(gn);
+    return PFMPE_OK;
+  }
+  pfmpe_assoc_in ain{};
+  ain.blobs = st.blobs;
+  ain.B = st.B;
+  ain.bank_frame = -1;
+  return pfmpe_refine_poses(c, &ain, &st.prm, out->winner_pose, out->corr, 1, gn, row, cov36);
+}
+// the fused call in flight on c's stream, ended on every path
+struct TailScope {
+  pfmpe_ctx* c;
+  TailScope(pfmpe_ctx* c_, int S) : c(c_) {
+    c->tail_S = S;
+    c->tail_seq0 = c->seq;
+  }
+  ~TailScope() { c->tail_S = 0; }
+};
+}  // namespace
+
+int pfmpe_step_refine(pfmpe_ctx* c, const pfmpe_frame_in* in, const pfmpe_refine_params* params, pfmpe_frame_out* out,
+                      pfmpe_refine_out* gn, pfmpe_refine_row* row, double* cov36) {
+  RET(check_step(c, in, out));
+  std::vector<TailStream> st(1);
+  pfmpe_default_refine_params(&st[0].prm);
+  if (params) st[0].prm = *params;
+  if (!gn) return fail(c, PFMPE_E_ARG, "step_refine: null gn");
+  if (!refine_params_ok(st[0].prm)) return fail(c, PFMPE_E_ARG, "step_refine: bad parameters");
+  tail_blobs(c, in, &st[0]);
+  HIPCHK(c, hipSetDevice(c->device));
+  RET(tail_stage(c, st));
+  {
+    TailScope scope(c, 1);
+    RET(step_run(c, in, out));
+  }
+  return tail_collect(c, 1, 0, c, st[0], out, gn, row, cov36);
+}
+
+int pfmpe_step_refine_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* in, const pfmpe_refine_params* params,
+                            pfmpe_frame_out* out, pfmpe_refine_out* gn, pfmpe_refine_row* rows, double* cov) {
+  RET(step_multi_check(ctxs, S, in, out, "step_refine_multi"));
+  pfmpe_ctx* c0 = ctxs[0];
+  if (!gn) return fail(c0, PFMPE_E_ARG, "step_refine_multi: null gn");
+  std::vector<TailStream> st(S);
+  for (int s = 0; s < S; ++s) {
+    pfmpe_default_refine_params(&st[s].prm);
+    if (params) st[s].prm = params[s];
+    if (!refine_params_ok(st[s].prm))
+      return fail(c0, PFMPE_E_ARG, "step_refine_multi: stream " + std::to_string(s) + ": bad parameters");
+    tail_blobs(ctxs[s], &in[s], &st[s]);
+  }
+  HIPCHK(c0, hipSetDevice(c0->device));
+  RET(tail_stage(c0, st));
+  {
+    TailScope scope(c0, S);
+    RET(step_multi_run(ctxs, S, in, out));
+  }
+  for (int s = 0; s < S; ++s)
+    RET(tail_collect(c0, S, s, ctxs[s], st[s], &out[s], &gn[s], rows ? rows + s : nullptr,
+                     cov ? cov + 36 * (size_t)s : nullptr));
+  return PFMPE_OK;
+}
+
+int pfmpe_host_step_tail(const double* markers_xyz, int M, const double* K, const double* blobs, int B,
+                         const pfmpe_frame_out* frame, const pfmpe_refine_params* params, pfmpe_refine_out* gn,
+                         pfmpe_refine_row* row, double* cov36) {
+  pfmpe_refine_params prm;
+  pfmpe_default_refine_params(&prm);
+  if (params) prm = *params;
+  if (!markers_xyz || !K || !frame || !gn || M < 1 || M > kMaxMarkers || B < 0 || (B > 0 && !blobs)) return PFMPE_E_ARG;
+  if (!refine_params_ok(prm)) return PFMPE_E_ARG;
+  if (!tail_wanted(frame->flag_fail, frame->winner_pose)) {
+    tail_empty(gn);
+    return PFMPE_OK;
+  }
+  double model[kMaxMarkers * 3] = {0}, zb[2 * kMaxMarkers] = {0}, c36[36];
+  uint32_t lcorr[2 * kMaxMarkers];
+  std::memcpy(model, markers_xyz, (size_t)M * 3 * sizeof(double));
+  for (int j = 0; j < kMaxMarkers; ++j) {
+    if (!tail_pair(frame->corr, j, M, B, lcorr + 2 * j)) return PFMPE_E_ARG;
+    if (lcorr[2 * j + 1] != 0u) {
+      zb[2 * j] = blobs[2 * (size_t)(frame->corr[2 * j + 1] - 1u)];
+      zb[2 * j + 1] = blobs[2 * (size_t)(frame->corr[2 * j + 1] - 1u) + 1];
+    }
+  }
+  pfmpe_refine_row r;
+  tail_refine(model, K, zb, lcorr, prm.max_iter, prm.revert_on_divergence ? 1 : 0, prm.converged, frame->winner_pose, r,
+              c36);
+  tail_summary(r, c36, gn);
+  if (row) *row = r;
+  if (cov36) std::memcpy(cov36, c36, sizeof(c36));
+  return PFMPE_OK;
+}
+
 // Undocumented diagnostic: reset (out == NULL) or read the kStamps stamps of the last frame (diag & 4).
 int pfmpe_debug_stamps(pfmpe_ctx* c, uint64_t* out) {
   if (!c || !c->d_stamps) return PFMPE_E_STATE;
@@ -1288,6 +1537,7 @@ int pfmpe_get_info(const pfmpe_ctx* c, int key, int64_t* value) {
     case PFMPE_INFO_GUARD_SKIPS: *value = c->guard_skips; return PFMPE_OK;
     case PFMPE_INFO_N: *value = c->N; return PFMPE_OK;
     case PFMPE_INFO_NUM_CU: *value = c->num_cu; return PFMPE_OK;
+    case PFMPE_INFO_TAIL_FALLBACKS: *value = c->tail_fallbacks; return PFMPE_OK;
     case 110: case 111: case 112: case 113: *value = c->mt_ns[key - 110]; return PFMPE_OK;  // batch host timing
     case 114: *value = c->mt_batches; return PFMPE_OK;
     case 115: *value = live_blocks().load(); return PFMPE_OK;  // buffers alive in this process (any context)

@@ -1,7 +1,9 @@
 // pfmpe_refine.hip — k_refine / k_refine_fold (pfmpe_refine_poses / pfmpe_refine_cloud), k_refine_multi /
-// k_refine_fold_multi (pfmpe_refine_multi) and their launches: Gauss-Newton (pf_gn.hpp) of one hypothesis per lane,
-// fp64 for every state type, and the call's summary.  A TU of its own so it builds beside the others.
+// k_refine_fold_multi (pfmpe_refine_multi), k_step_tail (pfmpe_step_refine / pfmpe_step_refine_multi) and their
+// launches: Gauss-Newton (pf_gn.hpp) of one hypothesis per lane, fp64 for every state type, and the call's summary.
+// A TU of its own so it builds beside the others.
 #include "pf_gn.hpp"
+#include "pf_tail.hpp"
 #include "pf_wave.hpp"
 #include "pfmpe_ctx.hpp"
 #include "pfmpe_refine_plan.hpp"
@@ -214,7 +216,99 @@ __global__ __launch_bounds__(kWave) void k_refine_fold_multi(const RefineMultiAr
     else if (q < kRowWords + 36) out->best_cov[q - kRowWords] = 0.0;
   }
 }
+
+// ---- the step's tail (pfmpe_step_refine / pfmpe_step_refine_multi, pf_tail.hpp)
+typedef __attribute__((address_space(1))) uint64_t tail_gu64_t;
+__device__ __forceinline__ void tail_st_sys64(uint64_t* p, uint64_t v) {
+  __hip_atomic_store((tail_gu64_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ uint64_t tail_ld_sys64(const uint64_t* p) {
+  return __hip_atomic_load((tail_gu64_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One wave per stream, launched behind every launch that can finish a frame.  The wave takes its stream's frame
+// record where the finishing wave left it (the mapped pinned RecOut), and only if every granule carries this frame's
+// finished tag (sequence seq0 + delta) goes on: an unfinished iteration round, another frame's record (an orphaned
+// tail, a stream of a batch that finished in an earlier round) leave nothing.  The winner pose and the pair row come
+// out of the record, the fp64 model and the blobs the row names out of the staging block, all into LDS, once; then lane
+// 0 runs k_refine's gn_optimise on LDS alone and the wave publishes the row and the covariance as tagged granules.
+// No wait, no atomic read-modify-write, no loop but Gauss-Newton's own (max_iter <= 10000): stream order is the only
+// synchronisation.  miss: kDiagTailMiss, every finished frame is reported "not ready".
+__global__ __launch_bounds__(kWave) void k_step_tail(const TailDesc* __restrict__ desc,
+                                                     const unsigned char* __restrict__ block, const int32_t delta,
+                                                     const int32_t miss) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_rec[2 * kWave];  // the OutDev words
+  __shared__ double s_model[kMaxMarkers * 3 + 16];
+  __shared__ double s_zb[2 * kMaxMarkers];
+  __shared__ uint32_t s_corr[2 * kMaxMarkers];
+  __shared__ pfmpe_refine_row s_row;
+  __shared__ double s_cov[36];
+  static_assert(kRecWords <= 2 * kWave && kTailWords <= 2 * kWave, "two words per lane");
+  const int lane = threadIdx.x;
+  const TailDesc d = desc[blockIdx.x];
+  const int32_t seq = (d.seq0 + delta) & 0x3fffffff;
+  const uint32_t fin = ((uint32_t)seq << 1) | 1u;
+  const uint64_t g0 = tail_ld_sys64(d.rec + lane);
+  const uint64_t g1 = lane + kWave < kRecWords ? tail_ld_sys64(d.rec + lane + kWave) : ((uint64_t)fin << 32);
+  const uint32_t t0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(g0 >> 32));
+  if (t0 != fin) return;  // not this frame's, or unfinished
+  const bool stale = (uint32_t)(g0 >> 32) != fin || (uint32_t)(g1 >> 32) != fin;
+  const bool torn = __builtin_amdgcn_ballot_w64(stale) != 0ull;
+  s_rec[lane] = (uint32_t)g0;
+  s_rec[lane + kWave] = (uint32_t)g1;
+  wave_lds_sync();
+  const OutDev& rec = *(const OutDev*)s_rec;
+  uint32_t state = kTailRefined;
+  if (torn || miss) {
+    state = kTailNotReady;
+  } else if (!tail_wanted(rec.flag_fail, rec.winner_pose)) {
+    state = kTailEmpty;
+  } else {
+    // the model (a double per lane) and the blobs the pair row names (a row per lane), straight into LDS
+    const double* model = (const double*)(block + d.model_off);
+    const double* blobs = (const double*)(block + d.blobs_off);
+    if (lane < kMaxMarkers * 3 + 9) s_model[lane] = model[lane];
+    bool bad = false;
+    if (lane < kMaxMarkers) {
+      uint32_t lrow[2];
+      bad = !tail_pair(rec.corr, lane, d.M, d.B, lrow);
+      const bool used = !bad && lrow[1] != 0u;
+      const size_t b = used ? (size_t)(rec.corr[2 * lane + 1] - 1u) : 0;
+      s_zb[2 * lane] = used ? blobs[2 * b] : 0.0;
+      s_zb[2 * lane + 1] = used ? blobs[2 * b + 1] : 0.0;
+      s_corr[2 * lane] = lrow[0];
+      s_corr[2 * lane + 1] = lrow[1];
+    }
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull) state = kTailNotReady;  // (the host path reports the index)
+  }
+  wave_lds_sync();
+  const uint64_t th = (uint64_t)tail_tag(seq, state) << 32;
+  if (state != kTailRefined) {
+    if (lane == 0) tail_st_sys64(d.out, th | state);
+    return;
+  }
+  if (lane == 0) {
+    pfmpe_refine_row r;
+    tail_refine(s_model, s_model + kMaxMarkers * 3, s_zb, s_corr, d.max_iter, d.revert, d.converged, rec.winner_pose, r,
+                s_cov);
+    s_row = r;
+  }
+  wave_lds_sync();
+  // word k of the record: the state, the row's words, the covariance's
+  const uint32_t* rw = (const uint32_t*)&s_row;
+  const uint32_t* cw = (const uint32_t*)s_cov;
+  const int k1 = lane + kWave;
+  tail_st_sys64(d.out + lane, th | (lane == 0 ? state : (lane <= kTailRowWords ? rw[lane - 1] : cw[lane - 1 - kTailRowWords])));
+  if (k1 < kTailWords) tail_st_sys64(d.out + k1, th | cw[k1 - 1 - kTailRowWords]);
+}
 }  // namespace
+
+int tail_launch(pfmpe_ctx* c, int32_t delta) {
+  return launch_ext(c, PFMPE_K_AUX, [&] {
+    klaunch(c, k_step_tail, dim3((unsigned)c->tail_S), dim3(kWave), 0, (const TailDesc*)c->h_tail.dev(),
+            (const unsigned char*)c->h_tail.dev(), delta, (c->diag & kDiagTailMiss) ? 1 : 0);
+  });
+}
 
 int refine_multi_launch(pfmpe_ctx* c0, const RefineMultiArgs& ma, int S) {
   const int nblk = (ma.H + kBlock - 1) / kBlock;

@@ -236,6 +236,7 @@ struct Seq {
                 c->d_ctrl.get(), table, prior, c->d_cpart.get(), c->d_cand.get(), c->d_mlpose.get(), c->h_rec.dev(), seq, c->d_stamps.get(), kept ? 1 : 0,
                 c->d_winkey.get());
       }));
+    RET(tail_after(c));
     if (const int rc = wait_frame(c); rc != PFMPE_OK) {
       const std::string err = c->err;
       (void)reset_handoffs(c, c->stream);
@@ -296,6 +297,7 @@ struct Seq {
                            n.tcount_w, n.gcount_r, n.tcount_r, c->d_gen.get(), counts, c->d_cand.get(), c->d_mlpose.get(), c->h_rec.dev(), seq,
                            c->d_stamps.get(), tree_count ? nullptr : c->d_flat.get());
     }));
+    RET(tail_after(c));
     *launched = true;
     if (wait_frame(c) != PFMPE_OK) {
       RET(abandoned(c));
@@ -583,6 +585,7 @@ struct Seq {
           klaunch(c0, k_resample_final_multi<T, RNG, MAXM, SP>, dim3((unsigned)na), dim3(kFinalBlock), lds_f, dd,
                   (const uint32_t*)dstat, gen);
         }));
+      if (c0->tail_S) RET(tail_launch(c0, round + 1));  // a stream active in this round was active in every earlier one
       const int64_t t_l1 = now_ns();
       c0->mt_ns[1] += t_l1 - t_l0;
       std::vector<int> next;
