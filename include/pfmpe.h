@@ -508,6 +508,38 @@ typedef struct {
 } pfmpe_cloud_out;
 int pfmpe_cloud_stats(pfmpe_ctx* ctx, int which, const double* ref_pose12, pfmpe_cloud_out* out);
 
+#define PFMPE_CLOUD_MAX_STREAMS 64
+
+/* The single call above for S entries (the statistics of every object of a frame, pose_covariance_Vec[objectNumber]
+ * of the numUAV loop, PE:89) as one launch sequence with one synchronise.  out[s] is byte for byte what
+ * pfmpe_cloud_stats(ctxs[s], in[s].which, in[s].ref_pose, &out[s]) writes, the degenerate record of an entry whose
+ * weights are all zero included.  `which` and the reference pose are per entry; N, the prior's storage (particle
+ * order or owner indices, fp16 anchor) and the kept iteration are the context's.  A context may appear in several
+ * entries (both sets of one object, or two reference poses); a context with at least one WEIGHTED entry regenerates
+ * its kept propagated set once, and all its entries read that set.  Contexts: on one device, of one state type.
+ * Runs on ctxs[0]'s stream and uses scratch ctxs[0] owns; work a member has pending elsewhere (its regeneration, on
+ * its own stream, included) is ordered before the batch; blocking.  Reads only: no context's state changes.  Not timed
+ * by PFMPE_OPT_TIMING, as the single call is not (a member's regeneration counts as aux on that member).  DESIGN.md
+ * §4.11a: design and measured times.
+ * Everything is checked before anything is staged, regenerated or launched, and out is untouched on an error:
+ * PFMPE_E_ARG (S < 1, NULL ctxs / in / out / ctxs[s], a device or state-type mismatch, a bad `which`, a non-finite
+ * reference pose), PFMPE_E_CAP (S > PFMPE_CLOUD_MAX_STREAMS), PFMPE_E_STATE (an entry whose context has no particle
+ * set, or a WEIGHTED entry before that context's first step); the text, "cloud_stats_multi: stream <s>: ...", is the
+ * last-error text of ctxs[0].  With ctxs == NULL or ctxs[0] == NULL: PFMPE_E_ARG and no text. */
+typedef struct {
+  double ref_pose[12];   /* T_ref of this entry */
+  int32_t which;         /* PFMPE_CLOUD_WEIGHTED / PFMPE_CLOUD_POSTERIOR */
+  int32_t pad;
+} pfmpe_cloud_in;        /* 104 bytes */
+int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out);
+
+/* host-only (no GPU, no context): the grid a pfmpe_cloud_stats_multi batch launches for entries of N[s] particles.
+ * Entry s gets blocks = min(ceil(N[s] / 256), 1024), the single call's grid, so its sums have the single call's
+ * order; first_block is the running sum of blocks and *total_blocks the flat grid's size.  PFMPE_E_ARG for a NULL
+ * pointer, S < 1 or an N < 1; PFMPE_E_CAP for S > PFMPE_CLOUD_MAX_STREAMS; the outputs are untouched then. */
+typedef struct { int32_t first_block, blocks; } pfmpe_cloud_plan;   /* 8 bytes */
+int pfmpe_host_cloud_plan(const int32_t* N, int S, pfmpe_cloud_plan* plan, int32_t* total_blocks);
+
 /* ------------------------------------------------------------- LED-blob association of the particle cloud */
 /* The reference keeps the correspondences of every particle (correspondencesVec, PE:2385-2445, read at PE:688); a
  * step reports the winner's only (pfmpe_frame_out.corr).  These calls derive every particle's pairs on the device

@@ -24,6 +24,7 @@ from ._capi import (  # noqa: F401
     REFINE_MAX_STREAMS, REFINE_MULTI_MAX_HYPOTHESES, REFINE_DESC_BYTES, RefineIn, RefinePlan, RefinePlanTotal,
     host_refine_plan,
     DIAG_TAIL_MISS, INFO_TAIL_FALLBACKS, host_step_tail,
+    CLOUD_MAX_STREAMS, CloudIn, CloudPlan, host_cloud_plan,
 )
 
 __all__ = [

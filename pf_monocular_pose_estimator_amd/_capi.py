@@ -60,12 +60,14 @@ EXPORTED_SYMBOLS = (
     "pfmpe_initialise_multi", "pfmpe_host_init_plan",
     "pfmpe_refine_multi", "pfmpe_host_refine_plan",
     "pfmpe_step_refine", "pfmpe_step_refine_multi", "pfmpe_host_step_tail",
+    "pfmpe_cloud_stats_multi", "pfmpe_host_cloud_plan",
 )
 DETECT_MAX_ROIS = 64
 DETECT_MAX_IMAGES = 64
 ROI_MAX_STREAMS = 64
 INIT_MAX_STREAMS = 64
 REFINE_MAX_STREAMS = 64
+CLOUD_MAX_STREAMS = 64
 REFINE_MULTI_MAX_HYPOTHESES = 65536
 REFINE_DESC_BYTES = 48
 
@@ -196,6 +198,17 @@ class CloudOut(C.Structure):
                 "mean_pose": np.array(self.mean_pose), "max_trans": self.max_trans, "max_rot": self.max_rot}
 
 
+class CloudIn(C.Structure):
+    _fields_ = [("ref_pose", C.c_double * 12), ("which", C.c_int32), ("pad", C.c_int32)]
+
+
+class CloudPlan(C.Structure):
+    _fields_ = [("first_block", C.c_int32), ("blocks", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"first_block": self.first_block, "blocks": self.blocks}
+
+
 class AssocIn(C.Structure):
     _fields_ = [("blobs", C.POINTER(C.c_double)), ("B", C.c_int32), ("bank_frame", C.c_int32)]
 
@@ -305,6 +318,8 @@ def load() -> C.CDLL:
         "pfmpe_host_philox": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "pfmpe_host_pose_twist": (None, [dp, dp, dp]),
         "pfmpe_cloud_stats": (I, [P, I, dp, C.POINTER(CloudOut)]),
+        "pfmpe_cloud_stats_multi": (I, [C.POINTER(P), I, C.POINTER(CloudIn), C.POINTER(CloudOut)]),
+        "pfmpe_host_cloud_plan": (I, [C.POINTER(C.c_int32), I, C.POINTER(CloudPlan), C.POINTER(C.c_int32)]),
         "pfmpe_assoc_stats": (I, [P, I, C.POINTER(AssocIn), C.POINTER(AssocOut), C.POINTER(C.c_uint32)]),
         "pfmpe_get_pairs": (I, [P, I, C.POINTER(AssocIn), C.c_int64, C.c_int32, C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_int32)]),
@@ -816,6 +831,31 @@ class Engine:
         return out.as_dict()
 
     @staticmethod
+    def make_cloud_in(which: int, ref) -> CloudIn:
+        """A CloudIn from the arguments of cloud_stats (ref: 12 values, 3x4 or 4x4; no default)."""
+        r = np.asarray(ref, dtype=np.float64).reshape(-1)[:12]
+        if r.size != 12:
+            raise ValueError("cloud_stats_multi: ref must hold 12 values (3x4) or a 4x4")
+        ci = CloudIn()
+        ci.ref_pose[:] = r.tolist()
+        ci.which = int(which)
+        return ci
+
+    @staticmethod
+    def cloud_stats_multi(engines, whichs, refs) -> list:
+        """The cloud statistics of S entries as ONE batch on the device (pfmpe_cloud_stats_multi): entry s is
+        cloud_stats(whichs[s], refs[s]) of engines[s] (an engine may appear several times: both sets of one object, or
+        two reference poses); returns one dict per entry, each what cloud_stats returns."""
+        S = len(engines)
+        if S == 0 or S != len(whichs) or S != len(refs):
+            raise ValueError("cloud_stats_multi: one which and one ref per engine")
+        ctxs = (C.c_void_p * S)(*[e.ctx.value for e in engines])
+        arr_in = (CloudIn * S)(*[Engine.make_cloud_in(w, r) for w, r in zip(whichs, refs)])
+        arr_out = (CloudOut * S)()
+        engines[0]._chk(engines[0].lib.pfmpe_cloud_stats_multi(ctxs, S, arr_in, arr_out))
+        return [o.as_dict() for o in arr_out]
+
+    @staticmethod
     def _assoc_in(blobs, bank_frame):
         ai = AssocIn()
         keep = None
@@ -1235,6 +1275,19 @@ def host_init_plan(M, B, num_cu: int) -> tuple:
     if rc != OK:
         raise PFError(rc, "pfmpe_host_init_plan")
     return [plan[s].as_dict() for s in range(S)], list(per_bucket)
+
+
+def host_cloud_plan(Ns) -> tuple:
+    """pfmpe_host_cloud_plan: the grid of a cloud_stats_multi batch whose entries hold Ns[s] particles.  Returns (one
+    dict per entry: first_block, blocks; the flat grid's size)."""
+    n = np.ascontiguousarray(Ns, dtype=np.int32).reshape(-1)
+    S = int(n.shape[0])
+    plan = (CloudPlan * max(S, 1))()
+    total = C.c_int32(0)
+    rc = load().pfmpe_host_cloud_plan(n.ctypes.data_as(C.POINTER(C.c_int32)), S, plan, C.byref(total))
+    if rc != OK:
+        raise PFError(rc, "pfmpe_host_cloud_plan")
+    return [plan[s].as_dict() for s in range(S)], int(total.value)
 
 
 def host_refine_plan(K, B) -> tuple:

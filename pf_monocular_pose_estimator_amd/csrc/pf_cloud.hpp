@@ -1,6 +1,7 @@
 // pf_cloud.hpp — read-backs of the cloud: the weights (pfmpe_get_weights) and the cloud statistics
-// (pfmpe_cloud_stats).
+// (pfmpe_cloud_stats, pfmpe_cloud_stats_multi).
 #pragma once
+#include "pf_roi.hpp"  // roi_stream_of_block, k_roi_stage (the batch)
 #include "pf_state.hpp"
 #include "pf_wave.hpp"
 
@@ -175,6 +176,128 @@ __global__ __launch_bounds__(kCloudSegs* kCloudWords) void k_cloud_final(const V
   if (sg == 0) {
     for (int s = 1; s < kCloudSegs; ++s) v = sum ? v + sh[s][q] : (sh[s][q] > v ? sh[s][q] : v);
     out[q] = v;
+  }
+}
+
+// ---- the cloud statistics of S entries in one batch (pfmpe_cloud_stats_multi).  One flat grid, as k_roi_multi's:
+// entry s owns the blocks first[s] .. first[s + 1], the cloud_blocks(N_s) blocks of its single call, and a block
+// finds its entry with roi_stream_of_block (wave-uniform: the descriptor is read with scalar loads).  Inside its
+// entry a block is block lb of nb: it starts at particle lb * kBlock and strides by nb * kBlock, the single call's
+// gridDim.x * kBlock, so every lane sums the particles the single call's lane sums, in that order; the wave and
+// block reductions and the tree over the partial rows are the single call's too, and so are the bits.
+// (k_cloud_partials and k_cloud_final keep their own text: the single call is the timing baseline of the batch.)
+constexpr int kCloudMaxStreams = 64;
+static_assert(kCloudMaxStreams <= kRoiMaxStreams, "CloudBatch::first is read by roi_stream_of_block");
+struct CloudBatch {  // head of the batch's device image, the descriptors follow
+  int32_t S, pad;
+  int32_t first[kCloudMaxStreams + 1];  // first block of entry s; first[S] = all blocks
+  int32_t pad2;
+};
+struct CloudDesc {
+  CloudArgs a;
+  const void* st;  // resident: the prior's storage (SP planes); dense: unused
+  int32_t dense, pad;
+};
+static_assert(sizeof(CloudBatch) % sizeof(uint64_t) == 0 && sizeof(CloudDesc) % sizeof(uint64_t) == 0,
+              "k_roi_stage copies 8-byte words");
+template <typename T, typename SP>
+__global__ __launch_bounds__(kBlock) void k_cloud_multi(const CloudBatch* __restrict__ hd,
+                                                       const CloudDesc* __restrict__ descs,
+                                                       double* __restrict__ part) {
+  __shared__ double sh[kWaves][kCloudWords];
+  const int s = roi_stream_of_block(hd->first, hd->S, blockIdx.x);
+  const CloudDesc& d = descs[s];
+  const CloudArgs& ca = d.a;
+  const int b0 = hd->first[s];
+  const int lb = (int)blockIdx.x - b0, nb = hd->first[s + 1] - b0;
+  const bool dense = d.dense != 0;  // wave-uniform
+  const SP* __restrict__ st = (const SP*)d.st;
+  double acc[kCloudSums];
+#pragma unroll
+  for (int q = 0; q < kCloudSums; ++q) acc[q] = 0.0;
+  double mt = 0.0, mr = 0.0;
+  const int64_t stride = (int64_t)nb * kBlock;  // the entry's own grid, not gridDim.x
+  for (int64_t n = (int64_t)lb * kBlock + threadIdx.x; n < ca.N; n += stride) {
+    double P[12], w = 1.0;
+    if (dense) {
+#pragma unroll
+      for (int q = 0; q < 12; ++q) P[q] = ca.dense[12 * n + q];
+      w = (double)((const T*)ca.w)[n];
+    } else {
+      const int64_t r = ca.owner ? (int64_t)ca.owner[n] : n;
+#pragma unroll
+      for (int q = 0; q < 12; ++q)
+        P[q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ca.ld)], (T)ca.anchor[q]);
+    }
+    double xi[6], wx[6];
+    pose_twist(P, ca.ref, xi);
+    acc[0] = acc[0] + w;
+    acc[1] = acc[1] + w * w;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      wx[q] = w * xi[q];
+      acc[2 + q] = acc[2 + q] + wx[q];
+    }
+    int k = 8;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j, ++k) acc[k] = acc[k] + wx[i] * xi[j];
+    const double t2 = (xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2];
+    const double r2 = (xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5];
+    mt = (w > 0.0 && t2 > mt) ? t2 : mt;
+    mr = (w > 0.0 && r2 > mr) ? r2 : mr;
+  }
+#pragma unroll
+  for (int q = 0; q < kCloudSums; ++q) acc[q] = lane_value(wave_incl_sum(acc[q]), 63);
+  mt = wave_max(mt);
+  mr = wave_max(mr);
+  const int wv = wave_id();
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int q = 0; q < kCloudSums; ++q) sh[wv][q] = acc[q];
+    sh[wv][kCloudSums] = mt;
+    sh[wv][kCloudSums + 1] = mr;
+    sh[wv][kCloudSums + 2] = 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x < kCloudWords) {
+    const int q = threadIdx.x;
+    double v = sh[0][q];
+    for (int x = 1; x < kWaves; ++x) v = q < kCloudSums ? v + sh[x][q] : (sh[x][q] > v ? sh[x][q] : v);
+    part[(size_t)blockIdx.x * kCloudWords + q] = v;  // row first[s] + lb
+  }
+}
+// one block per entry: its partial rows through k_cloud_final's tree (the runs are cut on the entry's own block
+// count) -> the kCloudWords words of entry s of `out` (pinned, host-mapped: no copy back)
+__global__ __launch_bounds__(kCloudSegs* kCloudWords) void k_cloud_multi_final(const CloudBatch* __restrict__ hd,
+                                                                              const double* __restrict__ part,
+                                                                              double* __restrict__ out) {
+  __shared__ double sh[kCloudSegs][kCloudWords];
+  const int e = blockIdx.x, r0 = hd->first[e], nblk = hd->first[e + 1] - r0;
+  part += (size_t)r0 * kCloudWords;
+  const int q = threadIdx.x % kCloudWords, sg = threadIdx.x / kCloudWords;
+  const int per = (nblk + kCloudSegs - 1) / kCloudSegs;
+  const int b0 = sg * per, b1 = b0 + per < nblk ? b0 + per : nblk;
+  const bool sum = q < kCloudSums;
+  double v = 0;
+  int b = b0;
+  for (; b + 16 <= b1; b += 16) {
+    double x[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x[i] = part[(size_t)(b + i) * kCloudWords + q];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v = sum ? v + x[i] : (x[i] > v ? x[i] : v);
+  }
+  for (; b < b1; ++b) {
+    const double x = part[(size_t)b * kCloudWords + q];
+    v = sum ? v + x : (x > v ? x : v);
+  }
+  sh[sg][q] = v;
+  __syncthreads();
+  if (sg == 0) {
+    for (int s = 1; s < kCloudSegs; ++s) v = sum ? v + sh[s][q] : (sh[s][q] > v ? sh[s][q] : v);
+    out[(size_t)e * kCloudWords + q] = v;
   }
 }
 

@@ -206,6 +206,11 @@ struct pfmpe_ctx : CtxQueue {
   // followed by the result boxes of PFMPE_ROI_MAX_STREAMS streams
   Buf<unsigned char> d_roim;
   Buf<unsigned char, Mem::Mapped> h_roim;
+  // pfmpe_cloud_stats_multi (owned by the batch's first context): the batch scratch (head + descriptors, then one
+  // partial row per block of the batch; grown on demand, never shrunk), and the pinned, host-mapped image of the
+  // head + descriptors followed by the result rows of PFMPE_CLOUD_MAX_STREAMS entries
+  Buf<unsigned char> d_cloudm;
+  Buf<unsigned char, Mem::Mapped> h_cloudm;
   int num_cu = 0;
   bool coop = false;               // device supports cooperative launches
   int fused = 2;                   // PFMPE_OPT_FUSED: 2 flat one-launch (k_frame2), 1 tree (k_frame), 0 two launches

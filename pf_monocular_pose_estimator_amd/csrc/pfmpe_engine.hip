@@ -783,61 +783,32 @@ void host_exp_map(const double* xi, double* pose) {
     pose[i * 4 + 3] = V[i * 3] * u[0] + V[i * 3 + 1] * u[1] + V[i * 3 + 2] * u[2];
   }
 }
-}  // namespace
-
-int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_out* out) {
-  if (!c) return PFMPE_E_ARG;
-  if (!ref || !out || (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR))
-    return fail(c, PFMPE_E_ARG, "cloud_stats: bad arguments");
-  for (int q = 0; q < 12; ++q)
-    if (!std::isfinite(ref[q])) return fail(c, PFMPE_E_ARG, "cloud_stats: non-finite reference pose");
-  if (!c->has_prior) return fail(c, PFMPE_E_STATE, "cloud_stats: no particle set");
-  if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_stats(weighted): no step yet");
-  RET(set_device(c));
-  // scratch of the call's own (nothing a frame reads): the result row, then one partial row per block
-  RET(c->d_cloud.ensure(c, ((size_t)kCloudMaxBlocks + 1) * kCloudWords * sizeof(double)));
-  const int N = c->N;
-  const int nblk = cloud_blocks(N);
+// the kernel arguments of one statistics request on context c: its kept propagated set regenerated into d_xfer with
+// the kept iteration's raw weights (WEIGHTED), or its current prior (POSTERIOR)
+CloudArgs cloud_args(const pfmpe_ctx* c, int which, const double* ref) {
   CloudArgs ca{};
   std::memcpy(ca.ref, ref, sizeof(ca.ref));
-  ca.N = N;
-  double* part = c->d_cloud.get() + kCloudWords;
+  ca.N = c->N;
   if (which == PFMPE_CLOUD_WEIGHTED) {
-    // the kept propagated set as get_particles(0) delivers it (d_xfer is written and read inside one blocking call
-    // by every user), weighted by the kept iteration's raw weights
-    RET(ensure_xfer(c));
-    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()));
     ca.dense = c->d_xfer.get();
     ca.w = c->d_w[c->last_kept_slot].get();
-    visit_state(c, [&](auto s) {  // the dense set is in the compute type
-      using T = typename decltype(s)::T;
-      hipLaunchKernelGGL((k_cloud_partials<T, T, true>), dim3(nblk), dim3(kBlock), 0, c->stream, ca, (const T*)nullptr,
-                         part);
-    });
   } else {
     std::memcpy(ca.anchor, c->anchor[c->prior_idx], sizeof(ca.anchor));
     ca.ld = c->ld;
     ca.owner = prior_owner_ptr(c);
-    visit_state(c, [&](auto s) {
-      using SP = typename decltype(s)::SP;
-      hipLaunchKernelGGL((k_cloud_partials<typename decltype(s)::T, SP, false>), dim3(nblk), dim3(kBlock), 0, c->stream,
-                         ca, (const SP*)c->d_state[c->prior_idx].get(), part);
-    });
   }
-  hipLaunchKernelGGL((k_cloud_final<double>), dim3(1), dim3(kCloudSegs * kCloudWords), 0, c->stream, part, nblk, c->d_cloud.get());
-  HIPCHK(c, hipGetLastError());
-  double r[kCloudWords];
-  HIPCHK(c, hipMemcpyAsync(r, c->d_cloud.get(), sizeof(r), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  RET(harvest_timing(c));  // (a weighted call's regeneration is bracketed like get_particles(0)'s)
-
+  return ca;
+}
+// the kCloudWords reduced words r of a set of N particles about ref -> pfmpe_cloud_out (pfmpe_cloud_stats and every
+// entry of pfmpe_cloud_stats_multi)
+void cloud_epilogue(const double* r, int N, const double* ref, pfmpe_cloud_out* out) {
   std::memset(out, 0, sizeof(*out));
   out->n = N;
   out->wsum = r[0];
   if (!(r[0] > 0.0)) {  // all weights zero (the re-initialisation branch): no mean to speak of
     out->degenerate = 1;
     std::memcpy(out->mean_pose, ref, sizeof(out->mean_pose));
-    return PFMPE_OK;
+    return;
   }
   const double W = r[0];
   out->ess = W * W / r[1];
@@ -859,9 +830,170 @@ int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_ou
       out->mean_pose[i * 4 + j] = E[i * 4] * ref[j] + E[i * 4 + 1] * ref[4 + j] + E[i * 4 + 2] * ref[8 + j];
     out->mean_pose[i * 4 + 3] = E[i * 4] * ref[3] + E[i * 4 + 1] * ref[7] + E[i * 4 + 2] * ref[11] + E[i * 4 + 3];
   }
+}
+}  // namespace
+
+int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_out* out) {
+  if (!c) return PFMPE_E_ARG;
+  if (!ref || !out || (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR))
+    return fail(c, PFMPE_E_ARG, "cloud_stats: bad arguments");
+  for (int q = 0; q < 12; ++q)
+    if (!std::isfinite(ref[q])) return fail(c, PFMPE_E_ARG, "cloud_stats: non-finite reference pose");
+  if (!c->has_prior) return fail(c, PFMPE_E_STATE, "cloud_stats: no particle set");
+  if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_stats(weighted): no step yet");
+  RET(set_device(c));
+  // scratch of the call's own (nothing a frame reads): the result row, then one partial row per block
+  RET(c->d_cloud.ensure(c, ((size_t)kCloudMaxBlocks + 1) * kCloudWords * sizeof(double)));
+  const int N = c->N;
+  const int nblk = cloud_blocks(N);
+  double* part = c->d_cloud.get() + kCloudWords;
+  if (which == PFMPE_CLOUD_WEIGHTED) {
+    // the kept propagated set as get_particles(0) delivers it (d_xfer is written and read inside one blocking call
+    // by every user), weighted by the kept iteration's raw weights
+    RET(ensure_xfer(c));
+    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()));
+    const CloudArgs ca = cloud_args(c, which, ref);
+    visit_state(c, [&](auto s) {  // the dense set is in the compute type
+      using T = typename decltype(s)::T;
+      hipLaunchKernelGGL((k_cloud_partials<T, T, true>), dim3(nblk), dim3(kBlock), 0, c->stream, ca, (const T*)nullptr,
+                         part);
+    });
+  } else {
+    const CloudArgs ca = cloud_args(c, which, ref);
+    visit_state(c, [&](auto s) {
+      using SP = typename decltype(s)::SP;
+      hipLaunchKernelGGL((k_cloud_partials<typename decltype(s)::T, SP, false>), dim3(nblk), dim3(kBlock), 0, c->stream,
+                         ca, (const SP*)c->d_state[c->prior_idx].get(), part);
+    });
+  }
+  hipLaunchKernelGGL((k_cloud_final<double>), dim3(1), dim3(kCloudSegs * kCloudWords), 0, c->stream, part, nblk, c->d_cloud.get());
+  HIPCHK(c, hipGetLastError());
+  double r[kCloudWords];
+  HIPCHK(c, hipMemcpyAsync(r, c->d_cloud.get(), sizeof(r), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  RET(harvest_timing(c));  // (a weighted call's regeneration is bracketed like get_particles(0)'s)
+  cloud_epilogue(r, N, ref, out);
   return PFMPE_OK;
 }
 
+int pfmpe_host_cloud_plan(const int32_t* N, int S, pfmpe_cloud_plan* plan, int32_t* total_blocks) {
+  if (!N || !plan || !total_blocks || S < 1) return PFMPE_E_ARG;
+  if (S > PFMPE_CLOUD_MAX_STREAMS) return PFMPE_E_CAP;
+  for (int s = 0; s < S; ++s)
+    if (N[s] < 1) return PFMPE_E_ARG;
+  int32_t nb = 0;  // at most 64 x 1024
+  for (int s = 0; s < S; ++s) {
+    plan[s].first_block = nb;
+    // (cloud_blocks rounds N up in int: any N, not a context's only, comes through here)
+    plan[s].blocks = N[s] >= kCloudMaxBlocks * kBlock ? kCloudMaxBlocks : cloud_blocks(N[s]);
+    nb += plan[s].blocks;
+  }
+  *total_blocks = nb;
+  return PFMPE_OK;
+}
+
+int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out) {
+  static_assert(PFMPE_CLOUD_MAX_STREAMS == kCloudMaxStreams, "stream capacity mismatch");
+  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+  pfmpe_ctx* c0 = ctxs[0];
+  if (!in || !out) return fail(c0, PFMPE_E_ARG, "cloud_stats_multi: null in/out");
+  if (S > PFMPE_CLOUD_MAX_STREAMS)
+    return fail(c0, PFMPE_E_CAP, "cloud_stats_multi: S exceeds PFMPE_CLOUD_MAX_STREAMS");
+  // the distinct contexts in order of first appearance (ctxs[0] first), and which of them have a WEIGHTED entry
+  std::vector<pfmpe_ctx*> distinct;
+  std::vector<char> weighted;
+  int32_t Ns[PFMPE_CLOUD_MAX_STREAMS];
+  for (int s = 0; s < S; ++s) {
+    pfmpe_ctx* c = ctxs[s];
+    const std::string at = "cloud_stats_multi: stream " + std::to_string(s) + ": ";
+    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
+    if (c->device != c0->device || c->state_dtype != c0->state_dtype)
+      return fail(c0, PFMPE_E_ARG, at + "device and state type must match ctxs[0]");
+    const int which = in[s].which;
+    if (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR) return fail(c0, PFMPE_E_ARG, at + "bad which");
+    for (int q = 0; q < 12; ++q)
+      if (!std::isfinite(in[s].ref_pose[q])) return fail(c0, PFMPE_E_ARG, at + "non-finite reference pose");
+    if (!c->has_prior) return fail(c0, PFMPE_E_STATE, at + "no particle set");
+    if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c0, PFMPE_E_STATE, at + "weighted: no step yet");
+    size_t m = 0;
+    while (m < distinct.size() && distinct[m] != c) ++m;
+    if (m == distinct.size()) {
+      distinct.push_back(c);
+      weighted.push_back(0);
+    }
+    if (which == PFMPE_CLOUD_WEIGHTED) weighted[m] = 1;
+    Ns[s] = c->N;
+  }
+  pfmpe_cloud_plan plan[PFMPE_CLOUD_MAX_STREAMS];
+  int32_t total = 0;
+  if (pfmpe_host_cloud_plan(Ns, S, plan, &total) != PFMPE_OK)
+    return fail(c0, PFMPE_E_STATE, "cloud_stats_multi: a context without particles");
+  RET(set_device(c0));
+  // the scratch before any member's ordering state changes: pinned image (head, descriptors, result rows) once,
+  // device image + partial rows grown on demand (nothing of an earlier batch is pending: the call is blocking)
+  constexpr size_t kDescOff = (sizeof(CloudBatch) + 255) / 256 * 256;
+  constexpr size_t kRowOff = (kDescOff + kCloudMaxStreams * sizeof(CloudDesc) + 255) / 256 * 256;
+  constexpr size_t kRowBytes = kCloudWords * sizeof(double);
+  RET(c0->h_cloudm.ensure(c0, kRowOff + kCloudMaxStreams * kRowBytes));
+  const size_t need = kRowOff + (size_t)total * kRowBytes;
+  RET(c0->d_cloudm.grow(c0, need, kRowOff + (need - kRowOff) * 2));
+  for (size_t m = 0; m < distinct.size(); ++m)
+    if (weighted[m]) RET(ensure_xfer(distinct[m]));
+  // each WEIGHTED context's kept propagated set once, as its single call regenerates it: into its own d_xfer, on its
+  // own stream (set_device: after whatever it has pending elsewhere); all its entries read that set
+  for (size_t m = 0; m < distinct.size(); ++m) {
+    pfmpe_ctx* c = distinct[m];
+    if (!weighted[m]) continue;
+    if (c != c0) RET(set_device(c));
+    if (const int r_ = dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()))
+      return c == c0 ? r_ : fail(c0, r_, "cloud_stats_multi: " + c->err);
+  }
+  // every member's work so far, that regeneration included, is ordered before the batch (a context that appears
+  // twice once); a failure from here on gives the members their ordering state back (the leader's own was set by
+  // set_device)
+  OrderGuard members(distinct.data(), (int)distinct.size());
+  RET(members.order(1, c0->stream, c0));
+  unsigned char* hd_img = c0->h_cloudm.dev();
+  CloudBatch* hd = (CloudBatch*)c0->h_cloudm.get();
+  CloudDesc* descs = (CloudDesc*)(c0->h_cloudm.get() + kDescOff);
+  std::memset(hd, 0, sizeof(*hd));
+  hd->S = S;
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = ctxs[s];
+    CloudDesc& d = descs[s];
+    d.a = cloud_args(c, in[s].which, in[s].ref_pose);
+    d.dense = in[s].which == PFMPE_CLOUD_WEIGHTED;
+    d.pad = 0;
+    d.st = d.dense ? nullptr : c->d_state[c->prior_idx].get();
+    hd->first[s] = plan[s].first_block;
+  }
+  hd->first[S] = total;
+  const int stage_words = (int)((kDescOff + (size_t)S * sizeof(CloudDesc)) / sizeof(uint64_t));
+  const CloudBatch* dhd = (const CloudBatch*)c0->d_cloudm.get();
+  const CloudDesc* ddescs = (const CloudDesc*)(c0->d_cloudm.get() + kDescOff);
+  double* part = (double*)(c0->d_cloudm.get() + kRowOff);
+  const double* hrow = (const double*)(c0->h_cloudm.get() + kRowOff);
+  hipLaunchKernelGGL((k_roi_stage<uint64_t>), dim3(1), dim3(kBlock), 0, c0->stream, (const uint64_t*)hd_img,
+                     (uint64_t*)c0->d_cloudm.get(), stage_words);
+  visit_state(c0, [&](auto s) {
+    hipLaunchKernelGGL((k_cloud_multi<typename decltype(s)::T, typename decltype(s)::SP>), dim3(total), dim3(kBlock), 0,
+                       c0->stream, dhd, ddescs, part);
+  });
+  hipLaunchKernelGGL(k_cloud_multi_final, dim3(S), dim3(kCloudSegs * kCloudWords), 0, c0->stream, dhd,
+                     (const double*)part, (double*)(hd_img + kRowOff));
+  HIPCHK(c0, hipGetLastError());
+  if (hipStreamSynchronize(c0->stream) != hipSuccess)
+    return fail(c0, PFMPE_E_HIP, "cloud_stats_multi: stream synchronise failed");
+  members.commit();  // nothing of the batch is pending: no member needs a fence
+  for (pfmpe_ctx* c : distinct)  // (as every single call ends: the brackets of sampled frames still pending)
+    if (const int r_ = harvest_timing(c)) return c == c0 ? r_ : fail(c0, r_, "cloud_stats_multi: " + c->err);
+  for (int s = 0; s < S; ++s) {
+    double r[kCloudWords];
+    std::memcpy(r, hrow + (size_t)kCloudWords * s, sizeof(r));
+    cloud_epilogue(r, ctxs[s]->N, in[s].ref_pose, &out[s]);
+  }
+  return PFMPE_OK;
+}
 int pfmpe_host_assoc_summary(const uint32_t* votes, int M, int B, pfmpe_assoc_out* out) {
   if (!votes || !out || M < 1 || M > kMaxMarkers || B < 0) return PFMPE_E_ARG;
   std::memset(out, 0, sizeof(*out));
