@@ -3,7 +3,9 @@
 // (pf_mpe_lib/src/pose_estimator.cpp:1805-2009) with computeJacobian (PE:2163-2192) and exponentialMap
 // (PE:2194-2226), in fp64.  One function for the kernel (k_refine, one lane per hypothesis) and the host
 // (pfmpe_host_optimise_pose); both sides are built with -ffp-contract=off and share gn_sincos, so they do the same
-// arithmetic (+, -, *, /, sqrt and fmod are correctly rounded on both).
+// arithmetic (+, -, *, /, sqrt and fmod are correctly rounded on both).  What IEEE 754 leaves open is which NaN an
+// operation gives (the sign of a generated one, the payload that is passed on): every double of a result goes through
+// gn_canon, so a non-finite row is the same bytes on both sides too.
 //
 // Everything a lane keeps across iterations lives in registers: the pose (12), the lower triangle of A (21), b (6),
 // K34 * pose (12) and the pivots (6).  Every array below is indexed by loop counters of fully unrolled loops only;
@@ -203,6 +205,9 @@ PFGN_HD void gn_residual(const double* Q, const double* X, const double* z, doub
   e[1] = z[1] - p[1] / p[2];
 }
 
+// a NaN as one bit pattern (the positive quiet NaN without payload); every other value as it is
+PFGN_HD double gn_canon(const double v) { return v == v ? v : __builtin_nan(""); }
+
 // One hypothesis.  markers: M x 3, K: 3 x 3 row-major, blobs: B x 2, corr: n_rows 1-based (LED, blob) rows of which
 // those with blob 0 are skipped, pose0: the 12 doubles of the start pose (read again for the divergence rule, not
 // kept).  The indices are the caller's to check.  cov36: 36 doubles.
@@ -306,7 +311,7 @@ PFGN_HD void gn_optimise(const double* markers, const double* K, const double* b
       for (int r = 0; r < 6; ++r) x[r] = (r == c) ? 1.0 : 0.0;
       gn_solve(a, pv, x);
 #pragma unroll
-      for (int r = 0; r < 6; ++r) cov36[r * 6 + c] = x[r];
+      for (int r = 0; r < 6; ++r) cov36[r * 6 + c] = gn_canon(x[r]);
     }
   } else {
 #pragma unroll
@@ -325,9 +330,9 @@ PFGN_HD void gn_optimise(const double* markers, const double* K, const double* b
     ss1 = ss1 + (e[0] * e[0] + e[1] * e[1]);
   }
 #pragma unroll
-  for (int q = 0; q < 12; ++q) out.pose[q] = P[q];
-  out.rms_before = sqrt(ss0 / (double)np);
-  out.rms_after = sqrt(ss1 / (double)np);
+  for (int q = 0; q < 12; ++q) out.pose[q] = gn_canon(P[q]);
+  out.rms_before = gn_canon(sqrt(ss0 / (double)np));
+  out.rms_after = gn_canon(sqrt(ss1 / (double)np));
   out.iters = iters;
   out.status = conv ? PFMPE_REFINE_CONVERGED : (reverted ? PFMPE_REFINE_CAP_REVERTED : PFMPE_REFINE_CAP_KEPT);
 }
