@@ -591,6 +591,62 @@ int pfmpe_assoc_stats(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, pfmpe
 int pfmpe_get_pairs(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, int64_t first, int32_t count,
                     uint32_t* corr, int32_t* n_corr);
 
+/* ------------------------------------------------------------- the K best distinct hypotheses of a frame */
+/* A step names two particles (the most likely one, the most resampled one); the runner-up, the mirror solution LED
+ * markers are known for (the reference's checkAmbiguity / correspondencesVec), had to be found on the host from
+ * pfmpe_get_weights and pfmpe_get_particles(0).  pfmpe_top_particles ranks the cloud on the device and returns the K
+ * best rows, optionally thinned so that no two of them are the same mode; its poses / corr feed pfmpe_refine_poses.
+ *
+ * Set: the kept propagated set of the last step, the rows of pfmpe_get_particles(0).  Key: PFMPE_TOP_BY_WEIGHT the
+ * kept iteration's raw weight (the particle's value in pfmpe_get_weights), PFMPE_TOP_BY_COUNT its resample count
+ * (pfmpe_get_counts).  Eligible: key > 0 (never a zero or NaN weight, never a zero count).  Ranking: larger key
+ * first, the lower particle index first among equal keys (the reference's first-max rule, maxCoeff, extended to K): a
+ * total order, so a repeated call returns the same bytes.
+ * Without suppression (min_trans == 0 and min_rot == 0) the rows are the first min(K, n_positive) of the ranking.
+ * With suppression the pool, the first min(PFMPE_TOP_POOL, n_positive) of the ranking, is walked in rank order:
+ * candidate j is kept unless an already kept candidate i is near it; the walk stops when K are kept or the pool ends;
+ * n_examined counts the candidates walked.  Near = near_t and near_r, in fp64 on the 12-double poses, every product and
+ * sum rounded on its own, left to right:
+ *   d2 = (tj0-ti0)^2 + (tj1-ti1)^2 + (tj2-ti2)^2;             near_t: min_trans == 0 or d2 < min_trans*min_trans
+ *   tr = sum of Rj[r][c]*Ri[r][c] over the nine entries, row-major;  near_r: min_rot == 0 or tr > 1 + 2*cos(min_rot)
+ * (a threshold of 0 does not separate; the right-hand sides are formed once on the host).
+ *
+ * Outputs, all optional but `out`: index[r] the particle index of row r, key_value[r] its key as a double, poses the
+ * rows pfmpe_get_particles(0) holds for these indices, corr / n_corr the rows
+ * pfmpe_get_pairs(PFMPE_ASSOC_PROPAGATED, blobs, index[r], 1) returns (only when blobs is not NULL).  Exactly n_out
+ * rows of each array are written, nothing else of them is touched.
+ * The call blocks, runs on the context's stream, changes nothing a later frame reads, moves no per-particle array to
+ * the host and is not timed by PFMPE_OPT_TIMING (regenerating the pool's poses counts as aux).
+ * Errors, checked before anything is launched (the outputs stay untouched): PFMPE_E_ARG for a NULL ctx, params or
+ * out, a bad key, K outside 0..PFMPE_TOP_MAX, a negative or non-finite min_trans, min_rot outside [0, pi] or NaN, a
+ * blob descriptor pfmpe_get_pairs refuses; PFMPE_E_CAP for B > max_blobs; PFMPE_E_STATE before the first step, for
+ * BY_COUNT with PFMPE_OPT_RECORD_COUNTS off or after a step that did not resample (as pfmpe_get_counts), and for
+ * blobs without a model. */
+#define PFMPE_TOP_MAX  1024   /* largest K */
+#define PFMPE_TOP_POOL 1024   /* ranked candidates the suppression walks */
+enum { PFMPE_TOP_BY_WEIGHT = 0, PFMPE_TOP_BY_COUNT = 1 };
+typedef struct {
+  int32_t key;        /* PFMPE_TOP_BY_*                                    */
+  int32_t K;          /* rows wanted, 0 .. PFMPE_TOP_MAX                    */
+  double  min_trans;  /* m,   >= 0, finite; 0: translation does not separate */
+  double  min_rot;    /* rad, 0 .. pi;      0: rotation does not separate    */
+} pfmpe_top_params;   /* 24 bytes */
+typedef struct {
+  int64_t n;           /* particles ranked (N)                              */
+  int64_t n_positive;  /* particles with key > 0 (the eligible ones)        */
+  int32_t n_out;       /* rows written                                      */
+  int32_t n_examined;  /* ranked candidates walked (== n_out without suppression) */
+} pfmpe_top_out;       /* 24 bytes */
+void pfmpe_default_top_params(pfmpe_top_params* p);   /* BY_WEIGHT, K = 8, 0, 0 */
+/* blobs NULL: no pairs; poses K x 12, corr K x 2*PFMPE_MAX_MARKERS, index / key_value / n_corr K */
+int pfmpe_top_particles(pfmpe_ctx* ctx, const pfmpe_top_params* params, const pfmpe_assoc_in* blobs, pfmpe_top_out* out,
+                        int32_t* index, double* key_value, double* poses, uint32_t* corr, int32_t* n_corr);
+/* The suppression walk alone, on the host, for P caller-given poses already in rank order (P >= 0, may exceed
+ * PFMPE_TOP_POOL): the predicate is the function the device runs.  keep (K) receives positions within the list.
+ * PFMPE_E_ARG for a NULL pointer, P < 0, K outside 0..PFMPE_TOP_MAX, a bad threshold or a non-finite pose. */
+int pfmpe_host_top_suppress(const double* poses, int32_t P, int32_t K, double min_trans, double min_rot,
+                            int32_t* keep, int32_t* n_out, int32_t* n_examined);
+
 /* ------------------------------------------------------------------- Gauss-Newton refinement of hypotheses */
 /* Replaces PoseEstimator::optimisePose (PE:1805-2009): the reference refines the winner of the PF step over its
  * correspondences and publishes that pose and pose_covariance_ = A.inverse() (PE:2004).  pfmpe_refine_poses does so

@@ -61,7 +61,11 @@ EXPORTED_SYMBOLS = (
     "pfmpe_refine_multi", "pfmpe_host_refine_plan",
     "pfmpe_step_refine", "pfmpe_step_refine_multi", "pfmpe_host_step_tail",
     "pfmpe_cloud_stats_multi", "pfmpe_host_cloud_plan",
+    "pfmpe_default_top_params", "pfmpe_top_particles", "pfmpe_host_top_suppress",
 )
+TOP_MAX = 1024
+TOP_POOL = 1024
+TOP_BY_WEIGHT, TOP_BY_COUNT = 0, 1
 DETECT_MAX_ROIS = 64
 DETECT_MAX_IMAGES = 64
 ROI_MAX_STREAMS = 64
@@ -229,6 +233,17 @@ class AssocOut(C.Structure):
         return d
 
 
+class TopParams(C.Structure):
+    _fields_ = [("key", C.c_int32), ("K", C.c_int32), ("min_trans", C.c_double), ("min_rot", C.c_double)]
+
+
+class TopOut(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_positive", C.c_int64), ("n_out", C.c_int32), ("n_examined", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RefineParams(C.Structure):
     _fields_ = [("max_iter", C.c_int32), ("revert_on_divergence", C.c_int32), ("converged", C.c_double)]
 
@@ -324,6 +339,11 @@ def load() -> C.CDLL:
         "pfmpe_get_pairs": (I, [P, I, C.POINTER(AssocIn), C.c_int64, C.c_int32, C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_int32)]),
         "pfmpe_host_assoc_summary": (I, [C.POINTER(C.c_uint32), I, I, C.POINTER(AssocOut)]),
+        "pfmpe_default_top_params": (None, [C.POINTER(TopParams)]),
+        "pfmpe_top_particles": (I, [P, C.POINTER(TopParams), C.POINTER(AssocIn), C.POINTER(TopOut), C.POINTER(C.c_int32),
+                                    dp, dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+        "pfmpe_host_top_suppress": (I, [dp, C.c_int32, C.c_int32, D, D, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32)]),
         "pfmpe_default_refine_params": (None, [C.POINTER(RefineParams)]),
         "pfmpe_refine_poses": (I, [P, C.POINTER(AssocIn), C.POINTER(RefineParams), dp, C.POINTER(C.c_uint32), C.c_int32,
                                    C.POINTER(RefineOut), P, dp]),
@@ -901,6 +921,36 @@ class Engine:
                                            n_corr.ctypes.data_as(C.POINTER(C.c_int32))))
         return corr, n_corr
 
+    def top_particles(self, key: int = TOP_BY_WEIGHT, K: int = 8, min_trans: float = 0.0, min_rot: float = 0.0,
+                      blobs=None, bank_frame: int = -1) -> dict:
+        """The K best distinct hypotheses of the last step's kept propagated set, ranked on the device
+        (pfmpe_top_particles).  key: TOP_BY_WEIGHT (the raw weights of get_weights) or TOP_BY_COUNT (get_counts);
+        min_trans (m) / min_rot (rad): a candidate closer than both to a better kept one is dropped (0: that threshold
+        does not separate; both 0: the plain ranking).  blobs / bank_frame: also each row's pairs.  Returns
+        TopOut.as_dict() plus the n_out rows: "index" int32, "key_value" and "poses" (n_out, 12) float64 and, with
+        blobs, "corr" (n_out, MAX_MARKERS, 2) uint32 and "n_corr" int32, ready for refine_poses."""
+        prm = TopParams(int(key), int(K), float(min_trans), float(min_rot))
+        want_pairs = blobs is not None or bank_frame >= 0
+        ai, keep = self._assoc_in(blobs, bank_frame)
+        k = min(max(int(K), 0), TOP_MAX)
+        index = np.zeros(k, dtype=np.int32)
+        key_value = np.zeros(k, dtype=np.float64)
+        poses = np.zeros((k, 12), dtype=np.float64)
+        corr = np.zeros((k, MAX_MARKERS, 2), dtype=np.uint32)
+        n_corr = np.zeros(k, dtype=np.int32)
+        out = TopOut()
+        self._chk(self.lib.pfmpe_top_particles(
+            self.ctx, C.byref(prm), C.byref(ai) if want_pairs else None, C.byref(out),
+            index.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(key_value), _dptr(poses),
+            corr.ctypes.data_as(C.POINTER(C.c_uint32)) if want_pairs else None,
+            n_corr.ctypes.data_as(C.POINTER(C.c_int32)) if want_pairs else None))
+        d = out.as_dict()
+        n = out.n_out
+        d.update(index=index[:n], key_value=key_value[:n], poses=poses[:n])
+        if want_pairs:
+            d.update(corr=corr[:n], n_corr=n_corr[:n])
+        return d
+
     def _refine_result(self, out, rows, cov):
         d = out.as_dict()
         d["rows"] = rows
@@ -1184,6 +1234,25 @@ def host_assoc_summary(votes) -> dict:
     d = out.as_dict()
     del d["n_any"], d["npairs_hist"]
     return d
+
+
+def default_top_params() -> TopParams:
+    p = TopParams()
+    load().pfmpe_default_top_params(C.byref(p))
+    return p
+
+
+def host_top_suppress(poses, K: int, min_trans: float = 0.0, min_rot: float = 0.0) -> dict:
+    """The suppression walk of top_particles on the host (pfmpe_host_top_suppress), for P poses already in rank order
+    (P x 12, any P): "keep" the positions kept (n_out of them), "n_out", "n_examined"."""
+    p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+    keep = np.zeros(max(int(K), 1), dtype=np.int32)
+    n_out, n_ex = C.c_int32(-1), C.c_int32(-1)
+    rc = load().pfmpe_host_top_suppress(_dptr(p), p.shape[0], int(K), float(min_trans), float(min_rot),
+                                        keep.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n_out), C.byref(n_ex))
+    if rc != OK:
+        raise PFError(rc, "host_top_suppress: bad arguments")
+    return {"keep": keep[: n_out.value].copy(), "n_out": n_out.value, "n_examined": n_ex.value}
 
 
 def make_detect_images(images):

@@ -3283,6 +3283,24 @@ __global__ __launch_bounds__(kBlock) void k_regen(const FrameArgsT<T> fa, int ke
   make_particle<T, RNG, SP>(fa, sc, prior, n, kept_iter, P);
   for (int q = 0; q < 12; ++q) poses[12 * (int64_t)n + q] = (double)P[q];
 }
+// k_regen for a list of particles (pfmpe_top_particles): row i of `poses` is particle list[i], for i below
+// min(*count, limit); the numbers are k_regen's, make_particle being a function of (prior, n, iteration) alone
+template <typename T, int RNG, typename SP>
+__global__ __launch_bounds__(kBlock) void k_regen_list(const FrameArgsT<T> fa, int kept_iter, const SP* __restrict__ prior,
+                                                      const int32_t* __restrict__ list, const uint32_t* __restrict__ count,
+                                                      int limit, double* __restrict__ poses) {
+  __shared__ LdsConst<T> sc;
+  stage_consts(fa, sc);
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t cnt = *count;
+  if (i >= limit || (uint32_t)i >= cnt) return;
+  const int n = list[i];
+  if (n < 0 || n >= fa.N) return;
+  T P[12];
+  make_particle<T, RNG, SP>(fa, sc, prior, n, kept_iter, P);
+  for (int q = 0; q < 12; ++q) poses[12 * (int64_t)i + q] = (double)P[q];
+}
 // stream of the batch, one launch each): grid (max groups, streams) for the group scans, (streams) for the tops.
 // The bodies are the one-stream kernels' (same functions, same association), with the stream's frame arguments,
 // buffers and counters from its descriptor; blocks past a stream's groups, and streams that failed the staging

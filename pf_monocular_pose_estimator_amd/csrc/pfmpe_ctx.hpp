@@ -172,6 +172,10 @@ struct pfmpe_ctx : CtxQueue {
   Buf<uint32_t> d_assoc; // association votes: M x B bins + the pair-count bins (pfmpe_assoc_stats)
   Buf<uint32_t> d_pairs; // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
   Buf<unsigned char> d_refine; // Gauss-Newton refinement scratch (RefineBuf layout, pfmpe_refine_*)
+  // pfmpe_top_particles: the selection's scratch and the record (pf_top.hpp TopBuf; one size for every N and K,
+  // allocated on first use), and the pinned block the record is read back into
+  Buf<unsigned char> d_top;
+  Buf<unsigned char, Mem::Pinned> h_top;
   // pfmpe_refine_multi (owned by the batch's first context): the packed upload followed by the batch's summaries,
   // rows and covariances, and the pinned block the upload is built in and the results land in; grown on demand
   Buf<unsigned char> d_refm;
@@ -761,14 +765,20 @@ template <typename T, int RNG, typename SP>
 int multi_m(pfmpe_ctx* const* cs, int S, const pfmpe_frame_in* in);
 template <typename T, int RNG, typename SP>
 int regen_m(pfmpe_ctx* c, int kept_iter, const void* prior, double* out);
+// the same for a device list of particle indices: particle list[i] of the kept iteration into out + 12 * i, for
+// i < min(*count, limit) (list, count and out on the device; pfmpe_top_particles)
+template <typename T, int RNG, typename SP>
+int regen_list_m(pfmpe_ctx* c, int kept_iter, const void* prior, const int32_t* list, const uint32_t* count, int limit,
+                 double* out);
 
 }  // namespace pfmpe_impl
 
-// dispatch_m, regen_m and multi_m of one (state type, RNG): defined by a pfmpe_k_*.hip unit (EXT empty), declared for
-// pfmpe_engine.hip (EXT = extern).  Used at file scope.
+// dispatch_m, regen_m, regen_list_m and multi_m of one (state type, RNG): defined by a pfmpe_k_*.hip unit (EXT empty),
+// declared for pfmpe_engine.hip (EXT = extern).  Used at file scope.
 #define PFMPE_DECLARE_INSTANCE(T, RNG, SP, EXT)                                                                        \
   namespace pfmpe_impl {                                                                                               \
   EXT template int dispatch_m<T, RNG, SP>(pfmpe_ctx*, const pfmpe_frame_in*, const unsigned char*, size_t, const GridHdr&); \
   EXT template int regen_m<T, RNG, SP>(pfmpe_ctx*, int, const void*, double*);                                         \
+  EXT template int regen_list_m<T, RNG, SP>(pfmpe_ctx*, int, const void*, const int32_t*, const uint32_t*, int, double*); \
   EXT template int multi_m<T, RNG, SP>(pfmpe_ctx* const*, int, const pfmpe_frame_in*);                                 \
   }

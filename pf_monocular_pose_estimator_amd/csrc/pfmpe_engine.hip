@@ -8,6 +8,7 @@
 #include "pf_likelihood.hpp"
 #include "pf_roi.hpp"
 #include "pf_tail.hpp"
+#include "pf_top.hpp"
 #include "pfmpe_prior.hpp"
 #include "pfmpe_refine_plan.hpp"
 
@@ -34,6 +35,14 @@ int dispatch_regen(pfmpe_ctx* c, int kept_iter, const void* prior, double* out) 
   return visit_state_rng(c, [&](auto s) {
     using S = decltype(s);
     return regen_m<typename S::T, S::RNG, typename S::SP>(c, kept_iter, prior, out);
+  });
+}
+
+int dispatch_regen_list(pfmpe_ctx* c, int kept_iter, const void* prior, const int32_t* list, const uint32_t* count,
+                        int limit, double* out) {
+  return visit_state_rng(c, [&](auto s) {
+    using S = decltype(s);
+    return regen_list_m<typename S::T, S::RNG, typename S::SP>(c, kept_iter, prior, list, count, limit, out);
   });
 }
 
@@ -1125,6 +1134,96 @@ int pfmpe_get_pairs(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, int64_t f
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RET(harvest_timing(c));
+  return PFMPE_OK;
+}
+
+// ---- the K best distinct hypotheses of the kept propagated set (pf_top.hpp; the kernels are in pfmpe_top.hip)
+void pfmpe_default_top_params(pfmpe_top_params* p) {
+  if (!p) return;
+  p->key = PFMPE_TOP_BY_WEIGHT;
+  p->K = 8;
+  p->min_trans = 0.0;
+  p->min_rot = 0.0;
+}
+
+int pfmpe_top_particles(pfmpe_ctx* c, const pfmpe_top_params* params, const pfmpe_assoc_in* in, pfmpe_top_out* out,
+                        int32_t* index, double* key_value, double* poses, uint32_t* corr, int32_t* n_corr) {
+  if (!c) return PFMPE_E_ARG;
+  if (!params || !out) return fail(c, PFMPE_E_ARG, "top_particles: null params or out");
+  const pfmpe_top_params prm = *params;
+  if (prm.key != PFMPE_TOP_BY_WEIGHT && prm.key != PFMPE_TOP_BY_COUNT) return fail(c, PFMPE_E_ARG, "top_particles: bad key");
+  if (prm.K < 0 || prm.K > PFMPE_TOP_MAX) return fail(c, PFMPE_E_ARG, "top_particles: K out of range");
+  if (!(prm.min_trans >= 0.0) || !std::isfinite(prm.min_trans))
+    return fail(c, PFMPE_E_ARG, "top_particles: min_trans must be finite and >= 0");
+  if (!(prm.min_rot >= 0.0 && prm.min_rot <= M_PI)) return fail(c, PFMPE_E_ARG, "top_particles: min_rot outside [0, pi]");
+  const double* blobs = nullptr;
+  int B = 0;
+  if (in) RET(resolve_blobs(c, "top_particles", in, &blobs, &B));
+  if (!c->has_prior || !c->has_last) return fail(c, PFMPE_E_STATE, "top_particles: no step yet");
+  if (prm.key == PFMPE_TOP_BY_COUNT) {
+    if (!c->record_counts || !c->d_counts.get()) return fail(c, PFMPE_E_STATE, "top_particles: PFMPE_OPT_RECORD_COUNTS off");
+    if (!c->last_accepted) return fail(c, PFMPE_E_STATE, "top_particles: last step did not resample");
+  }
+  if (in && !c->has_model) return fail(c, PFMPE_E_STATE, "top_particles: blobs given without a model");
+  RET(set_device(c));
+  RET(c->d_top.ensure(c, TopBuf::bytes()));
+  RET(c->h_top.ensure(c, TopRows::bytes(PFMPE_TOP_MAX)));
+  const int N = c->N;
+  const int rows = std::min(prm.K, N);  // n_out <= min(K, n_positive): the rows the record is laid out for
+  const TopThresholds th = top_thresholds(prm.min_trans, prm.min_rot);
+  const bool suppress = prm.min_trans != 0.0 || prm.min_rot != 0.0;
+  const bool pairs = in && rows > 0;
+  const bool want_poses = suppress || pairs || (poses && rows > 0);
+  unsigned char* d = c->d_top.get();
+
+  const void* keys = c->d_w[c->last_kept_slot].get();
+  int key_type = c->state_dtype == PFMPE_STATE_F64 ? kTopKeyF64 : kTopKeyF32;
+  if (prm.key == PFMPE_TOP_BY_COUNT) {
+    keys = c->d_counts.get();
+    key_type = kTopKeyU32;
+  }
+  const uint32_t* pool_count = nullptr;
+  RET(top_select_launch(c, d, keys, key_type, N, &pool_count));
+  // the poses of the ranked pool only (all of it for the suppression walk, else the rows wanted), as k_regen makes
+  // them: bracketed as aux like every regeneration
+  if (want_poses)
+    RET(dispatch_regen_list(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), (const int32_t*)(d + TopBuf::kPoolIdx),
+                            pool_count, suppress ? kTopPool : rows, (double*)(d + TopBuf::kPoolPoses)));
+  RET(top_finish_launch(c, d, prm.K, rows, th, want_poses));
+  unsigned char* rec = d + TopBuf::kRecord;
+  if (pairs) {
+    // the rows' pairs as pfmpe_get_pairs derives them: the blob table as assoc_prepare builds it, the pair kernel in
+    // rows mode over the dense list of the kept rows' poses (it bounds its range by first / count alone; count is
+    // `rows`, the rows behind n_out hold a constant pose and are not returned)
+    const size_t tbytes = build_table(c, blobs, B, c->h_table.get());
+    const GridHdr gh = *(const GridHdr*)(c->h_table.get() + grid_off(c, B));
+    HIPCHK(c, hipMemcpyAsync(c->d_table.get(), c->h_table.get(), tbytes, hipMemcpyHostToDevice, c->stream));
+    AssocArgs aa{};
+    aa.dense = (const double*)(rec + TopRows::poses(rows));
+    aa.corr = (uint32_t*)(rec + TopRows::corr(rows));
+    aa.n_corr = (int32_t*)(rec + TopRows::n_corr(rows));
+    aa.first = 0;
+    aa.count = rows;
+    RET(assoc_launch(c, B, c->d_table.get(), tbytes, gh, aa));
+  }
+  // one read-back: the record and the rows (without the pair rows when no blobs were given)
+  unsigned char* h = c->h_top.get();
+  const size_t bytes = pairs ? TopRows::bytes(rows) : TopRows::n_corr(rows);
+  HIPCHK(c, hipMemcpyAsync(h, rec, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  RET(harvest_timing(c));
+  const TopRecord r = *(const TopRecord*)h;
+  if (r.n_out < 0 || r.n_out > rows) return fail(c, PFMPE_E_STATE, "top_particles: inconsistent record");
+  out->n = N;
+  out->n_positive = r.n_positive;
+  out->n_out = r.n_out;
+  out->n_examined = r.n_examined;
+  const size_t n = (size_t)r.n_out;
+  if (index) std::memcpy(index, h + TopRows::index(rows), n * sizeof(int32_t));
+  if (key_value) std::memcpy(key_value, h + TopRows::kKey, n * sizeof(double));
+  if (poses) std::memcpy(poses, h + TopRows::poses(rows), n * 12 * sizeof(double));
+  if (pairs && corr) std::memcpy(corr, h + TopRows::corr(rows), n * kPairRow * sizeof(uint32_t));
+  if (pairs && n_corr) std::memcpy(n_corr, h + TopRows::n_corr(rows), n * sizeof(int32_t));
   return PFMPE_OK;
 }
 

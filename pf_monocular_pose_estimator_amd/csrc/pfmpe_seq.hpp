@@ -1,7 +1,7 @@
 #pragma once
 // pfmpe_seq.hpp — the launch sequences of pfmpe_step and pfmpe_step_multi (Seq) and their entry points for one
-// (state type, RNG): dispatch_m, multi_m, regen_m.  Included only by the pfmpe_k_<state>_<rng>.hip units, which
-// instantiate them (PFMPE_DECLARE_INSTANCE); every other unit sees the declarations in pfmpe_ctx.hpp.
+// (state type, RNG): dispatch_m, multi_m, regen_m, regen_list_m.  Included only by the pfmpe_k_<state>_<rng>.hip units,
+// which instantiate them (PFMPE_DECLARE_INSTANCE); every other unit sees the declarations in pfmpe_ctx.hpp.
 #include "pf_kernels.hpp"
 #include "pf_weigh_pk.hpp"
 #include "pfmpe_args.hpp"
@@ -618,6 +618,15 @@ struct Seq {
                          (const SP*)prior, out);
     });
   }
+  static int regen_list(pfmpe_ctx* c, int kept_iter, const void* prior, const int32_t* list, const uint32_t* count,
+                        int limit, double* out) {
+    const FrameArgsT<T>& fa = last_args<T>(c);
+    if (limit < 1) return PFMPE_OK;
+    return launch_ext(c, PFMPE_K_AUX, [&] {
+      klaunch(c, k_regen_list<T, RNG, SP>, dim3((limit + kBlock - 1) / kBlock), dim3(kBlock), 0, fa, kept_iter,
+              (const SP*)prior, list, count, limit, out);
+    });
+  }
 };
 
 template <typename T, int RNG, typename SP>
@@ -773,6 +782,11 @@ int multi_m(pfmpe_ctx* const* cs, int S, const pfmpe_frame_in* in) {
 template <typename T, int RNG, typename SP>
 int regen_m(pfmpe_ctx* c, int kept_iter, const void* prior, double* out) {
   return Seq<T, RNG, 8, SP>::regen(c, kept_iter, prior, out);
+}
+template <typename T, int RNG, typename SP>
+int regen_list_m(pfmpe_ctx* c, int kept_iter, const void* prior, const int32_t* list, const uint32_t* count, int limit,
+                 double* out) {
+  return Seq<T, RNG, 8, SP>::regen_list(c, kept_iter, prior, list, count, limit, out);
 }
 
 }  // namespace pfmpe_impl
