@@ -169,7 +169,8 @@ int pfmpe_step_multi_batch(pfmpe_ctx* const* ctxs, int S, const pfmpe_frame_in* 
  * N particles of the current prior, plus the markers at predicted_pose_; the bounding box (x_min/y_min
  * from +inf, x_max/y_max from 0); its corners as cv::Point2f through distortPoints (plumb_bob D, in
  * double); border, clamp to the image, integer cv::Rect (the whole image when narrower than 1 px).
- * Call it before pfmpe_step of the same frame (the prior is the resampled set of the previous one). */
+ * Call it before pfmpe_step of the same frame (the prior is the resampled set of the previous one).  The call is
+ * pfmpe_predict_roi_multi (below) with S = 1: the same kernels and host path, on ctx's stream and scratch. */
 typedef struct {
   double cam_move_inv[12];   /* camMoveInv (PE:241-393)                                          */
   double prediction[12];     /* predictionMatrix (PE:234)                                        */
@@ -490,7 +491,8 @@ int pfmpe_get_counts(pfmpe_ctx* ctx, uint32_t* out);
  *
  * Blocking; runs on the context's stream (after the last frame, before the next).  Changes nothing the next
  * frame reads.  Not timed by PFMPE_OPT_TIMING (there is no kernel-statistics slot for it; regenerating the
- * WEIGHTED set counts as aux, as for the particle read-back).
+ * WEIGHTED set counts as aux, as for the particle read-back).  The call is pfmpe_cloud_stats_multi (below) with one
+ * entry: the same kernels and host path, on ctx's stream and scratch.
  * Errors: PFMPE_E_ARG for a bad `which`, a NULL pointer or a non-finite reference pose; PFMPE_E_STATE with no
  * particle set, and for WEIGHTED before the first step. */
 enum { PFMPE_CLOUD_WEIGHTED = 0,   /* kept propagated set of the last step with probPart as weights
@@ -885,7 +887,7 @@ enum { PFMPE_K_PROPAGATE = 0, /* k_propagate_weigh (+ last-block iteration reduc
        PFMPE_K_RESAMPLE = 1,  /* k_resample / k_resample_owners: resampling           */
        PFMPE_K_AUX = 2,       /* hand-off kernels (k_group*, k_top*), regeneration   */
        PFMPE_K_FRAME = 3,     /* k_frame: the whole frame in one launch              */
-       PFMPE_K_ROI = 4,       /* k_roi + k_roi_final (pfmpe_predict_roi), k_roi_multi* */
+       PFMPE_K_ROI = 4,       /* k_roi_stage + k_roi_multi* (pfmpe_predict_roi[_multi]) */
        PFMPE_K_FINAL = 5,     /* k_resample_final (non-deferred frames): the record   */
        PFMPE_K_P3P_HIST = 6,  /* k_p3p_hist: initialisation histogram                */
        PFMPE_K_P3P_CHECK = 7, /* k_p3p_check: checkCorrespondences of all candidates */

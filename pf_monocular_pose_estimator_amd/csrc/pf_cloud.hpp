@@ -78,114 +78,20 @@ struct CloudArgs {
   int32_t N, pad;
   int64_t ld;
   const uint32_t* owner;  // a deferred prior's owner indices (FrameArgsT::owner), or null
-  const double* dense;    // DENSE: N x 12 poses (the regenerated kept set)
-  const void* w;          // DENSE: its raw weights (compute type T)
+  const double* dense;    // dense: N x 12 poses (the regenerated kept set)
+  const void* w;          // dense: its raw weights (compute type T)
 };
-// DENSE = false: the resident prior through StateIO / the owner indices, exactly the rows k_export writes, unit
-// weights.  DENSE = true: N x 12 doubles with weights widened as k_weights_export widens them.  Each lane sums its
-// particles in index order; one DPP reduction per wave after the stride loop; the block's waves are added in wave
-// order through LDS.  No atomics, no waits on other blocks: k_cloud_final is a second launch.
-template <typename T, typename SP, bool DENSE>
-__global__ __launch_bounds__(kBlock) void k_cloud_partials(const CloudArgs ca, const SP* __restrict__ st,
-                                                          double* __restrict__ part) {
-  __shared__ double sh[kWaves][kCloudWords];
-  double acc[kCloudSums];
-#pragma unroll
-  for (int q = 0; q < kCloudSums; ++q) acc[q] = 0.0;
-  double mt = 0.0, mr = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t n = (int64_t)blockIdx.x * kBlock + threadIdx.x; n < ca.N; n += stride) {
-    double P[12], w = 1.0;
-    if constexpr (DENSE) {
-#pragma unroll
-      for (int q = 0; q < 12; ++q) P[q] = ca.dense[12 * n + q];
-      w = (double)((const T*)ca.w)[n];
-    } else {
-      const int64_t r = ca.owner ? (int64_t)ca.owner[n] : n;
-#pragma unroll
-      for (int q = 0; q < 12; ++q)
-        P[q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ca.ld)], (T)ca.anchor[q]);
-    }
-    double xi[6], wx[6];
-    pose_twist(P, ca.ref, xi);
-    acc[0] = acc[0] + w;
-    acc[1] = acc[1] + w * w;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      wx[q] = w * xi[q];
-      acc[2 + q] = acc[2 + q] + wx[q];
-    }
-    int k = 8;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = i; j < 6; ++j, ++k) acc[k] = acc[k] + wx[i] * xi[j];
-    const double t2 = (xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2];
-    const double r2 = (xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5];
-    mt = (w > 0.0 && t2 > mt) ? t2 : mt;
-    mr = (w > 0.0 && r2 > mr) ? r2 : mr;
-  }
-#pragma unroll
-  for (int q = 0; q < kCloudSums; ++q) acc[q] = lane_value(wave_incl_sum(acc[q]), 63);
-  mt = wave_max(mt);
-  mr = wave_max(mr);
-  const int wv = wave_id();
-  if (lane_id() == 0) {
-#pragma unroll
-    for (int q = 0; q < kCloudSums; ++q) sh[wv][q] = acc[q];
-    sh[wv][kCloudSums] = mt;
-    sh[wv][kCloudSums + 1] = mr;
-    sh[wv][kCloudSums + 2] = 0.0;
-  }
-  __syncthreads();
-  if (threadIdx.x < kCloudWords) {
-    const int q = threadIdx.x;
-    double v = sh[0][q];
-    for (int x = 1; x < kWaves; ++x) v = q < kCloudSums ? v + sh[x][q] : (sh[x][q] > v ? sh[x][q] : v);
-    part[(size_t)blockIdx.x * kCloudWords + q] = v;
-  }
-}
-// One block: word q of the result = the partial rows' word q combined in block order.  The rows are cut into
-// kCloudSegs runs of consecutive rows; 32 lanes per run add its rows in index order (16 loads in flight: one lane
-// walking all 1024 rows, a load's latency per row, took 50 us), then the runs are added in run order.  The tree
-// depends on nblk alone.  (0 is the identity of the sums and of the maxima, which are of squares.)
-constexpr int kCloudSegs = 8;
-template <typename V>  // (a template from when the header was in several TUs; its symbol is kept)
-__global__ __launch_bounds__(kCloudSegs* kCloudWords) void k_cloud_final(const V* __restrict__ part, int nblk,
-                                                                        V* __restrict__ out) {
-  __shared__ V sh[kCloudSegs][kCloudWords];
-  const int q = threadIdx.x % kCloudWords, sg = threadIdx.x / kCloudWords;
-  const int per = (nblk + kCloudSegs - 1) / kCloudSegs;
-  const int b0 = sg * per, b1 = b0 + per < nblk ? b0 + per : nblk;
-  const bool sum = q < kCloudSums;
-  V v = 0;
-  int b = b0;
-  for (; b + 16 <= b1; b += 16) {
-    V x[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x[i] = part[(size_t)(b + i) * kCloudWords + q];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v = sum ? v + x[i] : (x[i] > v ? x[i] : v);
-  }
-  for (; b < b1; ++b) {
-    const V x = part[(size_t)b * kCloudWords + q];
-    v = sum ? v + x : (x > v ? x : v);
-  }
-  sh[sg][q] = v;
-  __syncthreads();
-  if (sg == 0) {
-    for (int s = 1; s < kCloudSegs; ++s) v = sum ? v + sh[s][q] : (sh[s][q] > v ? sh[s][q] : v);
-    out[q] = v;
-  }
-}
 
-// ---- the cloud statistics of S entries in one batch (pfmpe_cloud_stats_multi).  One flat grid, as k_roi_multi's:
-// entry s owns the blocks first[s] .. first[s + 1], the cloud_blocks(N_s) blocks of its single call, and a block
-// finds its entry with roi_stream_of_block (wave-uniform: the descriptor is read with scalar loads).  Inside its
-// entry a block is block lb of nb: it starts at particle lb * kBlock and strides by nb * kBlock, the single call's
-// gridDim.x * kBlock, so every lane sums the particles the single call's lane sums, in that order; the wave and
-// block reductions and the tree over the partial rows are the single call's too, and so are the bits.
-// (k_cloud_partials and k_cloud_final keep their own text: the single call is the timing baseline of the batch.)
+// ---- the cloud statistics of S entries in one batch (pfmpe_cloud_stats_multi; pfmpe_cloud_stats is a batch of
+// one).  One flat grid, as k_roi_multi's: entry s owns the blocks first[s] .. first[s + 1], cloud_blocks(N_s) of
+// them, and a block finds its entry with roi_stream_of_block (wave-uniform: the descriptor is read with scalar
+// loads).  Inside its entry a block is block lb of nb: it starts at particle lb * kBlock and strides by nb * kBlock.
+// Grid, stride, reductions and the tree over the partial rows are a function of the entry's N alone, so an entry's
+// bits do not depend on its neighbours.
+// Resident entry: the prior through StateIO / the owner indices, exactly the rows k_export writes, unit weights.
+// Dense entry: N x 12 doubles with weights widened as k_weights_export widens them.  Each lane sums its particles
+// in index order; one DPP reduction per wave after the stride loop; the block's waves are added in wave order
+// through LDS.  No atomics, no waits on other blocks: k_cloud_multi_final is a second launch.
 constexpr int kCloudMaxStreams = 64;
 static_assert(kCloudMaxStreams <= kRoiMaxStreams, "CloudBatch::first is read by roi_stream_of_block");
 struct CloudBatch {  // head of the batch's device image, the descriptors follow
@@ -268,8 +174,12 @@ __global__ __launch_bounds__(kBlock) void k_cloud_multi(const CloudBatch* __rest
     part[(size_t)blockIdx.x * kCloudWords + q] = v;  // row first[s] + lb
   }
 }
-// one block per entry: its partial rows through k_cloud_final's tree (the runs are cut on the entry's own block
-// count) -> the kCloudWords words of entry s of `out` (pinned, host-mapped: no copy back)
+// One block per entry: word q of its result = its partial rows' word q combined in block order -> the kCloudWords
+// words of entry e of `out` (pinned, host-mapped: no copy back).  The rows are cut into kCloudSegs runs of
+// consecutive rows; 32 lanes per run add its rows in index order (16 loads in flight: one lane walking all 1024 rows,
+// a load's latency per row, took 50 us), then the runs are added in run order.  The tree depends on the entry's own
+// block count alone.  (0 is the identity of the sums and of the maxima, which are of squares.)
+constexpr int kCloudSegs = 8;
 __global__ __launch_bounds__(kCloudSegs* kCloudWords) void k_cloud_multi_final(const CloudBatch* __restrict__ hd,
                                                                               const double* __restrict__ part,
                                                                               double* __restrict__ out) {

@@ -19,7 +19,7 @@ struct RoiArgs {
 };
 // One particle's share of the box: prior particle n (stored row owner[n] of a deferred prior) through
 // camMoveInv * prior_n * predictionMatrix, K * that, and the M projections folded into box = {x_min, x_max, y_min,
-// y_max} with the reference's strict comparisons.  The one body of k_roi, k_roi_multi and the host twin
+// y_max} with the reference's strict comparisons.  The one body of k_roi_multi and the host twin
 // (pfmpe_host_predict_roi, which passes each caller-given pose as a one-particle set with ld = 1); host and device
 // are built with -ffp-contract=off, so they round alike.
 template <typename T, typename SP>
@@ -100,86 +100,13 @@ __device__ __forceinline__ void roi_partials_box(double (&sh)[4][kWaves], const 
   }
   roi_block_box(sh, xmin, xmax, ymin, ymax, out);
 }
-template <typename T, typename SP>
-__global__ __launch_bounds__(kBlock) void k_roi(const RoiArgs ra, const SP* __restrict__ prior,
-                                               double* __restrict__ part) {
-  __shared__ double sh[4][kWaves];
-  const int n = blockIdx.x * kBlock + threadIdx.x;
-  double xmin = INFINITY, xmax = 0.0, ymin = INFINITY, ymax = 0.0;
-  // (the text of roi_particle_box and roi_block_box, kept here: calling either changes this kernel's register
-  // allocation, and the single call is the timing baseline of the batch)
-  if (n < ra.N) {
-    double A[12], X[12], P[12];
-    const int r = ra.owner ? (int)ra.owner[n] : n;
-#pragma unroll
-    for (int q = 0; q < 12; ++q)
-      A[q] = (double)StateIO<T, SP>::load(prior[plane_index<SP>(q, r, ra.ld)], (T)ra.anchor[q]);
-    compose(ra.cam, A, X);   // camMoveInv * newPoseEstimation[j]
-    compose(X, ra.predm, P); // ... * predictionMatrix
-    double Q[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        double s = ra.K[i * 3 + 0] * P[0 * 4 + j];
-        s = s + ra.K[i * 3 + 1] * P[1 * 4 + j];
-        s = s + ra.K[i * 3 + 2] * P[2 * 4 + j];
-        Q[i * 4 + j] = s;
-      }
-    for (int m = 0; m < ra.M; ++m) {
-      const double x = ra.markers[3 * m], y = ra.markers[3 * m + 1], z = ra.markers[3 * m + 2];
-      double p[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        double s = Q[i * 4 + 0] * x;
-        s = s + Q[i * 4 + 1] * y;
-        s = s + Q[i * 4 + 2] * z;
-        p[i] = s + Q[i * 4 + 3];
-      }
-      const double u = p[0] / p[2], v = p[1] / p[2];
-      if (u < xmin) xmin = u;
-      if (u > xmax) xmax = u;
-      if (v < ymin) ymin = v;
-      if (v > ymax) ymax = v;
-    }
-  }
-  xmin = wave_min(xmin);
-  xmax = wave_max(xmax);
-  ymin = wave_min(ymin);
-  ymax = wave_max(ymax);
-  const int lane = lane_id(), wv = wave_id();
-  if (lane == 0) {
-    sh[0][wv] = xmin;
-    sh[1][wv] = xmax;
-    sh[2][wv] = ymin;
-    sh[3][wv] = ymax;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; ++w) {
-      xmin = sh[0][w] < xmin ? sh[0][w] : xmin;
-      xmax = sh[1][w] > xmax ? sh[1][w] : xmax;
-      ymin = sh[2][w] < ymin ? sh[2][w] : ymin;
-      ymax = sh[3][w] > ymax ? sh[3][w] : ymax;
-    }
-    double* o = part + 4 * (size_t)blockIdx.x;
-    o[0] = xmin;
-    o[1] = xmax;
-    o[2] = ymin;
-    o[3] = ymax;
-  }
-}
-template <typename T>  // (a template from when the header was in several TUs; its symbol is kept)
-__global__ __launch_bounds__(kBlock) void k_roi_final(const T* __restrict__ part, int nblk, T* __restrict__ out) {
-  __shared__ double sh[4][kWaves];
-  roi_partials_box(sh, part, nblk, out);
-}
 
-// ---- the ROIs of S contexts in one batch (pfmpe_predict_roi_multi).  One flat grid: stream s owns the blocks
-// first[s] .. first[s + 1] (kBlock particles each, the blocks of its single call), so a small cloud next to a large
+// ---- the ROIs of S contexts in one batch (pfmpe_predict_roi_multi; pfmpe_predict_roi is a batch of one).  One flat
+// grid: stream s owns the blocks first[s] .. first[s + 1] (kBlock particles each), so a small cloud next to a large
 // one launches its own block count only.  A block finds its stream by one wave-wide comparison against the prefix
 // (S <= 64 = the wave size: lane s holds first[s]); the index is wave-uniform, so the descriptor is read with scalar
-// loads.  Block and wave boundaries, the partials and their reduction are the single call's, so are the bits.
+// loads.  Block and wave boundaries, the partials and their reduction are a stream's own, so its bits do not depend
+// on its neighbours.
 constexpr int kRoiMaxStreams = 64;
 static_assert(kRoiMaxStreams <= 64, "roi_stream_of_block compares one prefix entry per lane of a wave");
 struct RoiBatch {  // head of the batch's device image, the descriptors follow

@@ -167,8 +167,6 @@ struct pfmpe_ctx : CtxQueue {
   Buf<uint32_t> d_gen; // k_frame iteration release word (monotonic)
   Buf<Cand> d_cand; // per-block winner candidates
   Buf<double> d_mlpose; // most likely pose (12)
-  Buf<double> d_roi;   // ROI box [4] + per-block partials
-  Buf<double> d_cloud; // cloud statistics: result row + per-block partial rows (pfmpe_cloud_stats)
   Buf<uint32_t> d_assoc; // association votes: M x B bins + the pair-count bins (pfmpe_assoc_stats)
   Buf<uint32_t> d_pairs; // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
   Buf<unsigned char> d_refine; // Gauss-Newton refinement scratch (RefineBuf layout, pfmpe_refine_*)
@@ -205,14 +203,14 @@ struct pfmpe_ctx : CtxQueue {
   // pfmpe_find_leds_streams (owned by the batch's first context): the pinned, host-mapped pack of the ROI crops of the
   // batch's host images, grown on demand; on the device they land in a region of d_detm
   Buf<uint8_t, Mem::Mapped> h_detm_pix;
-  // pfmpe_predict_roi_multi (owned by the batch's first context): the batch scratch (head + descriptors, then one
-  // partial per block of the batch; grown on demand), and the pinned, host-mapped image of the head + descriptors
-  // followed by the result boxes of PFMPE_ROI_MAX_STREAMS streams
+  // pfmpe_predict_roi_multi (owned by the batch's first context; pfmpe_predict_roi is a batch of one): the batch
+  // scratch (head + descriptors, then one partial per block of the batch; grown on demand), and the pinned,
+  // host-mapped image of the head + descriptors followed by the result boxes of PFMPE_ROI_MAX_STREAMS streams
   Buf<unsigned char> d_roim;
   Buf<unsigned char, Mem::Mapped> h_roim;
-  // pfmpe_cloud_stats_multi (owned by the batch's first context): the batch scratch (head + descriptors, then one
-  // partial row per block of the batch; grown on demand, never shrunk), and the pinned, host-mapped image of the
-  // head + descriptors followed by the result rows of PFMPE_CLOUD_MAX_STREAMS entries
+  // pfmpe_cloud_stats_multi (owned by the batch's first context; pfmpe_cloud_stats is a batch of one): the batch
+  // scratch (head + descriptors, then one partial row per block of the batch; grown on demand, never shrunk), and the
+  // pinned, host-mapped image of the head + descriptors followed by the result rows of PFMPE_CLOUD_MAX_STREAMS entries
   Buf<unsigned char> d_cloudm;
   Buf<unsigned char, Mem::Mapped> h_cloudm;
   int num_cu = 0;

@@ -593,55 +593,19 @@ RoiArgs roi_args(const pfmpe_ctx* c, const pfmpe_roi_in* in) {
   ra.owner = prior_owner_ptr(c);
   return ra;
 }
-}  // namespace
-
-int pfmpe_predict_roi(pfmpe_ctx* c, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
-  if (!c) return PFMPE_E_ARG;
-  if (!in || !out) return fail(c, PFMPE_E_ARG, "predict_roi: null in/out");
-  if (!c->has_model || !c->has_prior) return fail(c, PFMPE_E_STATE, "predict_roi: set_model and set_prior first");
-  if (in->image_w < 1 || in->image_h < 1) return fail(c, PFMPE_E_ARG, "predict_roi: bad image size");
-  RET(set_device(c));
-  const int N = c->N;
-  const int nblk = (N + kBlock - 1) / kBlock;
-  RET(c->d_roi.ensure(c, ((size_t)c->max_blk + 1) * 4 * sizeof(double)));
-  const RoiArgs ra = roi_args(c, in);
-  double* part = c->d_roi.get() + 4;
-  c->timing_now = c->timing > 0;  // bracketed like the detector's and the initialisation's launches
-  const int rl = launch(c, PFMPE_K_ROI, [&] {
-    visit_state(c, [&](auto s) {
-      using SP = typename decltype(s)::SP;
-      hipLaunchKernelGGL((k_roi<typename decltype(s)::T, SP>), dim3(nblk), dim3(kBlock), 0, c->stream, ra,
-                         (const SP*)c->d_state[c->prior_idx].get(), part);
-    });
-    hipLaunchKernelGGL((k_roi_final<double>), dim3(1), dim3(kBlock), 0, c->stream, part, nblk, c->d_roi.get());
-  });
-  c->timing_now = false;
-  RET(rl);
-  double bb[4];
-  HIPCHK(c, hipMemcpyAsync(bb, c->d_roi.get(), sizeof(bb), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  RET(harvest_timing(c));
-  roi_epilogue(c->K, c->markers, c->M, in, bb, out);
+// what one stream of an ROI call must satisfy: its context c and its request; the text begins with `at`, on `err`
+int roi_check_stream(pfmpe_ctx* err, const pfmpe_ctx* c, const pfmpe_roi_in* in, const std::string& at) {
+  if (!c->has_model || !c->has_prior) return fail(err, PFMPE_E_STATE, at + "set_model and set_prior first");
+  if (in->image_w < 1 || in->image_h < 1) return fail(err, PFMPE_E_ARG, at + "bad image size");
   return PFMPE_OK;
 }
-
-int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
-  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+// The ROIs of S checked streams, 1 <= S <= kRoiMaxStreams, on ctxs[0]'s stream: pfmpe_predict_roi_multi and, as a
+// batch of one, pfmpe_predict_roi.  The errors it can raise itself begin with `who`.
+int roi_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* in, pfmpe_roi_out* out, const std::string& who) {
   pfmpe_ctx* c0 = ctxs[0];
-  if (!in || !out) return fail(c0, PFMPE_E_ARG, "predict_roi_multi: null in/out");
-  if (S > PFMPE_ROI_MAX_STREAMS)
-    return fail(c0, PFMPE_E_CAP, "predict_roi_multi: S exceeds PFMPE_ROI_MAX_STREAMS");
   int64_t total = 0;
-  RET(check_members(
-      ctxs, S, "predict_roi_multi", "device and state type", [](const pfmpe_ctx*) { return true; },
-      [&](int s, const std::string& at) {
-        const pfmpe_ctx* c = ctxs[s];
-        if (!c->has_model || !c->has_prior) return fail(c0, PFMPE_E_STATE, at + "set_model and set_prior first");
-        if (in[s].image_w < 1 || in[s].image_h < 1) return fail(c0, PFMPE_E_ARG, at + "bad image size");
-        total += (c->N + kBlock - 1) / kBlock;
-        return (int)PFMPE_OK;
-      }));
-  if (total > INT32_MAX) return fail(c0, PFMPE_E_CAP, "predict_roi_multi: too many blocks in one batch");
+  for (int s = 0; s < S; ++s) total += (ctxs[s]->N + kBlock - 1) / kBlock;
+  if (total > INT32_MAX) return fail(c0, PFMPE_E_CAP, who + ": too many blocks in one batch");
   RET(set_device(c0));
   // the scratch before any member's ordering state changes: pinned image (head, descriptors, result boxes) once,
   // device image + partials grown on demand (nothing of an earlier batch is pending: the call is blocking)
@@ -688,7 +652,7 @@ int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* i
   });
   c0->timing_now = false;
   if (rc == PFMPE_OK && hipStreamSynchronize(c0->stream) != hipSuccess)
-    rc = fail(c0, PFMPE_E_HIP, "predict_roi_multi: stream synchronise failed");
+    rc = fail(c0, PFMPE_E_HIP, who + ": stream synchronise failed");
   if (rc == PFMPE_OK) rc = harvest_timing(c0);
   RET(rc);
   members.commit();  // nothing of the batch is pending: no member needs a fence
@@ -698,6 +662,26 @@ int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* i
     roi_epilogue(ctxs[s]->K, ctxs[s]->markers, ctxs[s]->M, &in[s], bb, &out[s]);
   }
   return PFMPE_OK;
+}
+}  // namespace
+
+int pfmpe_predict_roi(pfmpe_ctx* c, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
+  if (!c) return PFMPE_E_ARG;
+  if (!in || !out) return fail(c, PFMPE_E_ARG, "predict_roi: null in/out");
+  RET(roi_check_stream(c, c, in, "predict_roi: "));
+  return roi_run(&c, 1, in, out, "predict_roi");
+}
+
+int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
+  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+  pfmpe_ctx* c0 = ctxs[0];
+  if (!in || !out) return fail(c0, PFMPE_E_ARG, "predict_roi_multi: null in/out");
+  if (S > PFMPE_ROI_MAX_STREAMS)
+    return fail(c0, PFMPE_E_CAP, "predict_roi_multi: S exceeds PFMPE_ROI_MAX_STREAMS");
+  RET(check_members(
+      ctxs, S, "predict_roi_multi", "device and state type", [](const pfmpe_ctx*) { return true; },
+      [&](int s, const std::string& at) { return roi_check_stream(c0, ctxs[s], &in[s], at); }));
+  return roi_run(ctxs, S, in, out, "predict_roi_multi");
 }
 
 int pfmpe_host_predict_roi(const double* markers_xyz, int M, const double* K, const double* poses, int64_t N,
@@ -842,49 +826,6 @@ void cloud_epilogue(const double* r, int N, const double* ref, pfmpe_cloud_out* 
 }
 }  // namespace
 
-int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_out* out) {
-  if (!c) return PFMPE_E_ARG;
-  if (!ref || !out || (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR))
-    return fail(c, PFMPE_E_ARG, "cloud_stats: bad arguments");
-  for (int q = 0; q < 12; ++q)
-    if (!std::isfinite(ref[q])) return fail(c, PFMPE_E_ARG, "cloud_stats: non-finite reference pose");
-  if (!c->has_prior) return fail(c, PFMPE_E_STATE, "cloud_stats: no particle set");
-  if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_stats(weighted): no step yet");
-  RET(set_device(c));
-  // scratch of the call's own (nothing a frame reads): the result row, then one partial row per block
-  RET(c->d_cloud.ensure(c, ((size_t)kCloudMaxBlocks + 1) * kCloudWords * sizeof(double)));
-  const int N = c->N;
-  const int nblk = cloud_blocks(N);
-  double* part = c->d_cloud.get() + kCloudWords;
-  if (which == PFMPE_CLOUD_WEIGHTED) {
-    // the kept propagated set as get_particles(0) delivers it (d_xfer is written and read inside one blocking call
-    // by every user), weighted by the kept iteration's raw weights
-    RET(ensure_xfer(c));
-    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()));
-    const CloudArgs ca = cloud_args(c, which, ref);
-    visit_state(c, [&](auto s) {  // the dense set is in the compute type
-      using T = typename decltype(s)::T;
-      hipLaunchKernelGGL((k_cloud_partials<T, T, true>), dim3(nblk), dim3(kBlock), 0, c->stream, ca, (const T*)nullptr,
-                         part);
-    });
-  } else {
-    const CloudArgs ca = cloud_args(c, which, ref);
-    visit_state(c, [&](auto s) {
-      using SP = typename decltype(s)::SP;
-      hipLaunchKernelGGL((k_cloud_partials<typename decltype(s)::T, SP, false>), dim3(nblk), dim3(kBlock), 0, c->stream,
-                         ca, (const SP*)c->d_state[c->prior_idx].get(), part);
-    });
-  }
-  hipLaunchKernelGGL((k_cloud_final<double>), dim3(1), dim3(kCloudSegs * kCloudWords), 0, c->stream, part, nblk, c->d_cloud.get());
-  HIPCHK(c, hipGetLastError());
-  double r[kCloudWords];
-  HIPCHK(c, hipMemcpyAsync(r, c->d_cloud.get(), sizeof(r), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  RET(harvest_timing(c));  // (a weighted call's regeneration is bracketed like get_particles(0)'s)
-  cloud_epilogue(r, N, ref, out);
-  return PFMPE_OK;
-}
-
 int pfmpe_host_cloud_plan(const int32_t* N, int S, pfmpe_cloud_plan* plan, int32_t* total_blocks) {
   if (!N || !plan || !total_blocks || S < 1) return PFMPE_E_ARG;
   if (S > PFMPE_CLOUD_MAX_STREAMS) return PFMPE_E_CAP;
@@ -901,42 +842,30 @@ int pfmpe_host_cloud_plan(const int32_t* N, int S, pfmpe_cloud_plan* plan, int32
   return PFMPE_OK;
 }
 
-int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out) {
-  static_assert(PFMPE_CLOUD_MAX_STREAMS == kCloudMaxStreams, "stream capacity mismatch");
-  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+namespace {
+// The statistics of S checked entries, 1 <= S <= kCloudMaxStreams, on ctxs[0]'s stream: pfmpe_cloud_stats_multi and,
+// as a batch of one, pfmpe_cloud_stats.  The errors it can raise itself begin with `who`.
+int cloud_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out, const std::string& who) {
   pfmpe_ctx* c0 = ctxs[0];
-  if (!in || !out) return fail(c0, PFMPE_E_ARG, "cloud_stats_multi: null in/out");
-  if (S > PFMPE_CLOUD_MAX_STREAMS)
-    return fail(c0, PFMPE_E_CAP, "cloud_stats_multi: S exceeds PFMPE_CLOUD_MAX_STREAMS");
   // the distinct contexts in order of first appearance (ctxs[0] first), and which of them have a WEIGHTED entry
   std::vector<pfmpe_ctx*> distinct;
   std::vector<char> weighted;
   int32_t Ns[PFMPE_CLOUD_MAX_STREAMS];
   for (int s = 0; s < S; ++s) {
     pfmpe_ctx* c = ctxs[s];
-    const std::string at = "cloud_stats_multi: stream " + std::to_string(s) + ": ";
-    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
-    if (c->device != c0->device || c->state_dtype != c0->state_dtype)
-      return fail(c0, PFMPE_E_ARG, at + "device and state type must match ctxs[0]");
-    const int which = in[s].which;
-    if (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR) return fail(c0, PFMPE_E_ARG, at + "bad which");
-    for (int q = 0; q < 12; ++q)
-      if (!std::isfinite(in[s].ref_pose[q])) return fail(c0, PFMPE_E_ARG, at + "non-finite reference pose");
-    if (!c->has_prior) return fail(c0, PFMPE_E_STATE, at + "no particle set");
-    if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c0, PFMPE_E_STATE, at + "weighted: no step yet");
     size_t m = 0;
     while (m < distinct.size() && distinct[m] != c) ++m;
     if (m == distinct.size()) {
       distinct.push_back(c);
       weighted.push_back(0);
     }
-    if (which == PFMPE_CLOUD_WEIGHTED) weighted[m] = 1;
+    if (in[s].which == PFMPE_CLOUD_WEIGHTED) weighted[m] = 1;
     Ns[s] = c->N;
   }
   pfmpe_cloud_plan plan[PFMPE_CLOUD_MAX_STREAMS];
   int32_t total = 0;
   if (pfmpe_host_cloud_plan(Ns, S, plan, &total) != PFMPE_OK)
-    return fail(c0, PFMPE_E_STATE, "cloud_stats_multi: a context without particles");
+    return fail(c0, PFMPE_E_STATE, who + ": a context without particles");
   RET(set_device(c0));
   // the scratch before any member's ordering state changes: pinned image (head, descriptors, result rows) once,
   // device image + partial rows grown on demand (nothing of an earlier batch is pending: the call is blocking)
@@ -955,7 +884,7 @@ int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in*
     if (!weighted[m]) continue;
     if (c != c0) RET(set_device(c));
     if (const int r_ = dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()))
-      return c == c0 ? r_ : fail(c0, r_, "cloud_stats_multi: " + c->err);
+      return c == c0 ? r_ : fail(c0, r_, who + ": " + c->err);
   }
   // every member's work so far, that regeneration included, is ordered before the batch (a context that appears
   // twice once); a failure from here on gives the members their ordering state back (the leader's own was set by
@@ -992,16 +921,54 @@ int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in*
                      (const double*)part, (double*)(hd_img + kRowOff));
   HIPCHK(c0, hipGetLastError());
   if (hipStreamSynchronize(c0->stream) != hipSuccess)
-    return fail(c0, PFMPE_E_HIP, "cloud_stats_multi: stream synchronise failed");
+    return fail(c0, PFMPE_E_HIP, who + ": stream synchronise failed");
   members.commit();  // nothing of the batch is pending: no member needs a fence
   for (pfmpe_ctx* c : distinct)  // (as every single call ends: the brackets of sampled frames still pending)
-    if (const int r_ = harvest_timing(c)) return c == c0 ? r_ : fail(c0, r_, "cloud_stats_multi: " + c->err);
+    if (const int r_ = harvest_timing(c)) return c == c0 ? r_ : fail(c0, r_, who + ": " + c->err);
   for (int s = 0; s < S; ++s) {
     double r[kCloudWords];
     std::memcpy(r, hrow + (size_t)kCloudWords * s, sizeof(r));
     cloud_epilogue(r, ctxs[s]->N, in[s].ref_pose, &out[s]);
   }
   return PFMPE_OK;
+}
+}  // namespace
+
+int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_out* out) {
+  if (!c) return PFMPE_E_ARG;
+  if (!ref || !out || (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR))
+    return fail(c, PFMPE_E_ARG, "cloud_stats: bad arguments");
+  for (int q = 0; q < 12; ++q)
+    if (!std::isfinite(ref[q])) return fail(c, PFMPE_E_ARG, "cloud_stats: non-finite reference pose");
+  if (!c->has_prior) return fail(c, PFMPE_E_STATE, "cloud_stats: no particle set");
+  if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_stats(weighted): no step yet");
+  pfmpe_cloud_in e{};
+  std::memcpy(e.ref_pose, ref, sizeof(e.ref_pose));
+  e.which = which;
+  return cloud_run(&c, 1, &e, out, "cloud_stats");
+}
+
+int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out) {
+  static_assert(PFMPE_CLOUD_MAX_STREAMS == kCloudMaxStreams, "stream capacity mismatch");
+  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+  pfmpe_ctx* c0 = ctxs[0];
+  if (!in || !out) return fail(c0, PFMPE_E_ARG, "cloud_stats_multi: null in/out");
+  if (S > PFMPE_CLOUD_MAX_STREAMS)
+    return fail(c0, PFMPE_E_CAP, "cloud_stats_multi: S exceeds PFMPE_CLOUD_MAX_STREAMS");
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = ctxs[s];
+    const std::string at = "cloud_stats_multi: stream " + std::to_string(s) + ": ";
+    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
+    if (c->device != c0->device || c->state_dtype != c0->state_dtype)
+      return fail(c0, PFMPE_E_ARG, at + "device and state type must match ctxs[0]");
+    const int which = in[s].which;
+    if (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR) return fail(c0, PFMPE_E_ARG, at + "bad which");
+    for (int q = 0; q < 12; ++q)
+      if (!std::isfinite(in[s].ref_pose[q])) return fail(c0, PFMPE_E_ARG, at + "non-finite reference pose");
+    if (!c->has_prior) return fail(c0, PFMPE_E_STATE, at + "no particle set");
+    if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c0, PFMPE_E_STATE, at + "weighted: no step yet");
+  }
+  return cloud_run(ctxs, S, in, out, "cloud_stats_multi");
 }
 int pfmpe_host_assoc_summary(const uint32_t* votes, int M, int B, pfmpe_assoc_out* out) {
   if (!votes || !out || M < 1 || M > kMaxMarkers || B < 0) return PFMPE_E_ARG;

@@ -5,8 +5,9 @@ pfmpe_cloud_stats_multi, for S = 1, 4, 16, 64 contexts of C2 size (100,000 fp32 
 Both routes are blocking, so each is timed on the host around the calls, through ctypes with the argument arrays
 built ahead: 5 warm-ups, then the median of 200 repetitions with the 10th and 90th percentiles, the two routes
 alternating within one process.  Then the batch alone, back to back ("alone": a loop of batches, whose members have no
-work on their own streams to be ordered after).  Route (a) is the baseline: the single call, whose kernels the batch
-leaves as they were.  Run it on an otherwise idle device.  Prints one row per case and one JSON line; no ratio is
+work on their own streams to be ordered after).  Route (a) is S batches of one: the single call runs the batch's
+kernels and host path with one entry (until it did, route (a) was a pair of kernels of its own; DESIGN.md §4.11a has
+those figures).  Run it on an otherwise idle device.  Prints one row per case and one JSON line; no ratio is
 required (exit status 0 unless the two routes disagree).
 
     python scripts/cloud_multi_time.py [--cases C2:1,C2:4,C2:16,C2:64,C5:4] [--warmup 5] [--reps 200]

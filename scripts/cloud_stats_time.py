@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time pfmpe_cloud_stats(POSTERIOR) against the route it replaces, pfmpe_get_particles(1) (the N x 12 doubles a
-host-side reduction would start from), after one step at the C2, C5 and C4 sizes.
+host-side reduction would start from), after one step at the C2, C5 and C4 sizes; pfmpe_cloud_stats(WEIGHTED), which
+regenerates the kept set first, is timed beside it.
 
 Both calls are blocking, so each is timed on the host around the call: 5 warm-up calls, then the median of 20.  The
 read-back writes into one preallocated buffer (no page faults of a fresh array in the timed calls).  Run it on an
@@ -66,16 +67,19 @@ def main():
                 eng._chk(eng.lib.pfmpe_get_particles(eng.ctx, 1, bp))
 
             t_stats = median_ms(lambda: eng.cloud_stats(pf.CLOUD_POSTERIOR, ref), args.warmup, args.reps)
+            t_weighted = median_ms(lambda: eng.cloud_stats(pf.CLOUD_WEIGHTED, ref), args.warmup, args.reps)
             t_read = median_ms(read_back, args.warmup, args.reps)
             cs = eng.cloud_stats(pf.CLOUD_POSTERIOR, ref)
         finally:
             eng.close()
         floor_ms = cfg.N * BYTES[state] / HBM_BYTES_PER_S * 1e3
         rows.append({"config": name, "N": cfg.N, "state_bytes": BYTES[state], "resampled": int(out.resampled),
-                     "cloud_stats_ms": t_stats, "get_particles_ms": t_read, "byte_floor_ms": floor_ms,
+                     "cloud_stats_ms": t_stats, "cloud_stats_weighted_ms": t_weighted, "get_particles_ms": t_read,
+                     "byte_floor_ms": floor_ms,
                      "ess": cs["ess"], "sigma_trans": float(np.sqrt(np.trace(cs["cov"][:3, :3]))),
                      "sigma_rot": float(np.sqrt(np.trace(cs["cov"][3:, 3:])))})
-        print(f"{name}: N={cfg.N} {BYTES[state]} B/particle  cloud_stats {t_stats:.3f} ms  "
+        print(f"{name}: N={cfg.N} {BYTES[state]} B/particle  cloud_stats {t_stats:.4f} ms  "
+              f"weighted {t_weighted:.4f} ms  "
               f"get_particles(1) {t_read:.3f} ms  byte floor {floor_ms:.4f} ms", flush=True)
     print(json.dumps({"cloud_stats_time": rows}))
     return 0 if all(r["cloud_stats_ms"] < r["get_particles_ms"] for r in rows) else 1

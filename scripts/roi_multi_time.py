@@ -6,7 +6,9 @@ Both routes are blocking, so each is timed on the host around the calls, through
 built ahead: 5 warm-ups, then the median of 200 repetitions, the two routes alternating within one process.  Then the
 batch alone, back to back ("alone": a loop of batches, whose members have no work on their own streams to be ordered
 after), and a pass with PFMPE_OPT_TIMING on that reads the PFMPE_K_ROI device time of both routes (route (a): summed
-over the S contexts).  Run it on an otherwise idle device.  Prints one row per case and one JSON line; exits non-zero unless the
+over the S contexts).  Route (a) is S batches of one: the single call runs the batch's kernels and host path with one
+stream (until it did, route (a) was a pair of kernels of its own and a copy back; DESIGN.md §4.14 has those figures).
+Run it on an otherwise idle device.  Prints one row per case and one JSON line; exits non-zero unless the
 batch is faster than the sequential calls for every S >= 4.
 
     python scripts/roi_multi_time.py [--cases C2:1,C2:4,C2:16,C5:4] [--warmup 5] [--reps 200]

@@ -1,4 +1,4 @@
-"""The twist of the cloud statistics (pfmpe_host_pose_twist: the code k_cloud_partials runs per particle) on the CPU:
+"""The twist of the cloud statistics (pfmpe_host_pose_twist: the code k_cloud_multi runs per particle) on the CPU:
 against the oracle's logarithmMap / exponentialMap, at the branch switches, and the binding's layout."""
 import ctypes
 

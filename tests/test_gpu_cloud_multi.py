@@ -5,8 +5,9 @@ A batch entry returns the bytes of its own single call: every comparison with pf
 larger than the 1,024-block grid (the entry's own grid stride) next to small ones, priors in particle order and read
 through owner indices, a context in several entries, reversed order, S = 1 and S = 64, members whose latest work is on
 another stream, a degenerate entry beside normal ones, repeatability and freedom from side effects, and every
-argument error.  One entry per state is also held against the numpy restatement (tests/cloud_ref.py) at that file's
-tolerance."""
+argument error.  The single call is the batch of one (it shares the leader's batch scratch, which has a test), so the
+batch is also held against the numpy restatement (tests/cloud_ref.py) at that file's tolerance: one entry per state,
+and every entry of one mixed batch."""
 import ctypes as C
 import functools
 
@@ -143,6 +144,59 @@ def test_grid_stride_and_owner_gather(state):
         equals_singles([(o, which) for which in (P, W) for o in objs[::-1]], (state, "large entry last"))
     finally:
         close(objs)
+
+
+def test_mixed_batch_against_numpy():
+    """One mixed batch held against the numpy restatement on each member's own read-backs, not against the single
+    call: both sets of one context, a second context of another N, and a context twice with two reference poses
+    (the default one and a particle of its own set, so both lie inside the cloud).  cloud_ref.check's 1e-9 rule
+    holds with room: the sums' rounding is at most N * 2^-53 = 5e-13 at N = 4,097."""
+    objs = [Obj(i, N, pf.STATE_F32) for i, N in enumerate((1000, 4097, 257))]
+    A, B, Cc = objs
+    try:
+        for o in objs:
+            o.step(0)
+        sets = {o.i: {W: (o.eng.get_particles(0), o.eng.get_weights()), P: (o.eng.get_particles(1), None)}
+                for o in objs}
+        own = sets[Cc.i][P][0][-1].reshape(12).copy()
+        entries = [(A, W, A.ref()), (A, P, A.ref()), (B, W, B.ref()), (Cc, P, Cc.ref()), (Cc, P, own)]
+        got = raw_batch(entries)
+        assert len(set(got)) == len(got)
+        for (o, which, ref), g in zip(entries, got):
+            poses, w = sets[o.i][which]
+            cloud_ref.check(as_dict(g), cloud_ref.stats(poses, w, ref))
+    finally:
+        close(objs)
+
+
+@pytest.mark.parametrize("state", ["f32", "f16"])
+def test_single_and_batch_share_scratch(state):
+    """The single call is a batch of one in the leader's batch scratch: a batch of three entries (the large context,
+    the small one, the large one again), the small context's single calls, the large one's, then the batch again.
+    Every record is the one a fresh pair of engines in the same state returns as its first statistics call."""
+    made = []
+
+    def fresh():
+        pair = [Obj(0, 257, STATES[state]), Obj(1, 4097, STATES[state])]
+        made.extend(pair)
+        for o in pair:
+            o.step(0)
+        return pair
+
+    def entries(small, large):
+        return [(large, W), (small, P), (large, P)]
+
+    try:
+        want_batch = raw_batch(entries(*fresh()))
+        want = {(i, which): fresh()[i].single(which) for i in (0, 1) for which in (W, P)}
+        small, large = fresh()
+        assert raw_batch(entries(small, large)) == want_batch
+        for o in (small, large):
+            for which in (W, P):
+                assert o.single(which) == want[o.i, which], (o.N, which)
+        assert raw_batch(entries(small, large)) == want_batch
+    finally:
+        close(made)
 
 
 def test_order_and_membership():

@@ -218,3 +218,57 @@ def test_errors():
         assert eng.cloud_stats(pf.CLOUD_POSTERIOR, ref=prior[0])["n"] == 1000  # and the context still works
     finally:
         eng.close()
+
+
+def test_error_texts():
+    """Every validation failure of the single call returns its code and its exact last-error text (the strings are
+    copied from the source of the version whose single call had a host path of its own), in the order of the checks:
+    arguments, reference pose, particle set, kept set.  The output record is untouched, and after each failure the
+    context steps and both of its statistics agree with numpy."""
+    N = 1000
+    st = _stream(N, 7)
+    prior = st.prior(fast=True)
+    good = np.ascontiguousarray(prior[0], dtype=np.float64).reshape(12)
+    nan_ref, inf_ref = good.copy(), good.copy()
+    nan_ref[7] = np.nan
+    inf_ref[0] = -np.inf
+    dp = ctypes.POINTER(ctypes.c_double)
+    W, P = pf.CLOUD_WEIGHTED, pf.CLOUD_POSTERIOR
+    ARGS, REF = "cloud_stats: bad arguments", "cloud_stats: non-finite reference pose"
+    NO_SET, NO_STEP = "cloud_stats: no particle set", "cloud_stats(weighted): no step yet"
+
+    def fails(eng, which, ref, code, text, null_out=False):
+        out = _capi.CloudOut()
+        ctypes.memset(ctypes.byref(out), 0xA5, ctypes.sizeof(out))
+        rc = eng.lib.pfmpe_cloud_stats(eng.ctx, which, dp() if ref is None else ref.ctypes.data_as(dp),
+                                       None if null_out else ctypes.byref(out))
+        assert (rc, eng.last_error()) == (code, text)
+        assert bytes(out) == b"\xa5" * ctypes.sizeof(out)
+
+    def works(eng, f):
+        _check_both(eng, eng.step(_frame(eng, st.frames[f], f)))
+
+    # a context without particles: the argument checks come first, then the reference pose, then the state
+    for which, ref, code, text in ((P, None, pf.E_ARG, ARGS), (3, good, pf.E_ARG, ARGS), (P, nan_ref, pf.E_ARG, REF),
+                                   (P, good, pf.E_STATE, NO_SET), (W, good, pf.E_STATE, NO_SET)):
+        eng = make_engine(N, st.markers, st.K, pf.STATE_F32, pf.RNG_PHILOX)
+        try:
+            fails(eng, which, ref, code, text)
+            eng.set_prior(prior)
+            works(eng, 0)
+        finally:
+            eng.close()
+    eng = make_engine(N, st.markers, st.K, pf.STATE_F32, pf.RNG_PHILOX)
+    try:
+        assert eng.lib.pfmpe_cloud_stats(None, P, good.ctypes.data_as(dp), ctypes.byref(_capi.CloudOut())) == pf.E_ARG
+        eng.set_prior(prior)
+        fails(eng, W, good, pf.E_STATE, NO_STEP)
+        works(eng, 0)
+        cases = [(P, None, pf.E_ARG, ARGS, False), (W, good, pf.E_ARG, ARGS, True), (2, good, pf.E_ARG, ARGS, False),
+                 (-1, good, pf.E_ARG, ARGS, False), (W, nan_ref, pf.E_ARG, REF, False),
+                 (P, inf_ref, pf.E_ARG, REF, False)]
+        for f, (which, ref, code, text, null_out) in enumerate(cases, start=1):
+            fails(eng, which, ref, code, text, null_out)
+            works(eng, f)
+    finally:
+        eng.close()

@@ -4,7 +4,8 @@ Every box of a batch must be the single call's, the host twin's (pfmpe_host_pred
 oracle's: rectangles equal, bbox bit patterns equal, for every state type, particle counts on both sides of every
 block and wave boundary (100,000 particles: 391 partials, a second pass of the per-stream reduction), priors in
 particle order and deferred (owner indices), members whose latest work is on another stream, and every argument
-error."""
+error.  The single call is the batch of one: its error texts, its timing bracket and the scratch it shares with the
+batches its context leads are checked here too."""
 import ctypes as C
 
 import numpy as np
@@ -206,6 +207,111 @@ def test_timing_slot():
         assert all(n == 0 for k, (n, _) in enumerate(lead) if k != pf.K_ROI)
     finally:
         close(objs)
+
+
+def test_single_timing_slot():
+    """the single call's launches are one PFMPE_K_ROI bracket on its context, and none with the timing option off"""
+    o = Obj(0, 3000, 5, pf.STATE_F32)
+    try:
+        for timing in (1, 0):
+            o.eng.set_option(pf.OPT_TIMING, timing)
+            o.eng.reset_kernel_stats()
+            o.single(0)
+            stats = list(o.eng.kernel_stats().values())
+            assert len(stats) == 9 == _capi.K_COUNT
+            assert all(n == 0 for k, (n, _) in enumerate(stats) if k != pf.K_ROI)
+            if timing:
+                assert stats[pf.K_ROI][0] == 1 and stats[pf.K_ROI][1] > 0.0
+            else:
+                assert stats[pf.K_ROI][0] == 0 and stats[pf.K_ROI][1] == 0.0
+    finally:
+        close([o])
+
+
+@pytest.mark.parametrize("state", ["f32", "f16"])
+def test_single_and_batch_share_scratch(state):
+    """The single call is a batch of one in its context's batch scratch: a batch of three led by the large context, the
+    small context's single call, the large one's, then the batch again.  Every box is the one a fresh set of engines
+    in the same state returns as its first ROI call."""
+    made = []
+
+    def fresh():
+        objs = [Obj(0, 4097, 5, STATES[state]), Obj(1, 257, 5, STATES[state]), Obj(2, 1000, 12, STATES[state])]
+        made.extend(objs)
+        for o in objs:
+            o.step(0)
+        return objs
+
+    try:
+        want_batch = batch(fresh(), 1)
+        want_single = [fresh()[i].single(1) for i in (0, 1)]
+        objs = fresh()
+        for rnd in (0, 1):
+            for g, w in zip(batch(objs, 1), want_batch):
+                same(g, w, (state, "batch", rnd))
+            if rnd == 0:
+                for i in (1, 0):
+                    same(objs[i].single(1), want_single[i], (state, "single", objs[i].N))
+    finally:
+        close(made)
+
+
+def test_single_error_texts():
+    """Every validation failure of the single call returns its code and its exact last-error text (the strings are
+    copied from the source of the version whose single call had a host path of its own), in the order of the checks:
+    in / out, model and prior, image size.  The output is untouched, and after each failure the context steps and its
+    ROI is the host twin's and the oracle's."""
+    lib = pf.load()
+    NULLS, STATE, SIZE = ("predict_roi: null in/out", "predict_roi: set_model and set_prior first",
+                          "predict_roi: bad image size")
+
+    def fails(o, code, text, size=None, null_in=False, null_out=False):
+        rin = o.roi_in(0)
+        if size is not None:
+            rin.image_w, rin.image_h = size
+        out = _capi.RoiOut(-7, -7, -7, -7, (C.c_double * 4)(-7.0, -7.0, -7.0, -7.0))
+        rc = lib.pfmpe_predict_roi(o.eng.ctx, None if null_in else C.byref(rin), None if null_out else C.byref(out))
+        assert (rc, o.eng.last_error()) == (code, text)
+        assert [out.x, out.y, out.width, out.height] + list(out.bbox) == [-7] * 8
+
+    def works(o, f):
+        o.step(f)
+        host, oracle = o.host_and_oracle(f + 1)
+        got = o.single(f + 1)
+        same(got, host, ("host", f))
+        same(got, oracle, ("oracle", f))
+
+    made = []
+    try:
+        # without a prior, and without a model: in / out are looked at first, the image size last
+        for model in (True, False):
+            for kw, code, text in (({"null_in": True}, pf.E_ARG, NULLS), ({"null_out": True}, pf.E_ARG, NULLS),
+                                   ({}, pf.E_STATE, STATE), ({"size": (0, 480)}, pf.E_STATE, STATE)):
+                o = Obj(4, 300, 5, pf.STATE_F32, with_prior=False)
+                made.append(o)
+                if not model:
+                    o.eng.close()
+                    o.eng = pf.Engine(device=0, max_particles=o.N, state_dtype=pf.STATE_F32)
+                fails(o, code, text, **kw)
+                if not model:
+                    o.eng.set_model(o.markers, o.K)
+                    prm = pf.default_params()
+                    prm.rng_mode = pf.RNG_PHILOX
+                    o.eng.set_params(prm)
+                    fails(o, pf.E_STATE, STATE)
+                o.eng.set_prior(syn.initial_prior_fast(syn.to44(o.st.frames[0].current_pose), o.N, seed=11))
+                works(o, 0)
+        A = Obj(0, 300, 5, pf.STATE_F32, n_frames=7)
+        made.append(A)
+        out = _capi.RoiOut()
+        assert lib.pfmpe_predict_roi(None, C.byref(A.roi_in(0)), C.byref(out)) == pf.E_ARG
+        cases = [({"null_in": True}, NULLS), ({"null_out": True}, NULLS), ({"size": (0, 480)}, SIZE),
+                 ({"size": (752, -1)}, SIZE), ({"size": (0, 0), "null_out": True}, NULLS)]
+        for f, (kw, text) in enumerate(cases):
+            fails(A, pf.E_ARG, text, **kw)
+            works(A, f)
+    finally:
+        close(made)
 
 
 def test_errors_leave_out_untouched():
