@@ -542,6 +542,64 @@ int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in*
 typedef struct { int32_t first_block, blocks; } pfmpe_cloud_plan;   /* 8 bytes */
 int pfmpe_host_cloud_plan(const int32_t* N, int S, pfmpe_cloud_plan* plan, int32_t* total_blocks);
 
+/* The cloud's mass and statistics per hypothesis.  pfmpe_top_particles names the K best distinct hypotheses of a frame
+ * (the winner and the mirror solution of a near-symmetric LED set); pfmpe_cloud_stats describes the whole cloud with
+ * one mean and one covariance, which between two modes describe neither.  pfmpe_cloud_modes assigns every particle to
+ * the nearest of K seed poses (from pfmpe_top_particles, or the caller's) and returns the record of pfmpe_cloud_stats
+ * per mode: how much of the posterior sits in each hypothesis, and how wide each one is.  No per-particle array moves
+ * to the host unless the caller asks for mode_of.
+ *
+ * Set: `which` as for pfmpe_cloud_stats: WEIGHTED the rows of pfmpe_get_particles(0) with pfmpe_get_weights,
+ * POSTERIOR the rows of pfmpe_get_particles(1) with unit weights.
+ * Distance of particle pose p to seed s, in fp64 on the 12-double rows, every product and sum rounded on its own, left
+ * to right, with d2 and tr exactly those of pfmpe_top_particles' predicate for the pair (p, s):
+ *   d2 = (tp0-ts0)^2 + (tp1-ts1)^2 + (tp2-ts2)^2;   tr = sum of Rp[r][c]*Rs[r][c] over the nine entries, row-major
+ *   a = d2 * it2,  b = (3.0 - tr) * ir2,  dist = a + b
+ *   it2 = trans_scale > 0 ? 1 / (trans_scale * trans_scale) : 0, ir2 likewise from rot_scale (formed once on the host)
+ * 3 - tr is 2 (1 - cos theta) ~ theta^2 of the relative rotation; rounding may leave it slightly negative, which is
+ * allowed.  A scale of 0 takes its part out of the distance.
+ * Assignment: best = +inf, mode = PFMPE_MODE_NONE; for k = 0 .. K-1: if (dist_k < best) { best = dist_k; mode = k; },
+ * so the lowest k wins a tie; a NaN or infinite dist_k (of either sign) never wins.  With max_dist > 0 a particle with
+ * !(best <= max_dist) becomes PFMPE_MODE_NONE.
+ * Records: out[k].stats is the record pfmpe_cloud_stats defines, taken over the members of mode k alone with
+ * T_ref = seeds[k]: every sum runs in the order pfmpe_cloud_stats uses for this N with the non-members skipped, n is the
+ * member count, and a mode without weight (no members, or members of weight 0) has the degenerate record.  out[K] is the
+ * same record of the PFMPE_MODE_NONE particles about seeds[0]; its mean_pose is where a caller would put the next
+ * seed.  share = stats.wsum / (out[0].stats.wsum + ... + out[K].stats.wsum, added in index order), 0 if that sum is
+ * 0.  mode_of, when given, receives every particle's mode (N bytes).
+ * Hence: with K = 1, max_dist = 0 and finite poses, out[0].stats is byte for byte what
+ * pfmpe_cloud_stats(ctx, which, seeds, .) writes, share is 1 and out[1] is the degenerate record with n = 0; a
+ * repeated call returns the same bytes; moving another seed without changing any particle's mode leaves a mode's
+ * record unchanged; the member counts sum to N; for POSTERIOR stats.wsum == stats.n exactly.
+ *
+ * Blocking; runs on the context's stream; reads only.  Not timed by PFMPE_OPT_TIMING (regenerating the WEIGHTED set
+ * counts as aux).  The records come from the kernels and the host path of pfmpe_cloud_stats_multi: one batch of K + 1
+ * entries on this context, each restricted to its mode.  DESIGN.md §4.16.
+ * Errors, all checked before anything is staged or launched (out and mode_of stay untouched): PFMPE_E_ARG for a NULL
+ * ctx, seeds or out, a bad `which`, K outside 1..PFMPE_MODES_MAX, a non-finite seed, a negative, NaN or infinite scale
+ * or max_dist, both scales 0; PFMPE_E_STATE as pfmpe_cloud_stats.  The text begins "cloud_modes: ". */
+#define PFMPE_MODES_MAX 16     /* largest K */
+#define PFMPE_MODE_NONE 255    /* mode_of value of a particle no seed takes */
+typedef struct {
+  double trans_scale;  /* m,   >= 0, finite; 0: translation does not count            */
+  double rot_scale;    /* rad, >= 0, finite; 0: rotation does not count (not both 0)   */
+  double max_dist;     /* >= 0, finite; 0: no gate                                     */
+} pfmpe_modes_params;  /* 24 bytes */
+typedef struct {
+  pfmpe_cloud_out stats;  /* of the mode's members about its seed; stats.n = members   */
+  double share;           /* stats.wsum / (sum of all K + 1 wsum, in index order); 0 if that sum is 0 */
+} pfmpe_mode_out;         /* 488 bytes */
+void pfmpe_default_modes_params(pfmpe_modes_params* p);   /* 0.01, 0.05, 0 */
+int pfmpe_cloud_modes(pfmpe_ctx* ctx, int which, const double* seeds /* K x 12 */, int K,
+                      const pfmpe_modes_params* params /* NULL: defaults */,
+                      pfmpe_mode_out* out /* K + 1 */, uint8_t* mode_of /* N bytes, may be NULL */);
+/* host-only (no GPU, no context): the assignment alone, for N caller-given poses (N x 12), by the function the device
+ * runs.  mode_of: N bytes; counts, when given: the members of modes 0 .. K-1, then the PFMPE_MODE_NONE particles
+ * (they sum to N).  A non-finite pose is not an error: it has no mode.  PFMPE_E_ARG for the argument errors above,
+ * N < 0, a NULL mode_of or NULL poses with N > 0; the outputs are untouched then. */
+int pfmpe_host_cloud_assign(const double* poses, int64_t N, const double* seeds, int K,
+                            const pfmpe_modes_params* params, uint8_t* mode_of, int64_t* counts /* K + 1, may be NULL */);
+
 /* ------------------------------------------------------------- LED-blob association of the particle cloud */
 /* The reference keeps the correspondences of every particle (correspondencesVec, PE:2385-2445, read at PE:688); a
  * step reports the winner's only (pfmpe_frame_out.corr).  These calls derive every particle's pairs on the device

@@ -26,6 +26,7 @@ from ._capi import (  # noqa: F401
     DIAG_TAIL_MISS, INFO_TAIL_FALLBACKS, host_step_tail,
     CLOUD_MAX_STREAMS, CloudIn, CloudPlan, host_cloud_plan,
     TOP_MAX, TOP_POOL, TOP_BY_WEIGHT, TOP_BY_COUNT, TopParams, TopOut, default_top_params, host_top_suppress,
+    MODES_MAX, MODE_NONE, ModesParams, ModeOut, default_modes_params, host_cloud_assign,
 )
 
 __all__ = [

@@ -62,7 +62,10 @@ EXPORTED_SYMBOLS = (
     "pfmpe_step_refine", "pfmpe_step_refine_multi", "pfmpe_host_step_tail",
     "pfmpe_cloud_stats_multi", "pfmpe_host_cloud_plan",
     "pfmpe_default_top_params", "pfmpe_top_particles", "pfmpe_host_top_suppress",
+    "pfmpe_default_modes_params", "pfmpe_cloud_modes", "pfmpe_host_cloud_assign",
 )
+MODES_MAX = 16
+MODE_NONE = 255
 TOP_MAX = 1024
 TOP_POOL = 1024
 TOP_BY_WEIGHT, TOP_BY_COUNT = 0, 1
@@ -213,6 +216,23 @@ class CloudPlan(C.Structure):
         return {"first_block": self.first_block, "blocks": self.blocks}
 
 
+class ModesParams(C.Structure):
+    _fields_ = [("trans_scale", C.c_double), ("rot_scale", C.c_double), ("max_dist", C.c_double)]
+
+
+class ModeOut(C.Structure):
+    _fields_ = [("stats", CloudOut), ("share", C.c_double)]
+
+    def as_dict(self) -> dict:
+        d = self.stats.as_dict()
+        d["share"] = self.share
+        return d
+
+
+# the sizes include/pfmpe.h states (pfmpe_engine.hip asserts them on its side)
+assert C.sizeof(ModesParams) == 24 and C.sizeof(CloudOut) == 480 and C.sizeof(ModeOut) == 488
+
+
 class AssocIn(C.Structure):
     _fields_ = [("blobs", C.POINTER(C.c_double)), ("B", C.c_int32), ("bank_frame", C.c_int32)]
 
@@ -344,6 +364,10 @@ def load() -> C.CDLL:
                                     dp, dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
         "pfmpe_host_top_suppress": (I, [dp, C.c_int32, C.c_int32, D, D, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32)]),
+        "pfmpe_default_modes_params": (None, [C.POINTER(ModesParams)]),
+        "pfmpe_cloud_modes": (I, [P, I, dp, I, C.POINTER(ModesParams), C.POINTER(ModeOut), C.POINTER(C.c_uint8)]),
+        "pfmpe_host_cloud_assign": (I, [dp, I64, dp, I, C.POINTER(ModesParams), C.POINTER(C.c_uint8),
+                                        C.POINTER(I64)]),
         "pfmpe_default_refine_params": (None, [C.POINTER(RefineParams)]),
         "pfmpe_refine_poses": (I, [P, C.POINTER(AssocIn), C.POINTER(RefineParams), dp, C.POINTER(C.c_uint32), C.c_int32,
                                    C.POINTER(RefineOut), P, dp]),
@@ -875,6 +899,24 @@ class Engine:
         engines[0]._chk(engines[0].lib.pfmpe_cloud_stats_multi(ctxs, S, arr_in, arr_out))
         return [o.as_dict() for o in arr_out]
 
+    def cloud_modes(self, which: int, seeds, params=None, trans_scale=None, rot_scale=None, max_dist=None,
+                    want_mode_of: bool = True) -> tuple:
+        """The cloud's mass and statistics per hypothesis (pfmpe_cloud_modes): every particle of the set `which` goes
+        to the nearest of the K seeds (K x 12, or K 3x4 / 4x4 poses; from top_particles or the caller's).  Returns
+        (K + 1 dicts, mode_of): dict k is what cloud_stats returns for the members of mode k about seed k, with
+        "share", its part of the total weight; dict K describes the particles no seed takes (about seed 0).  mode_of:
+        every particle's mode (uint8, MODE_NONE for none), or None with want_mode_of false (nothing per particle
+        crosses the host link then).  params: a ModesParams, default pfmpe_default_modes_params; the keyword scales
+        override its fields."""
+        sd, prm = _modes_args(seeds, params, trans_scale, rot_scale, max_dist)
+        K = sd.shape[0]
+        out = (ModeOut * (K + 1))()
+        mode_of = np.empty(self.N, dtype=np.uint8) if want_mode_of else None
+        self._chk(self.lib.pfmpe_cloud_modes(
+            self.ctx, int(which), _dptr(sd), K, C.byref(prm), out,
+            mode_of.ctypes.data_as(C.POINTER(C.c_uint8)) if want_mode_of else None))
+        return [o.as_dict() for o in out], mode_of
+
     @staticmethod
     def _assoc_in(blobs, bank_frame):
         ai = AssocIn()
@@ -1253,6 +1295,42 @@ def host_top_suppress(poses, K: int, min_trans: float = 0.0, min_rot: float = 0.
     if rc != OK:
         raise PFError(rc, "host_top_suppress: bad arguments")
     return {"keep": keep[: n_out.value].copy(), "n_out": n_out.value, "n_examined": n_ex.value}
+
+
+def default_modes_params() -> ModesParams:
+    p = ModesParams()
+    load().pfmpe_default_modes_params(C.byref(p))
+    return p
+
+
+def _modes_args(seeds, params, trans_scale, rot_scale, max_dist):
+    """The seeds as a K x 12 array and a ModesParams of its own (params, or the defaults, with the overrides)."""
+    sd = np.asarray(seeds, dtype=np.float64)
+    if sd.ndim >= 2 and sd.shape[-2:] == (4, 4):
+        sd = sd.reshape(-1, 4, 4)[:, :3, :]
+    sd = np.ascontiguousarray(sd.reshape(-1, 12))
+    src = params if params is not None else default_modes_params()
+    prm = ModesParams(src.trans_scale, src.rot_scale, src.max_dist)
+    for name, v in (("trans_scale", trans_scale), ("rot_scale", rot_scale), ("max_dist", max_dist)):
+        if v is not None:
+            setattr(prm, name, float(v))
+    return sd, prm
+
+
+def host_cloud_assign(poses, seeds, params=None, trans_scale=None, rot_scale=None, max_dist=None) -> tuple:
+    """The assignment of cloud_modes on the host (pfmpe_host_cloud_assign), by the function the device runs, for N
+    poses (N x 12, any N): (mode_of (N uint8), counts (K + 1 int64: modes 0 .. K-1, then the particles without one))."""
+    p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+    sd, prm = _modes_args(seeds, params, trans_scale, rot_scale, max_dist)
+    K = sd.shape[0]
+    mode_of = np.empty(max(p.shape[0], 1), dtype=np.uint8)
+    counts = np.zeros(max(K, 0) + 1, dtype=np.int64)
+    rc = load().pfmpe_host_cloud_assign(_dptr(p), p.shape[0], _dptr(sd), K, C.byref(prm),
+                                        mode_of.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        counts.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != OK:
+        raise PFError(rc, "host_cloud_assign: bad arguments")
+    return mode_of[: p.shape[0]], counts
 
 
 def make_detect_images(images):

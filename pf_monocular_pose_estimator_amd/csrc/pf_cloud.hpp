@@ -1,6 +1,8 @@
-// pf_cloud.hpp — read-backs of the cloud: the weights (pfmpe_get_weights) and the cloud statistics
-// (pfmpe_cloud_stats, pfmpe_cloud_stats_multi).
+// pf_cloud.hpp — read-backs of the cloud: the weights (pfmpe_get_weights), the cloud statistics
+// (pfmpe_cloud_stats, pfmpe_cloud_stats_multi) and the statistics per hypothesis (pfmpe_cloud_modes).
 #pragma once
+#include <float.h>
+
 #include "pf_roi.hpp"  // roi_stream_of_block, k_roi_stage (the batch)
 #include "pf_state.hpp"
 #include "pf_wave.hpp"
@@ -101,12 +103,34 @@ struct CloudBatch {  // head of the batch's device image, the descriptors follow
 };
 struct CloudDesc {
   CloudArgs a;
-  const void* st;  // resident: the prior's storage (SP planes); dense: unused
-  int32_t dense, pad;
+  const void* st;          // resident: the prior's storage (SP planes); dense: unused
+  const uint8_t* mode_of;  // a filtered entry (pfmpe_cloud_modes): every particle's mode, k_cloud_assign's output
+  int32_t dense;
+  int32_t mode;            // a filtered entry reduces the particles with mode_of[n] == mode, in the entry's order
 };
+// Particle n of an entry as the statistics read it, for every kernel that reads an entry: a dense entry's row and its
+// weight widened as k_weights_export widens it; a resident entry's prior row through the owner indices and the fp16
+// anchor, exactly what k_export writes, with unit weight.  dense is wave-uniform.
+template <typename T, typename SP>
+__device__ __forceinline__ void cloud_load(const CloudArgs& ca, const SP* __restrict__ st, bool dense, int64_t n,
+                                           double* P, double& w) {
+  if (dense) {
+#pragma unroll
+    for (int q = 0; q < 12; ++q) P[q] = ca.dense[12 * n + q];
+    w = (double)((const T*)ca.w)[n];
+  } else {
+    const int64_t r = ca.owner ? (int64_t)ca.owner[n] : n;
+#pragma unroll
+    for (int q = 0; q < 12; ++q)
+      P[q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ca.ld)], (T)ca.anchor[q]);
+  }
+}
 static_assert(sizeof(CloudBatch) % sizeof(uint64_t) == 0 && sizeof(CloudDesc) % sizeof(uint64_t) == 0,
               "k_roi_stage copies 8-byte words");
-template <typename T, typename SP>
+// kFiltered (pfmpe_cloud_modes): the entry's sums run over its mode's members alone, in the same order; a non-member
+// costs its byte of mode_of and nothing else (no state load, no twist).  The unfiltered instances are the ones
+// pfmpe_cloud_stats and pfmpe_cloud_stats_multi launch: no part of the test is compiled into them.
+template <typename T, typename SP, bool kFiltered>
 __global__ __launch_bounds__(kBlock) void k_cloud_multi(const CloudBatch* __restrict__ hd,
                                                        const CloudDesc* __restrict__ descs,
                                                        double* __restrict__ part) {
@@ -124,17 +148,11 @@ __global__ __launch_bounds__(kBlock) void k_cloud_multi(const CloudBatch* __rest
   double mt = 0.0, mr = 0.0;
   const int64_t stride = (int64_t)nb * kBlock;  // the entry's own grid, not gridDim.x
   for (int64_t n = (int64_t)lb * kBlock + threadIdx.x; n < ca.N; n += stride) {
-    double P[12], w = 1.0;
-    if (dense) {
-#pragma unroll
-      for (int q = 0; q < 12; ++q) P[q] = ca.dense[12 * n + q];
-      w = (double)((const T*)ca.w)[n];
-    } else {
-      const int64_t r = ca.owner ? (int64_t)ca.owner[n] : n;
-#pragma unroll
-      for (int q = 0; q < 12; ++q)
-        P[q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ca.ld)], (T)ca.anchor[q]);
+    if constexpr (kFiltered) {
+      if ((int32_t)d.mode_of[n] != d.mode) continue;
     }
+    double P[12], w = 1.0;
+    cloud_load<T, SP>(ca, st, dense, n, P, w);
     double xi[6], wx[6];
     pose_twist(P, ca.ref, xi);
     acc[0] = acc[0] + w;
@@ -208,6 +226,95 @@ __global__ __launch_bounds__(kCloudSegs* kCloudWords) void k_cloud_multi_final(c
   if (sg == 0) {
     for (int s = 1; s < kCloudSegs; ++s) v = sum ? v + sh[s][q] : (sh[s][q] > v ? sh[s][q] : v);
     out[(size_t)e * kCloudWords + q] = v;
+  }
+}
+
+// ---- the cloud's mass and statistics per hypothesis (pfmpe_cloud_modes; the definition is in include/pfmpe.h): every
+// particle goes to its nearest seed, then the reduction above runs once per mode as a filtered entry.
+constexpr int kModesMax = 16;
+constexpr int kModeNone = 255;
+// The seeds and the scales as the distance uses them, formed once on the host: it2 = 1 / trans_scale^2 and
+// ir2 = 1 / rot_scale^2 (0 for a scale of 0).  A kernel argument: wave-uniform, read with scalar loads.
+struct ModeSeeds {
+  double seed[kModesMax][12];
+  double it2, ir2, max_dist;
+  int32_t K, pad;
+};
+inline double mode_inv2(double scale) { return scale > 0.0 ? 1.0 / (scale * scale) : 0.0; }
+// Distance of pose p to seed s: d2 and tr as top_near (pf_top.hpp) forms them, fp64 on the 12-double rows, every
+// product and sum rounded on its own, in the order written; the same function on both sides, so the device's
+// assignment equals pfmpe_host_cloud_assign's bit for bit.
+__host__ __device__ inline double mode_dist(const double* p, const double* s, double it2, double ir2) {
+#pragma clang fp contract(off)
+  const double dx = p[3] - s[3], dy = p[7] - s[7], dz = p[11] - s[11];
+  double d2 = dx * dx;
+  d2 = d2 + dy * dy;
+  d2 = d2 + dz * dz;
+  double tr = p[0] * s[0];
+  tr = tr + p[1] * s[1];
+  tr = tr + p[2] * s[2];
+  tr = tr + p[4] * s[4];
+  tr = tr + p[5] * s[5];
+  tr = tr + p[6] * s[6];
+  tr = tr + p[8] * s[8];
+  tr = tr + p[9] * s[9];
+  tr = tr + p[10] * s[10];
+  const double a = d2 * it2;
+  const double b = (3.0 - tr) * ir2;
+  return a + b;
+}
+// The nearest seed: the lowest k among equal distances; a NaN or infinite distance (of either sign: an infinite
+// rotation entry can give -inf) never wins; with a gate, a particle farther than max_dist from every seed has none.
+__host__ __device__ inline int mode_assign(const double* p, const ModeSeeds& ms) {
+  double best = (double)INFINITY;
+  int mode = kModeNone;
+  for (int k = 0; k < ms.K; ++k) {
+    const double dist = mode_dist(p, ms.seed[k], ms.it2, ms.ir2);
+    if (dist < best && dist >= -DBL_MAX) {
+      best = dist;
+      mode = k;
+    }
+  }
+  if (ms.max_dist > 0.0 && !(best <= ms.max_dist)) mode = kModeNone;
+  return mode;
+}
+// One lane per particle over cloud_blocks(N) blocks, grid-stride beyond: mode_of[n] = the mode of particle n of the
+// entry `d` (read as k_cloud_multi reads it), counts[k] += the members of mode k, counts[K] those without a mode.
+// Every output is order-free: a byte per particle, and integer adds (a wave counts a mode with one ballot, lane k
+// keeps mode k's count; the block's waves meet in LDS and each non-empty bin goes out with one device atomic, the
+// k_top_hist idiom).  The host clears counts before the launch.
+template <typename T, typename SP>
+__global__ __launch_bounds__(kBlock) void k_cloud_assign(const CloudDesc d, const ModeSeeds ms,
+                                                        uint8_t* __restrict__ mode_of, uint32_t* __restrict__ counts) {
+  __shared__ uint32_t bins[kModesMax + 1];
+  if (threadIdx.x <= kModesMax) bins[threadIdx.x] = 0u;
+  __syncthreads();
+  const CloudArgs& ca = d.a;
+  const bool dense = d.dense != 0;  // wave-uniform
+  const SP* __restrict__ st = (const SP*)d.st;
+  const int lane = lane_id();
+  uint32_t mine = 0u;  // lane k <= K: this wave's particles in bin k
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t n0 = (int64_t)blockIdx.x * kBlock; n0 < ca.N; n0 += stride) {  // block-uniform trips: ballots
+    const int64_t n = n0 + threadIdx.x;
+    int bin = -1;
+    if (n < ca.N) {
+      double P[12], w = 1.0;  // (the weight plays no part in the assignment)
+      cloud_load<T, SP>(ca, st, dense, n, P, w);
+      const int mode = mode_assign(P, ms);
+      mode_of[n] = (uint8_t)mode;
+      bin = mode == kModeNone ? ms.K : mode;
+    }
+    for (int k = 0; k <= ms.K; ++k) {
+      const uint32_t c = (uint32_t)__popcll(__ballot(bin == k));
+      mine += lane == k ? c : 0u;
+    }
+  }
+  if (mine) (void)__hip_atomic_fetch_add(bins + lane, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __syncthreads();
+  if ((int)threadIdx.x <= ms.K) {
+    const uint32_t x = bins[threadIdx.x];
+    if (x) (void)__hip_atomic_fetch_add(counts + threadIdx.x, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 

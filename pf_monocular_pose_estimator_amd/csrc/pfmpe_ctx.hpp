@@ -213,6 +213,10 @@ struct pfmpe_ctx : CtxQueue {
   // pinned, host-mapped image of the head + descriptors followed by the result rows of PFMPE_CLOUD_MAX_STREAMS entries
   Buf<unsigned char> d_cloudm;
   Buf<unsigned char, Mem::Mapped> h_cloudm;
+  // pfmpe_cloud_modes: the member counts of the K + 1 modes (kModesCountBytes), then a byte per particle, N rounded
+  // up to 4 (grown on demand, never shrunk); and the pinned block the counts are read back into
+  Buf<unsigned char> d_modes;
+  Buf<unsigned char, Mem::Pinned> h_modes;
   int num_cu = 0;
   bool coop = false;               // device supports cooperative launches
   int fused = 2;                   // PFMPE_OPT_FUSED: 2 flat one-launch (k_frame2), 1 tree (k_frame), 0 two launches

@@ -843,9 +843,22 @@ int pfmpe_host_cloud_plan(const int32_t* N, int S, pfmpe_cloud_plan* plan, int32
 }
 
 namespace {
-// The statistics of S checked entries, 1 <= S <= kCloudMaxStreams, on ctxs[0]'s stream: pfmpe_cloud_stats_multi and,
-// as a batch of one, pfmpe_cloud_stats.  The errors it can raise itself begin with `who`.
-int cloud_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out, const std::string& who) {
+// pfmpe_cloud_modes' batch: its S = K + 1 entries are one set of one context, entry s < K about seed s and restricted
+// to mode s, entry K about seed 0 and restricted to the particles without a mode.
+struct CloudModesRun {
+  ModeSeeds seeds;
+  uint8_t* mode_of;  // the caller's N bytes, or null
+};
+constexpr size_t kModesCountBytes = 256;  // the K + 1 member counts in front of pfmpe_ctx::d_modes' bytes
+static_assert((kModesMax + 1) * sizeof(uint32_t) <= kModesCountBytes && PFMPE_MODES_MAX == kModesMax &&
+                  PFMPE_MODE_NONE == kModeNone && kModesMax + 1 <= kCloudMaxStreams,
+              "the modes of a call are one batch");
+// The statistics of S checked entries, 1 <= S <= kCloudMaxStreams, on ctxs[0]'s stream: pfmpe_cloud_stats_multi, as a
+// batch of one pfmpe_cloud_stats and, with `modes`, pfmpe_cloud_modes (the assignment runs between the regeneration
+// and the reduction, and every entry reduces its mode's members: the same launches otherwise).  The errors it can
+// raise itself begin with `who`.
+int cloud_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out, const std::string& who,
+              const CloudModesRun* modes = nullptr) {
   pfmpe_ctx* c0 = ctxs[0];
   // the distinct contexts in order of first appearance (ctxs[0] first), and which of them have a WEIGHTED entry
   std::vector<pfmpe_ctx*> distinct;
@@ -875,6 +888,11 @@ int cloud_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_clo
   RET(c0->h_cloudm.ensure(c0, kRowOff + kCloudMaxStreams * kRowBytes));
   const size_t need = kRowOff + (size_t)total * kRowBytes;
   RET(c0->d_cloudm.grow(c0, need, kRowOff + (need - kRowOff) * 2));
+  if (modes) {
+    RET(c0->h_modes.ensure(c0, kModesCountBytes));
+    const size_t bytes = kModesCountBytes + (((size_t)c0->N + 3) & ~(size_t)3);
+    RET(c0->d_modes.grow(c0, bytes, bytes));
+  }
   for (size_t m = 0; m < distinct.size(); ++m)
     if (weighted[m]) RET(ensure_xfer(distinct[m]));
   // each WEIGHTED context's kept propagated set once, as its single call regenerates it: into its own d_xfer, on its
@@ -901,8 +919,9 @@ int cloud_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_clo
     CloudDesc& d = descs[s];
     d.a = cloud_args(c, in[s].which, in[s].ref_pose);
     d.dense = in[s].which == PFMPE_CLOUD_WEIGHTED;
-    d.pad = 0;
     d.st = d.dense ? nullptr : c->d_state[c->prior_idx].get();
+    d.mode_of = modes ? c0->d_modes.get() + kModesCountBytes : nullptr;
+    d.mode = s < S - 1 ? s : kModeNone;  // (read by a filtered entry only)
     hd->first[s] = plan[s].first_block;
   }
   hd->first[S] = total;
@@ -913,13 +932,32 @@ int cloud_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_clo
   const double* hrow = (const double*)(c0->h_cloudm.get() + kRowOff);
   hipLaunchKernelGGL((k_roi_stage<uint64_t>), dim3(1), dim3(kBlock), 0, c0->stream, (const uint64_t*)hd_img,
                      (uint64_t*)c0->d_cloudm.get(), stage_words);
+  uint32_t* d_count = (uint32_t*)c0->d_modes.get();
+  if (modes) {  // every entry reads the same set: entry 0's descriptor names it
+    HIPCHK(c0, hipMemsetAsync(d_count, 0, kModesCountBytes, c0->stream));
+    visit_state(c0, [&](auto s) {
+      hipLaunchKernelGGL((k_cloud_assign<typename decltype(s)::T, typename decltype(s)::SP>), dim3(cloud_blocks(c0->N)),
+                         dim3(kBlock), 0, c0->stream, descs[0], modes->seeds, c0->d_modes.get() + kModesCountBytes,
+                         d_count);
+    });
+  }
   visit_state(c0, [&](auto s) {
-    hipLaunchKernelGGL((k_cloud_multi<typename decltype(s)::T, typename decltype(s)::SP>), dim3(total), dim3(kBlock), 0,
-                       c0->stream, dhd, ddescs, part);
+    using T = typename decltype(s)::T;
+    using SP = typename decltype(s)::SP;
+    if (modes)
+      hipLaunchKernelGGL((k_cloud_multi<T, SP, true>), dim3(total), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
+    else
+      hipLaunchKernelGGL((k_cloud_multi<T, SP, false>), dim3(total), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
   });
   hipLaunchKernelGGL(k_cloud_multi_final, dim3(S), dim3(kCloudSegs * kCloudWords), 0, c0->stream, dhd,
                      (const double*)part, (double*)(hd_img + kRowOff));
   HIPCHK(c0, hipGetLastError());
+  if (modes) {
+    HIPCHK(c0, hipMemcpyAsync(c0->h_modes.get(), d_count, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, c0->stream));
+    if (modes->mode_of)
+      HIPCHK(c0, hipMemcpyAsync(modes->mode_of, c0->d_modes.get() + kModesCountBytes, (size_t)c0->N,
+                                hipMemcpyDeviceToHost, c0->stream));
+  }
   if (hipStreamSynchronize(c0->stream) != hipSuccess)
     return fail(c0, PFMPE_E_HIP, who + ": stream synchronise failed");
   members.commit();  // nothing of the batch is pending: no member needs a fence
@@ -928,11 +966,88 @@ int cloud_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_clo
   for (int s = 0; s < S; ++s) {
     double r[kCloudWords];
     std::memcpy(r, hrow + (size_t)kCloudWords * s, sizeof(r));
-    cloud_epilogue(r, ctxs[s]->N, in[s].ref_pose, &out[s]);
+    const int64_t n = modes ? (int64_t)((const uint32_t*)c0->h_modes.get())[s] : (int64_t)ctxs[s]->N;
+    cloud_epilogue(r, n, in[s].ref_pose, &out[s]);
   }
   return PFMPE_OK;
 }
+// the checks pfmpe_cloud_modes and pfmpe_host_cloud_assign share: K, the seeds, the parameters
+const char* modes_args_bad(const double* seeds, int K, const pfmpe_modes_params& p) {
+  if (K < 1 || K > PFMPE_MODES_MAX) return "K outside 1..PFMPE_MODES_MAX";
+  for (int q = 0; q < 12 * K; ++q)
+    if (!std::isfinite(seeds[q])) return "non-finite seed";
+  for (const double v : {p.trans_scale, p.rot_scale, p.max_dist})
+    if (!(v >= 0.0) || !std::isfinite(v)) return "a scale or max_dist is negative or not finite";
+  if (p.trans_scale == 0.0 && p.rot_scale == 0.0) return "both scales are 0";
+  return nullptr;
+}
+ModeSeeds mode_seeds(const double* seeds, int K, const pfmpe_modes_params& p) {
+  ModeSeeds ms{};
+  std::memcpy(ms.seed, seeds, (size_t)K * 12 * sizeof(double));
+  ms.it2 = mode_inv2(p.trans_scale);
+  ms.ir2 = mode_inv2(p.rot_scale);
+  ms.max_dist = p.max_dist;
+  ms.K = K;
+  return ms;
+}
 }  // namespace
+
+void pfmpe_default_modes_params(pfmpe_modes_params* p) {
+  if (!p) return;
+  p->trans_scale = 0.01;
+  p->rot_scale = 0.05;
+  p->max_dist = 0.0;
+}
+
+int pfmpe_cloud_modes(pfmpe_ctx* c, int which, const double* seeds, int K, const pfmpe_modes_params* params,
+                      pfmpe_mode_out* out, uint8_t* mode_of) {
+  static_assert(sizeof(pfmpe_modes_params) == 24 && sizeof(pfmpe_mode_out) == 488, "ABI");
+  if (!c) return PFMPE_E_ARG;
+  if (!seeds || !out || (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR))
+    return fail(c, PFMPE_E_ARG, "cloud_modes: bad arguments");
+  pfmpe_modes_params prm;
+  pfmpe_default_modes_params(&prm);
+  if (params) prm = *params;
+  if (const char* bad = modes_args_bad(seeds, K, prm)) return fail(c, PFMPE_E_ARG, std::string("cloud_modes: ") + bad);
+  if (!c->has_prior) return fail(c, PFMPE_E_STATE, "cloud_modes: no particle set");
+  if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_modes(weighted): no step yet");
+  CloudModesRun run{mode_seeds(seeds, K, prm), mode_of};
+  pfmpe_ctx* ctxs[kModesMax + 1];
+  pfmpe_cloud_in in[kModesMax + 1];
+  pfmpe_cloud_out stats[kModesMax + 1];
+  for (int s = 0; s <= K; ++s) {
+    ctxs[s] = c;
+    in[s] = pfmpe_cloud_in{};
+    std::memcpy(in[s].ref_pose, seeds + 12 * (s < K ? s : 0), sizeof(in[s].ref_pose));
+    in[s].which = which;
+  }
+  RET(cloud_run(ctxs, K + 1, in, stats, "cloud_modes", &run));
+  double total = 0.0;
+  for (int s = 0; s <= K; ++s) total = total + stats[s].wsum;
+  for (int s = 0; s <= K; ++s) {
+    out[s].stats = stats[s];
+    out[s].share = total > 0.0 ? stats[s].wsum / total : 0.0;
+  }
+  return PFMPE_OK;
+}
+
+int pfmpe_host_cloud_assign(const double* poses, int64_t N, const double* seeds, int K, const pfmpe_modes_params* params,
+                            uint8_t* mode_of, int64_t* counts) {
+  if (!seeds || N < 0 || (N > 0 && (!poses || !mode_of))) return PFMPE_E_ARG;
+  pfmpe_modes_params prm;
+  pfmpe_default_modes_params(&prm);
+  if (params) prm = *params;
+  if (modes_args_bad(seeds, K, prm)) return PFMPE_E_ARG;
+  const ModeSeeds ms = mode_seeds(seeds, K, prm);
+  int64_t cnt[kModesMax + 1] = {0};
+  for (int64_t n = 0; n < N; ++n) {
+    const int mode = mode_assign(poses + 12 * n, ms);
+    mode_of[n] = (uint8_t)mode;
+    cnt[mode == kModeNone ? K : mode] += 1;
+  }
+  if (counts) std::memcpy(counts, cnt, (size_t)(K + 1) * sizeof(int64_t));
+  return PFMPE_OK;
+}
 
 int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_out* out) {
   if (!c) return PFMPE_E_ARG;
