@@ -651,6 +651,86 @@ int pfmpe_assoc_stats(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, pfmpe
 int pfmpe_get_pairs(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, int64_t first, int32_t count,
                     uint32_t* corr, int32_t* n_corr);
 
+#define PFMPE_ASSOC_MAX_STREAMS 64
+#define PFMPE_ASSOC_MAX_LAUNCHES 16   /* 2 sets x 4 marker buckets x 2 pruning options */
+
+/* pfmpe_assoc_stats for S entries (the votes of every object of a frame, the numUAV loop, PE:89) as one launch
+ * sequence with one synchronise: one upload of all blob tables and descriptors, one memset of all bins, one votes
+ * launch per kernel instance the batch needs, one read-back into pinned memory, one synchronise.  out[s] and votes[s]
+ * are byte for byte what pfmpe_assoc_stats(ctxs[s], in[s].which, &in[s].blobs, &out[s], votes[s]) writes; votes = NULL
+ * or votes[s] = NULL: that table is not wanted, otherwise votes[s] holds M_s x (B_s + 1) words.  Every number is an
+ * integer sum, so this holds whatever grid the batch uses.
+ * Per entry: its own `which`, blob list and B.  M, the markers, K, tol, tol_PF, the pruning option, N and the prior's
+ * storage (particle order or owner indices, fp16 anchor) are its context's.  A context may appear in several entries
+ * (both sets of one object, or two blob lists); a context with at least one PROPAGATED entry regenerates its kept set
+ * once, on its own stream, and all its entries read that set.  Contexts: on one device, of one state type; pruning
+ * options and marker counts may differ (entries are grouped into launches by set, marker bucket and pruning option).
+ * Runs on ctxs[0]'s stream in scratch ctxs[0] owns (grown on demand, never shrunk); ctxs[0] receives the error text;
+ * work a member has pending elsewhere (its regeneration included) is ordered before the batch; blocking.  Reads only:
+ * no context's state, staged table use or statistics change, except that a member's regeneration counts as aux on that
+ * member.  Not timed by PFMPE_OPT_TIMING.  DESIGN.md §4.12a: design, resources and measured times.
+ * Everything is checked before anything is staged, regenerated or launched, and out / votes are untouched on an error:
+ * PFMPE_E_ARG (S < 1, NULL ctxs / in / out / ctxs[s], a device or state-type mismatch, a bad `which`, B < 0, NULL blobs
+ * with B > 0 and no bank frame, a bank frame out of range), PFMPE_E_CAP (S > PFMPE_ASSOC_MAX_STREAMS, an entry's B above
+ * its context's max_blobs, a blob table that exceeds the LDS, as the single call), PFMPE_E_STATE (an entry whose context
+ * has no model or no particle set, PROPAGATED before that context's first step); the text begins
+ * "assoc_stats_multi: stream <s>: ".  With ctxs == NULL or ctxs[0] == NULL: PFMPE_E_ARG and no text. */
+typedef struct {
+  pfmpe_assoc_in blobs;   /* this entry's list: host pointer + B, or a frame of ITS context's staged bank */
+  int32_t which;          /* PFMPE_ASSOC_PROPAGATED / PFMPE_ASSOC_POSTERIOR */
+  int32_t pad;
+} pfmpe_assoc_multi_in;   /* 24 bytes */
+int pfmpe_assoc_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_assoc_multi_in* in,
+                            pfmpe_assoc_out* out, uint32_t* const* votes);
+
+/* host-only (no GPU, no context): the layout of a pfmpe_assoc_stats_multi batch, which the call stages exactly.  Entry
+ * s has N[s] particles, M[s] LEDs, B[s] blobs, the set which[s] (NULL: all POSTERIOR) and the pruning option prune[s]
+ * (NULL: all on) in a batch of contexts of state_dtype.  Per entry: blocks = min(ceil(N / 256), 1024), the single
+ * call's grid; launch, the index of its launch (entries of one set, marker bucket (M = 5; <= 8; <= 12; <= 16) and
+ * pruning option share a launch; launches are numbered in order of first appearance); first_block, the running sum of
+ * blocks over the earlier entries of that launch; bins_offset, in words, of its M * B + M + 1 bins in the one device
+ * table (entries follow each other in index order, each start rounded up to 4 words); lds_votes = 1 when table + 16
+ * bytes + bins + the kernel's constants fit the workgroup's 64 KiB of LDS, the single call's rule, else 0 (its votes
+ * then go straight into the device table; M = 16 with B = 1024 is such an entry).  The size of an fp32 blob table
+ * depends on the blob positions (its cell grid): table_bytes[s] gives the built table's size, as the call does; with
+ * table_bytes = NULL the size of a table without a grid is taken (every fp64 table, every table with B = 0).
+ * total: the bins' word count, the launches, and the blocks of each launch's flat grid.
+ * PFMPE_E_ARG for a NULL N / M / B / plan / total, S < 1, a bad state_dtype, N < 1, M outside 1..PFMPE_MAX_MARKERS, B < 0,
+ * a bad which, a negative table size; PFMPE_E_CAP for S > PFMPE_ASSOC_MAX_STREAMS, B > PFMPE_MAX_BLOBS or a table that
+ * does not fit the LDS at all; the outputs are untouched then. */
+typedef struct {
+  int64_t bins_offset;
+  int32_t first_block, blocks, launch, lds_votes;
+} pfmpe_assoc_plan;         /* 24 bytes */
+typedef struct {
+  int64_t bins_words;
+  int32_t launches, pad;
+  int32_t launch_blocks[PFMPE_ASSOC_MAX_LAUNCHES];
+} pfmpe_assoc_plan_total;   /* 80 bytes */
+int pfmpe_host_assoc_plan(const int32_t* N, const int32_t* M, const int32_t* B, const int32_t* which /* may be NULL */,
+                          const int32_t* prune /* may be NULL */, const int32_t* table_bytes /* may be NULL */, int S,
+                          int state_dtype, pfmpe_assoc_plan* plan, pfmpe_assoc_plan_total* total);
+
+/* host-only (no GPU, no context): gating a row of pairs (the winner's, pfmpe_frame_out.corr) by the support a votes
+ * table (pfmpe_assoc_stats, M x (B + 1)) gives it, before the row goes to Gauss-Newton.  n is row 0's sum.  For row
+ * k = (led, blob) of corr, in order: v = votes[led-1][blob], and (mode_blob, mode_votes, second_votes) of that LED as
+ * pfmpe_host_assoc_summary forms them.  reason[k] has bit 0 set when !((double)v >= min_share * (double)n), bit 1 when
+ * mode_blob != blob, bit 2 when lead * (double)second_votes > (double)mode_votes.  A row with reason[k] == 0 is kept,
+ * in order; n_gated counts them.  fallback = 1 when n_gated < min_pairs: then gated is the input row unchanged (the
+ * first n_corr pairs, zero padded) and the caller may skip Gauss-Newton; otherwise gated holds the kept rows and
+ * zeros.  Defaults: min_share 0.5, lead 2.0, min_pairs 4 (the reference's min_num_leds_detected_,
+ * pose_estimator.h:104).  reason[k] is 0 for k >= n_corr.
+ * PFMPE_E_ARG for a NULL votes / corr / gated / out, M outside 1..PFMPE_MAX_MARKERS, B outside 0..PFMPE_MAX_BLOBS, n_corr
+ * outside 0..PFMPE_MAX_MARKERS, an LED index outside 1..M or a blob index outside 1..B in the first n_corr rows, rows
+ * of votes that do not all sum to n, a NaN, negative or infinite min_share or lead, min_pairs < 0; the outputs are
+ * untouched then. */
+typedef struct { double min_share; double lead; int32_t min_pairs; int32_t pad; } pfmpe_gate_params;   /* 24 bytes */
+typedef struct { int32_t n_in, n_gated, fallback, pad; uint8_t reason[PFMPE_MAX_MARKERS]; } pfmpe_gate_out; /* 32 bytes */
+void pfmpe_default_gate_params(pfmpe_gate_params* p);   /* 0.5, 2.0, 4 */
+int pfmpe_host_gate_pairs(const uint32_t* votes, int M, int B, const uint32_t* corr /* 2*PFMPE_MAX_MARKERS */,
+                          int n_corr, const pfmpe_gate_params* params /* NULL: defaults */,
+                          uint32_t* gated /* 2*PFMPE_MAX_MARKERS, zero padded */, pfmpe_gate_out* out);
+
 /* ------------------------------------------------------------- the K best distinct hypotheses of a frame */
 /* A step names two particles (the most likely one, the most resampled one); the runner-up, the mirror solution LED
  * markers are known for (the reference's checkAmbiguity / correspondencesVec), had to be found on the host from

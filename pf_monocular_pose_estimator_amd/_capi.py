@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "pfmpe_cloud_stats_multi", "pfmpe_host_cloud_plan",
     "pfmpe_default_top_params", "pfmpe_top_particles", "pfmpe_host_top_suppress",
     "pfmpe_default_modes_params", "pfmpe_cloud_modes", "pfmpe_host_cloud_assign",
+    "pfmpe_assoc_stats_multi", "pfmpe_host_assoc_plan", "pfmpe_default_gate_params", "pfmpe_host_gate_pairs",
 )
 MODES_MAX = 16
 MODE_NONE = 255
@@ -75,6 +76,8 @@ ROI_MAX_STREAMS = 64
 INIT_MAX_STREAMS = 64
 REFINE_MAX_STREAMS = 64
 CLOUD_MAX_STREAMS = 64
+ASSOC_MAX_STREAMS = 64
+ASSOC_MAX_LAUNCHES = 16
 REFINE_MULTI_MAX_HYPOTHESES = 65536
 REFINE_DESC_BYTES = 48
 
@@ -253,6 +256,41 @@ class AssocOut(C.Structure):
         return d
 
 
+class AssocMultiIn(C.Structure):
+    _fields_ = [("blobs", AssocIn), ("which", C.c_int32), ("pad", C.c_int32)]
+
+
+class AssocPlan(C.Structure):
+    _fields_ = [("bins_offset", C.c_int64), ("first_block", C.c_int32), ("blocks", C.c_int32),
+                ("launch", C.c_int32), ("lds_votes", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AssocPlanTotal(C.Structure):
+    _fields_ = [("bins_words", C.c_int64), ("launches", C.c_int32), ("pad", C.c_int32),
+                ("launch_blocks", C.c_int32 * ASSOC_MAX_LAUNCHES)]
+
+    def as_dict(self) -> dict:
+        return {"bins_words": self.bins_words, "launches": self.launches,
+                "launch_blocks": list(self.launch_blocks[: self.launches])}
+
+
+class GateParams(C.Structure):
+    _fields_ = [("min_share", C.c_double), ("lead", C.c_double), ("min_pairs", C.c_int32), ("pad", C.c_int32)]
+
+
+class GateOut(C.Structure):
+    _fields_ = [("n_in", C.c_int32), ("n_gated", C.c_int32), ("fallback", C.c_int32), ("pad", C.c_int32),
+                ("reason", C.c_uint8 * MAX_MARKERS)]
+
+
+# the sizes include/pfmpe.h states (pfmpe_engine.hip asserts them on its side)
+assert (C.sizeof(AssocMultiIn), C.sizeof(AssocPlan), C.sizeof(AssocPlanTotal), C.sizeof(GateParams),
+        C.sizeof(GateOut)) == (24, 24, 80, 24, 32)
+
+
 class TopParams(C.Structure):
     _fields_ = [("key", C.c_int32), ("K", C.c_int32), ("min_trans", C.c_double), ("min_rot", C.c_double)]
 
@@ -359,6 +397,12 @@ def load() -> C.CDLL:
         "pfmpe_get_pairs": (I, [P, I, C.POINTER(AssocIn), C.c_int64, C.c_int32, C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_int32)]),
         "pfmpe_host_assoc_summary": (I, [C.POINTER(C.c_uint32), I, I, C.POINTER(AssocOut)]),
+        "pfmpe_assoc_stats_multi": (I, [C.POINTER(P), I, C.POINTER(AssocMultiIn), C.POINTER(AssocOut),
+                                        C.POINTER(C.POINTER(C.c_uint32))]),
+        "pfmpe_host_assoc_plan": (I, [C.POINTER(C.c_int32)] * 6 + [I, I, C.POINTER(AssocPlan), C.POINTER(AssocPlanTotal)]),
+        "pfmpe_default_gate_params": (None, [C.POINTER(GateParams)]),
+        "pfmpe_host_gate_pairs": (I, [C.POINTER(C.c_uint32), I, I, C.POINTER(C.c_uint32), I, C.POINTER(GateParams),
+                                      C.POINTER(C.c_uint32), C.POINTER(GateOut)]),
         "pfmpe_default_top_params": (None, [C.POINTER(TopParams)]),
         "pfmpe_top_particles": (I, [P, C.POINTER(TopParams), C.POINTER(AssocIn), C.POINTER(TopOut), C.POINTER(C.c_int32),
                                     dp, dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
@@ -949,6 +993,40 @@ class Engine:
             d["votes"] = votes[: out.M * (out.B + 1)].reshape(out.M, out.B + 1).copy()
         return d
 
+    @staticmethod
+    def assoc_stats_multi(engines, whichs, blobs_list=None, bank_frames=None, want_votes: bool = True) -> list:
+        """The association votes of S entries as ONE batch on the device (pfmpe_assoc_stats_multi): entry s is
+        assoc_stats(whichs[s], blobs_list[s] or bank_frames[s]) of engines[s] (an engine may appear several times: both
+        sets of one object, or two blob lists; a bank frame is one of ITS engine's staged bank).  Returns one dict per
+        entry, each what assoc_stats returns."""
+        S = len(engines)
+        blobs_list = [None] * S if blobs_list is None else list(blobs_list)
+        bank_frames = [-1] * S if bank_frames is None else list(bank_frames)
+        if S == 0 or S != len(whichs) or S != len(blobs_list) or S != len(bank_frames):
+            raise ValueError("assoc_stats_multi: one which and one blob list or bank frame per engine")
+        ctxs = (C.c_void_p * S)(*[e.ctx.value for e in engines])
+        arr_in = (AssocMultiIn * S)()
+        keep, tabs = [], []
+        vps = (C.POINTER(C.c_uint32) * S)()
+        for s in range(S):
+            ai, kb = Engine._assoc_in(blobs_list[s], int(bank_frames[s]))
+            keep.append(kb)
+            arr_in[s].blobs = ai
+            arr_in[s].which = int(whichs[s])
+            if want_votes:  # a bank frame's count comes back in out.B: room for the largest frame
+                nb = MAX_BLOBS if int(bank_frames[s]) >= 0 else (kb.shape[0] if kb is not None else 0)
+                tabs.append(np.zeros(max(engines[s].M, 1) * (nb + 1), dtype=np.uint32))
+                vps[s] = tabs[s].ctypes.data_as(C.POINTER(C.c_uint32))
+        arr_out = (AssocOut * S)()
+        engines[0]._chk(engines[0].lib.pfmpe_assoc_stats_multi(ctxs, S, arr_in, arr_out, vps if want_votes else None))
+        res = []
+        for s, o in enumerate(arr_out):
+            d = o.as_dict()
+            if want_votes:
+                d["votes"] = tabs[s][: o.M * (o.B + 1)].reshape(o.M, o.B + 1).copy()
+            res.append(d)
+        return res
+
     def get_pairs(self, which: int, blobs=None, bank_frame: int = -1, first: int = 0, count=None):
         """The pairs of particles first .. first + count - 1 of a set (pfmpe_get_pairs; count None: to the end):
         (corr[count, MAX_MARKERS, 2] uint32 of 1-based (LED, blob) rows padded with zeros, n_corr[count] int32)."""
@@ -1276,6 +1354,60 @@ def host_assoc_summary(votes) -> dict:
     d = out.as_dict()
     del d["n_any"], d["npairs_hist"]
     return d
+
+
+def host_assoc_plan(N, M, B, which=None, prune=None, table_bytes=None, state_dtype: int = STATE_F32) -> tuple:
+    """pfmpe_host_assoc_plan: the layout of an assoc_stats_multi batch whose entry s has N[s] particles, M[s] LEDs and
+    B[s] blobs (which / prune / table_bytes: per entry, or None for all POSTERIOR / all pruned / tables without a
+    grid).  Returns (one dict per entry: bins_offset, first_block, blocks, launch, lds_votes; the totals' dict)."""
+    arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) if a is not None else None
+            for a in (N, M, B, which, prune, table_bytes)]
+    S = arrs[0].size
+    if any(a is not None and a.size != S for a in arrs):
+        raise ValueError("host_assoc_plan: one value per entry in every array")
+    plan = (AssocPlan * max(S, 1))()
+    total = AssocPlanTotal()
+    ptr = [a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None for a in arrs]
+    rc = load().pfmpe_host_assoc_plan(*ptr, S, int(state_dtype), plan, C.byref(total))
+    if rc != OK:
+        raise PFError(rc, "pfmpe_host_assoc_plan")
+    return [plan[s].as_dict() for s in range(S)], total.as_dict()
+
+
+def default_gate_params() -> GateParams:
+    p = GateParams()
+    load().pfmpe_default_gate_params(C.byref(p))
+    return p
+
+
+def host_gate_pairs(votes, pairs, n_corr=None, params=None, min_share=None, lead=None, min_pairs=None) -> dict:
+    """pfmpe_host_gate_pairs: the pairs of a row (pairs: up to MAX_MARKERS 1-based (LED, blob) rows, e.g.
+    FrameOut.pairs(); n_corr None: all of them) that an (M, B + 1) votes table supports.  params: a GateParams, default
+    pfmpe_default_gate_params (0.5, 2.0, 4); the keywords override its fields.  Returns n_in, n_gated, fallback,
+    reason (n_in uint8: bit 0 too little support, bit 1 not the LED's mode, bit 2 a contested mode) and gated, the
+    (MAX_MARKERS, 2) uint32 row to refine: the kept pairs, or with fallback the input row."""
+    v = np.ascontiguousarray(votes, dtype=np.uint32)
+    if v.ndim != 2 or v.shape[1] < 1:
+        raise ValueError("host_gate_pairs: votes must be an (M, B + 1) table")
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    n = pr.shape[0] if n_corr is None else int(n_corr)
+    row = np.zeros((MAX_MARKERS, 2), dtype=np.uint32)
+    m = min(pr.shape[0], MAX_MARKERS)
+    row[:m] = pr[:m]
+    prm = GateParams()
+    C.memmove(C.byref(prm), C.byref(params if params is not None else default_gate_params()), C.sizeof(GateParams))
+    for k, val in (("min_share", min_share), ("lead", lead), ("min_pairs", min_pairs)):
+        if val is not None:
+            setattr(prm, k, val)
+    gated = np.zeros((MAX_MARKERS, 2), dtype=np.uint32)
+    out = GateOut()
+    u32 = C.POINTER(C.c_uint32)
+    rc = load().pfmpe_host_gate_pairs(v.ctypes.data_as(u32), v.shape[0], v.shape[1] - 1, row.ctypes.data_as(u32), n,
+                                      C.byref(prm), gated.ctypes.data_as(u32), C.byref(out))
+    if rc != OK:
+        raise PFError(rc, "pfmpe_host_gate_pairs: bad table, row or parameters")
+    return {"n_in": out.n_in, "n_gated": out.n_gated, "fallback": out.fallback,
+            "reason": np.array(out.reason[: out.n_in], dtype=np.uint8), "gated": gated}
 
 
 def default_top_params() -> TopParams:

@@ -217,6 +217,11 @@ struct pfmpe_ctx : CtxQueue {
   // up to 4 (grown on demand, never shrunk); and the pinned block the counts are read back into
   Buf<unsigned char> d_modes;
   Buf<unsigned char, Mem::Pinned> h_modes;
+  // pfmpe_assoc_stats_multi (owned by the batch's first context): the device copy of the batch's image (launch heads,
+  // descriptors, every entry's blob table) followed by the bins of all entries, and the pinned block the image is
+  // built in and the bins are read back into (same layout); grown on demand, never shrunk
+  Buf<unsigned char> d_assocm;
+  Buf<unsigned char, Mem::Pinned> h_assocm;
   int num_cu = 0;
   bool coop = false;               // device supports cooperative launches
   int fused = 2;                   // PFMPE_OPT_FUSED: 2 flat one-launch (k_frame2), 1 tree (k_frame), 0 two launches
@@ -608,6 +613,28 @@ inline const uint32_t* prior_owner_ptr(const pfmpe_ctx* c) {
 // against the blob table `table` (device, tbytes, grid header gh) of B blobs, with the context's current model and
 // parameters.  aa.lds_votes is set here.  Not bracketed by the timing events.
 int assoc_launch(pfmpe_ctx* c, int B, const unsigned char* table, size_t tbytes, const GridHdr& gh, AssocArgs aa);
+
+// The batch (pfmpe_assoc_stats_multi; pfmpe_assoc.hip).  The leader's pinned image and its device copy hold, in this
+// order: the launches' heads, the S descriptors, then every entry's blob table (assoc_multi_tables_off onwards, each
+// 16-byte aligned, built by the caller); the bins of all entries are one device table of their own.
+struct AssocMultiEntry {
+  pfmpe_ctx* c;
+  int32_t which, B;
+  size_t tbytes, table_off;  // the entry's built table: size, byte offset in the image
+  GridHdr gh;                // its grid header
+  int64_t bins_off;          // words: the entry's bins in the device table (pfmpe_host_assoc_plan)
+  int32_t launch, first_block, blocks, lds_votes;  // as planned (lds_votes: 0 also under kDiagAssocDirect)
+};
+size_t assoc_multi_tables_off(const pfmpe_ctx* c0, int S);
+// Writes the heads and descriptors into himg, then on c0's stream: one copy of the image (img_bytes) to dimg, one
+// memset of the bins_words words at dbins, one k_assoc_votes_multi launch per planned launch.  A PROPAGATED entry reads
+// its context's d_xfer (regenerated and ordered before by the caller).
+int assoc_multi_run(pfmpe_ctx* c0, const AssocMultiEntry* e, int S, int launches, unsigned char* himg,
+                    unsigned char* dimg, size_t img_bytes, uint32_t* dbins, size_t bins_words);
+// pfmpe_host_assoc_plan (which, prune, table_bytes may be null); *bad, when given: the entry an error is about
+int assoc_plan(const int32_t* N, const int32_t* M, const int32_t* B, const int32_t* which, const int32_t* prune,
+               const int32_t* table_bytes, int S, int state_dtype, pfmpe_assoc_plan* plan, pfmpe_assoc_plan_total* total,
+               int* bad);
 
 // Gauss-Newton refinement scratch (pfmpe_refine_poses / pfmpe_refine_cloud; pfmpe_refine.hip), one allocation: the
 // call's summary, the model in fp64 (markers, K, the call's blobs), one partial per block, then the rows and

@@ -1143,6 +1143,34 @@ int assoc_prepare(pfmpe_ctx* c, const char* who, int which, const pfmpe_assoc_in
   *B_out = B;
   return PFMPE_OK;
 }
+// The record and the table of one entry from its bins as the kernel leaves them (M x B votes, then the M + 1 bins of
+// the pair count), for N particles; votes may be null.  false: the rows do not sum to one n.
+bool assoc_epilogue(const uint32_t* bins, int M, int B, int N, pfmpe_assoc_out* out, uint32_t* votes) {
+  // column 0 is not voted: n minus the row's votes
+  std::vector<uint32_t> tab((size_t)M * (B + 1));
+  for (int m = 0; m < M; ++m) {
+    uint32_t sum = 0;
+    for (int b = 0; b < B; ++b) {
+      tab[(size_t)m * (B + 1) + 1 + b] = bins[(size_t)m * B + b];
+      sum += bins[(size_t)m * B + b];
+    }
+    tab[(size_t)m * (B + 1)] = (uint32_t)N - sum;
+  }
+  pfmpe_assoc_out o;
+  if (pfmpe_host_assoc_summary(tab.data(), M, B, &o) != PFMPE_OK) return false;
+  for (int k = 0; k <= M; ++k) o.npairs_hist[k] = bins[(size_t)M * B + k];
+  o.n_any = (int64_t)N - (int64_t)o.npairs_hist[0];
+  *out = o;
+  if (votes) std::memcpy(votes, tab.data(), tab.size() * sizeof(uint32_t));
+  return true;
+}
+// the largest table build_table can write for B blobs of this context's type (the finest grid B may get, full lists)
+size_t assoc_table_bound(const pfmpe_ctx* c, int B) {
+  return visit_state(c, [&](auto s) {
+    return BlobTable<typename decltype(s)::T>::total_bytes(B, B >= kGridFineMinBlobs ? kGridMaxCells : kGridCoarseCells,
+                                                           kGridMaxEntries);
+  });
+}
 }  // namespace
 
 int pfmpe_assoc_stats(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, pfmpe_assoc_out* out, uint32_t* votes) {
@@ -1167,22 +1195,185 @@ int pfmpe_assoc_stats(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, pfmpe_a
   HIPCHK(c, hipMemcpyAsync(bins.data(), c->d_assoc.get(), (size_t)nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   RET(harvest_timing(c));  // (a propagated call's regeneration is bracketed like the particle read-back's)
-
-  // column 0 is not voted: n minus the row's votes
-  std::vector<uint32_t> tab((size_t)M * (B + 1));
-  for (int m = 0; m < M; ++m) {
-    uint32_t sum = 0;
-    for (int b = 0; b < B; ++b) {
-      tab[(size_t)m * (B + 1) + 1 + b] = bins[(size_t)m * B + b];
-      sum += bins[(size_t)m * B + b];
-    }
-    tab[(size_t)m * (B + 1)] = (uint32_t)N - sum;
-  }
-  if (pfmpe_host_assoc_summary(tab.data(), M, B, out) != PFMPE_OK)
+  if (!assoc_epilogue(bins.data(), M, B, N, out, votes))
     return fail(c, PFMPE_E_STATE, "assoc_stats: inconsistent votes table");
-  for (int k = 0; k <= M; ++k) out->npairs_hist[k] = bins[(size_t)M * B + k];
-  out->n_any = (int64_t)N - (int64_t)out->npairs_hist[0];
-  if (votes) std::memcpy(votes, tab.data(), tab.size() * sizeof(uint32_t));
+  return PFMPE_OK;
+}
+
+int pfmpe_assoc_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_assoc_multi_in* in, pfmpe_assoc_out* out,
+                            uint32_t* const* votes) {
+  static_assert(sizeof(pfmpe_assoc_multi_in) == 24 && sizeof(pfmpe_assoc_plan) == 24 && sizeof(pfmpe_assoc_plan_total) == 80,
+                "ABI");
+  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
+  pfmpe_ctx* c0 = ctxs[0];
+  if (!in || !out) return fail(c0, PFMPE_E_ARG, "assoc_stats_multi: null in/out");
+  if (S > PFMPE_ASSOC_MAX_STREAMS) return fail(c0, PFMPE_E_CAP, "assoc_stats_multi: S exceeds PFMPE_ASSOC_MAX_STREAMS");
+  // ---- every check, on host data alone
+  AssocMultiEntry e[PFMPE_ASSOC_MAX_STREAMS];
+  const double* blobs[PFMPE_ASSOC_MAX_STREAMS];
+  for (int s = 0; s < S; ++s) {
+    pfmpe_ctx* c = ctxs[s];
+    const std::string at = "assoc_stats_multi: stream " + std::to_string(s) + ": ";
+    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
+    if (c->device != c0->device || c->state_dtype != c0->state_dtype)
+      return fail(c0, PFMPE_E_ARG, at + "device and state type must match ctxs[0]");
+    const int which = in[s].which;
+    if (which != PFMPE_ASSOC_PROPAGATED && which != PFMPE_ASSOC_POSTERIOR) return fail(c0, PFMPE_E_ARG, at + "bad which");
+    int B = 0;
+    RET(resolve_blobs(c, at.substr(0, at.size() - 2), &in[s].blobs, &blobs[s], &B, c0));
+    if (!c->has_model || !c->has_prior) return fail(c0, PFMPE_E_STATE, at + "set_model and a particle set first");
+    if (which == PFMPE_ASSOC_PROPAGATED && !c->has_last) return fail(c0, PFMPE_E_STATE, at + "propagated: no step yet");
+    e[s] = AssocMultiEntry{};
+    e[s].c = c;
+    e[s].which = which;
+    e[s].B = B;
+  }
+  // the distinct contexts in order of first appearance (ctxs[0] first), and which of them have a PROPAGATED entry
+  std::vector<pfmpe_ctx*> distinct;
+  std::vector<char> regen;
+  for (int s = 0; s < S; ++s) {
+    size_t m = 0;
+    while (m < distinct.size() && distinct[m] != ctxs[s]) ++m;
+    if (m == distinct.size()) {
+      distinct.push_back(ctxs[s]);
+      regen.push_back(0);
+    }
+    if (e[s].which == PFMPE_ASSOC_PROPAGATED) regen[m] = 1;
+  }
+  RET(set_device(c0));
+  // ---- the image: every entry's table, built in the leader's pinned block behind the heads and descriptors (host
+  // work: nothing is on the device yet).  The block holds the largest table each entry can get.
+  const size_t tables_off = assoc_multi_tables_off(c0, S);
+  size_t cap = tables_off;
+  for (int s = 0; s < S; ++s) cap += align16(assoc_table_bound(c0, e[s].B));
+  {
+    size_t bins_bound = 0;  // the batch's bins, each entry's start rounded up to 4 words
+    for (int s = 0; s < S; ++s) bins_bound += (((size_t)assoc_bins(e[s].c->M, e[s].B) + 3) & ~(size_t)3) * sizeof(uint32_t);
+    const size_t need = (cap + 255) / 256 * 256 + bins_bound;
+    RET(c0->h_assocm.grow(c0, need, need * 2));
+  }
+  unsigned char* himg = c0->h_assocm.get();
+  int32_t Ns[PFMPE_ASSOC_MAX_STREAMS], Ms[PFMPE_ASSOC_MAX_STREAMS], Bs[PFMPE_ASSOC_MAX_STREAMS], Ws[PFMPE_ASSOC_MAX_STREAMS],
+      Ps[PFMPE_ASSOC_MAX_STREAMS], Ts[PFMPE_ASSOC_MAX_STREAMS];
+  size_t img_bytes = tables_off;
+  for (int s = 0; s < S; ++s) {
+    const pfmpe_ctx* c = e[s].c;
+    e[s].table_off = img_bytes;
+    e[s].tbytes = build_table(c, blobs[s], e[s].B, himg + img_bytes);
+    e[s].gh = *(const GridHdr*)(himg + img_bytes + grid_off(c, e[s].B));
+    img_bytes += align16(e[s].tbytes);
+    Ns[s] = c->N;
+    Ms[s] = c->M;
+    Bs[s] = e[s].B;
+    Ws[s] = e[s].which;
+    Ps[s] = c->prune ? 1 : 0;
+    Ts[s] = (int32_t)e[s].tbytes;
+  }
+  pfmpe_assoc_plan plan[PFMPE_ASSOC_MAX_STREAMS];
+  pfmpe_assoc_plan_total total{};
+  int bad = 0;  // (S, the counts and B were checked above: what is left is a table that exceeds the LDS)
+  if (const int r_ = assoc_plan(Ns, Ms, Bs, Ws, Ps, Ts, S, c0->state_dtype, plan, &total, &bad))
+    return fail(c0, r_, "assoc_stats_multi: stream " + std::to_string(bad) + ": blob table exceeds the LDS");
+  for (int s = 0; s < S; ++s) {
+    e[s].bins_off = plan[s].bins_offset;
+    e[s].launch = plan[s].launch;
+    e[s].first_block = plan[s].first_block;
+    e[s].blocks = plan[s].blocks;
+    e[s].lds_votes = (plan[s].lds_votes && !(e[s].c->diag & kDiagAssocDirect)) ? 1 : 0;
+  }
+  // the device scratch: the image, then the bins (nothing of an earlier batch is pending: the call is blocking)
+  const size_t bins_at = (img_bytes + 255) / 256 * 256;
+  const size_t bins_bytes = (size_t)total.bins_words * sizeof(uint32_t);
+  RET(c0->d_assocm.grow(c0, bins_at + bins_bytes, (bins_at + bins_bytes) * 2));
+  for (size_t m = 0; m < distinct.size(); ++m)
+    if (regen[m]) RET(ensure_xfer(distinct[m]));
+  // each PROPAGATED context's kept propagated set once, as its single call regenerates it: into its own d_xfer, on its
+  // own stream (set_device: after whatever it has pending elsewhere); all its entries read that set
+  for (size_t m = 0; m < distinct.size(); ++m) {
+    pfmpe_ctx* c = distinct[m];
+    if (!regen[m]) continue;
+    if (c != c0) RET(set_device(c));
+    if (const int r_ = dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()))
+      return c == c0 ? r_ : fail(c0, r_, "assoc_stats_multi: " + c->err);
+  }
+  // every member's work so far, that regeneration included, is ordered before the batch; a failure from here on gives
+  // the members their ordering state back (the leader's own was set by set_device)
+  OrderGuard members(distinct.data(), (int)distinct.size());
+  RET(members.order(1, c0->stream, c0));
+  uint32_t* dbins = (uint32_t*)(c0->d_assocm.get() + bins_at);
+  RET(assoc_multi_run(c0, e, S, total.launches, himg, c0->d_assocm.get(), img_bytes, dbins, (size_t)total.bins_words));
+  const uint32_t* hbins = (const uint32_t*)(himg + bins_at);
+  HIPCHK(c0, hipMemcpyAsync((void*)hbins, dbins, bins_bytes, hipMemcpyDeviceToHost, c0->stream));
+  if (hipStreamSynchronize(c0->stream) != hipSuccess)
+    return fail(c0, PFMPE_E_HIP, "assoc_stats_multi: stream synchronise failed");
+  members.commit();  // nothing of the batch is pending: no member needs a fence
+  for (pfmpe_ctx* c : distinct)  // (as every single call ends: the brackets of sampled frames still pending)
+    if (const int r_ = harvest_timing(c)) return c == c0 ? r_ : fail(c0, r_, "assoc_stats_multi: " + c->err);
+  // the tables are checked before any output is written
+  for (int s = 0; s < S; ++s) {
+    pfmpe_assoc_out o;
+    if (!assoc_epilogue(hbins + e[s].bins_off, e[s].c->M, e[s].B, e[s].c->N, &o, nullptr))
+      return fail(c0, PFMPE_E_STATE, "assoc_stats_multi: stream " + std::to_string(s) + ": inconsistent votes table");
+  }
+  for (int s = 0; s < S; ++s)
+    (void)assoc_epilogue(hbins + e[s].bins_off, e[s].c->M, e[s].B, e[s].c->N, &out[s], votes ? votes[s] : nullptr);
+  return PFMPE_OK;
+}
+
+int pfmpe_host_assoc_plan(const int32_t* N, const int32_t* M, const int32_t* B, const int32_t* which, const int32_t* prune,
+                          const int32_t* table_bytes, int S, int state_dtype, pfmpe_assoc_plan* plan,
+                          pfmpe_assoc_plan_total* total) {
+  return assoc_plan(N, M, B, which, prune, table_bytes, S, state_dtype, plan, total, nullptr);
+}
+
+void pfmpe_default_gate_params(pfmpe_gate_params* p) {
+  if (!p) return;
+  p->min_share = 0.5;
+  p->lead = 2.0;
+  p->min_pairs = 4;
+  p->pad = 0;
+}
+
+int pfmpe_host_gate_pairs(const uint32_t* votes, int M, int B, const uint32_t* corr, int n_corr,
+                          const pfmpe_gate_params* params, uint32_t* gated, pfmpe_gate_out* out) {
+  static_assert(sizeof(pfmpe_gate_params) == 24 && sizeof(pfmpe_gate_out) == 32, "ABI");
+  if (!votes || !corr || !gated || !out || M < 1 || M > kMaxMarkers || B < 0 || B > kMaxBlobs || n_corr < 0 ||
+      n_corr > kMaxMarkers)
+    return PFMPE_E_ARG;
+  pfmpe_gate_params prm;
+  pfmpe_default_gate_params(&prm);
+  if (params) prm = *params;
+  for (const double v : {prm.min_share, prm.lead})
+    if (!(v >= 0.0) || !std::isfinite(v)) return PFMPE_E_ARG;
+  if (prm.min_pairs < 0) return PFMPE_E_ARG;
+  for (int k = 0; k < n_corr; ++k)
+    if (corr[2 * k] < 1u || corr[2 * k] > (uint32_t)M || corr[2 * k + 1] < 1u || corr[2 * k + 1] > (uint32_t)B)
+      return PFMPE_E_ARG;
+  pfmpe_assoc_out sum;
+  if (pfmpe_host_assoc_summary(votes, M, B, &sum) != PFMPE_OK) return PFMPE_E_ARG;  // rows that do not all sum to n
+  pfmpe_gate_out go{};
+  uint32_t kept[2 * kMaxMarkers] = {0};
+  go.n_in = n_corr;
+  for (int k = 0; k < n_corr; ++k) {
+    const uint32_t led = corr[2 * k], blob = corr[2 * k + 1];
+    const uint32_t v = votes[(size_t)(led - 1) * (B + 1) + blob];
+    uint8_t r = 0;
+    if (!((double)v >= prm.min_share * (double)sum.n)) r |= 1;
+    if (sum.mode_blob[led - 1] != blob) r |= 2;
+    if (prm.lead * (double)sum.second_votes[led - 1] > (double)sum.mode_votes[led - 1]) r |= 4;
+    go.reason[k] = r;
+    if (r) continue;
+    kept[2 * go.n_gated] = led;
+    kept[2 * go.n_gated + 1] = blob;
+    go.n_gated += 1;
+  }
+  go.fallback = go.n_gated < prm.min_pairs ? 1 : 0;
+  if (go.fallback) {
+    std::memset(kept, 0, sizeof(kept));
+    std::memcpy(kept, corr, (size_t)n_corr * 2 * sizeof(uint32_t));
+  }
+  std::memcpy(gated, kept, sizeof(kept));  // (corr and gated may be the same row)
+  *out = go;
   return PFMPE_OK;
 }
 
