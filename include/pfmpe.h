@@ -644,7 +644,8 @@ typedef struct {
   uint32_t npairs_hist[PFMPE_MAX_MARKERS + 1]; /* particles with exactly k pairs                     */
   uint32_t pad;
 } pfmpe_assoc_out;                             /* 352 bytes */
-/* votes: M x (B + 1) words, row-major, may be NULL */
+/* votes: M x (B + 1) words, row-major, may be NULL.  (Runs as pfmpe_assoc_stats_multi, below, with one entry: one
+ * path, one kernel and one scratch for both.) */
 int pfmpe_assoc_stats(pfmpe_ctx* ctx, int which, const pfmpe_assoc_in* in, pfmpe_assoc_out* out, uint32_t* votes);
 /* the rows of particles first .. first + count - 1 (the reference's correspondencesVec[i]):
  * corr count x 2*PFMPE_MAX_MARKERS words, n_corr count pair counts */

@@ -349,5 +349,9 @@ PFGN_HD bool gn_better(int np1, double r1, int64_t i1, int np2, double r2, int64
 PFGN_HD bool gn_eligible(const pfmpe_refine_row& r) {
   return r.n_pairs > 0 && r.rms_after - r.rms_after == 0.0;
 }
+// the parameters every refinement entry point accepts
+inline bool refine_params_ok(const pfmpe_refine_params& p) {
+  return p.max_iter >= 1 && p.max_iter <= 10000 && p.converged >= 0.0;  // (a NaN fails the comparison)
+}
 
 }  // namespace pfmpe

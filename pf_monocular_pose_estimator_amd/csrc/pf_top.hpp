@@ -1,7 +1,8 @@
 #pragma once
 // pf_top.hpp — pfmpe_top_particles: the K best distinct hypotheses of the last step's kept propagated set (the
 // definition is in include/pfmpe.h).  Here: the separation predicate and the suppression walk, shared by the device
-// and pfmpe_host_top_suppress; the keys as ordered bit patterns; the scratch layout; the launches of pfmpe_top.hip.
+// and pfmpe_host_top_suppress; the keys as ordered bit patterns; the scratch layout.  The kernels, their launches and the
+// entry point are in pfmpe_top.hip.
 #include <math.h>
 #include <stdint.h>
 
@@ -204,20 +205,3 @@ struct TopBuf {
 static_assert(TopBuf::kRecord % 16 == 0 && TopBuf::kCandKey % 8 == 0 && TopBuf::kPoolPoses % 8 == 0, "scratch alignment");
 
 }  // namespace pfmpe
-
-namespace pfmpe_impl {
-
-enum { kTopKeyF32 = 0, kTopKeyF64 = 1, kTopKeyU32 = 2 };
-// The selection on the context's stream: the scratch cleared, then the radix select over the N keys (`key_type` says
-// what they are), the compaction and the sort.  Leaves the result state (state[kTopMaxPasses]), the ranked
-// pool's particle indices (kPoolIdx) and keys as doubles (kPoolKey).  *pool_count: the device address of the pool's
-// size.
-int top_select_launch(pfmpe_ctx* c, unsigned char* d_top, const void* keys, int key_type, int N,
-                      const uint32_t** pool_count);
-// The rest, behind the regeneration of the pool's poses into kPoolPoses (skipped when neither suppression nor a pose
-// row is wanted: poses = false): the near-matrix (suppression only), then one block that walks it and writes the
-// record and the rows of the kept candidates for `rows` rows; pose rows n_out .. rows - 1 get a harmless constant
-// (the pair kernel runs over `rows` rows: n_out is not known to the host yet).
-int top_finish_launch(pfmpe_ctx* c, unsigned char* d_top, int K, int rows, const pfmpe::TopThresholds& th, bool poses);
-
-}  // namespace pfmpe_impl

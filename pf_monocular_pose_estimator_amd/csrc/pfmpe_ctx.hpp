@@ -167,7 +167,6 @@ struct pfmpe_ctx : CtxQueue {
   Buf<uint32_t> d_gen; // k_frame iteration release word (monotonic)
   Buf<Cand> d_cand; // per-block winner candidates
   Buf<double> d_mlpose; // most likely pose (12)
-  Buf<uint32_t> d_assoc; // association votes: M x B bins + the pair-count bins (pfmpe_assoc_stats)
   Buf<uint32_t> d_pairs; // pair rows of one chunk of particles, then their counts (pfmpe_get_pairs)
   Buf<unsigned char> d_refine; // Gauss-Newton refinement scratch (RefineBuf layout, pfmpe_refine_*)
   // pfmpe_top_particles: the selection's scratch and the record (pf_top.hpp TopBuf; one size for every N and K,
@@ -217,7 +216,7 @@ struct pfmpe_ctx : CtxQueue {
   // up to 4 (grown on demand, never shrunk); and the pinned block the counts are read back into
   Buf<unsigned char> d_modes;
   Buf<unsigned char, Mem::Pinned> h_modes;
-  // pfmpe_assoc_stats_multi (owned by the batch's first context): the device copy of the batch's image (launch heads,
+  // pfmpe_assoc_stats_multi (owned by the batch's first context; pfmpe_assoc_stats is a batch of one): the device copy of the batch's image (launch heads,
   // descriptors, every entry's blob table) followed by the bins of all entries, and the pinned block the image is
   // built in and the bins are read back into (same layout); grown on demand, never shrunk
   Buf<unsigned char> d_assocm;
@@ -608,87 +607,28 @@ inline const uint32_t* prior_owner_ptr(const pfmpe_ctx* c) {
   return c->prior_owner >= 0 ? c->d_owner[c->prior_owner].get() : nullptr;
 }
 
-// k_assoc_votes for the context's state type, marker bucket and pruning option on its stream (pfmpe_assoc.hip, a TU
-// of its own): the particles aa.first .. + aa.count of the regenerated kept set (aa.dense) or of the resident prior,
-// against the blob table `table` (device, tbytes, grid header gh) of B blobs, with the context's current model and
-// parameters.  aa.lds_votes is set here.  Not bracketed by the timing events.
-int assoc_launch(pfmpe_ctx* c, int B, const unsigned char* table, size_t tbytes, const GridHdr& gh, AssocArgs aa);
-
-// The batch (pfmpe_assoc_stats_multi; pfmpe_assoc.hip).  The leader's pinned image and its device copy hold, in this
-// order: the launches' heads, the S descriptors, then every entry's blob table (assoc_multi_tables_off onwards, each
-// 16-byte aligned, built by the caller); the bins of all entries are one device table of their own.
-struct AssocMultiEntry {
-  pfmpe_ctx* c;
-  int32_t which, B;
-  size_t tbytes, table_off;  // the entry's built table: size, byte offset in the image
-  GridHdr gh;                // its grid header
-  int64_t bins_off;          // words: the entry's bins in the device table (pfmpe_host_assoc_plan)
-  int32_t launch, first_block, blocks, lds_votes;  // as planned (lds_votes: 0 also under kDiagAssocDirect)
-};
-size_t assoc_multi_tables_off(const pfmpe_ctx* c0, int S);
-// Writes the heads and descriptors into himg, then on c0's stream: one copy of the image (img_bytes) to dimg, one
-// memset of the bins_words words at dbins, one k_assoc_votes_multi launch per planned launch.  A PROPAGATED entry reads
-// its context's d_xfer (regenerated and ordered before by the caller).
-int assoc_multi_run(pfmpe_ctx* c0, const AssocMultiEntry* e, int S, int launches, unsigned char* himg,
-                    unsigned char* dimg, size_t img_bytes, uint32_t* dbins, size_t bins_words);
-// pfmpe_host_assoc_plan (which, prune, table_bytes may be null); *bad, when given: the entry an error is about
-int assoc_plan(const int32_t* N, const int32_t* M, const int32_t* B, const int32_t* which, const int32_t* prune,
-               const int32_t* table_bytes, int S, int state_dtype, pfmpe_assoc_plan* plan, pfmpe_assoc_plan_total* total,
-               int* bad);
-
-// Gauss-Newton refinement scratch (pfmpe_refine_poses / pfmpe_refine_cloud; pfmpe_refine.hip), one allocation: the
-// call's summary, the model in fp64 (markers, K, the call's blobs), one partial per block, then the rows and
-// covariances of one chunk of hypotheses.  Hypotheses are refined a chunk at a time (the pair rows of a chunk are in
-// d_pairs, kPairsChunk rows at most), so the scratch does not grow with the particle count.
-constexpr int kPairsChunk = 1 << 16;  // pair rows per get_pairs / refine launch (d_pairs: 132 B per particle)
-constexpr int kRefineMaxBlocks = kPairsChunk / kBlock;
-struct RefinePart {
-  int64_t n_with, n_conv, n_kept, n_rev, it_total;
-  int32_t it_max, best_np;
-  double best_rms;
-  int64_t best;  // index within the call, -1: none
-};
-struct RefineBuf {
-  static constexpr size_t kOut = 0;
-  static constexpr size_t kMarkers = 512;
-  static constexpr size_t kK = kMarkers + kMaxMarkers * 3 * sizeof(double);
-  static constexpr size_t kBlobs = kK + 16 * sizeof(double);
-  static size_t part(int max_blobs) { return (kBlobs + (size_t)max_blobs * 2 * sizeof(double) + 255) / 256 * 256; }
-  static size_t rows(int max_blobs) { return part(max_blobs) + kRefineMaxBlocks * sizeof(RefinePart); }
-  static size_t cov(int max_blobs, int cap) { return rows(max_blobs) + (size_t)cap * sizeof(pfmpe_refine_row); }
-  static size_t bytes(int max_blobs, int cap) { return cov(max_blobs, cap) + (size_t)cap * 36 * sizeof(double); }
-};
-static_assert(sizeof(pfmpe_refine_row) == 128 && sizeof(pfmpe_refine_out) <= RefineBuf::kMarkers, "refine layout");
-// One chunk: k_refine over `count` hypotheses (start poses at poses + 12 * i, rows at corr + 2 * kMaxMarkers * i,
-// i = 0 .. count - 1; index within the call base + i), then k_refine_fold of its partials into the summary at
-// d_refine (begun anew when `begin`).  d_refine holds the model and the blobs already.
-int refine_launch(pfmpe_ctx* c, const pfmpe_refine_params& prm, const double* poses, const uint32_t* corr, int64_t base,
-                  int count, int cap, bool begin);
-
-// The batch (pfmpe_refine_multi): the leader's d_refm holds the packed upload of pfmpe_refine_plan.hpp (`up`), and
-// behind it what the device writes: S summaries, H rows, H covariances, read back as one block.  All pointers are
-// into d_refm.  (RefineDesc: pfmpe_refine_plan.hpp, included by the two units that use it.)
-}  // namespace pfmpe_impl
-namespace pfmpe_plan {
-struct RefineDesc;
-}
-namespace pfmpe_impl {
-using pfmpe_plan::RefineDesc;
-struct RefineMultiArgs {
-  const unsigned char* up;   // the upload: the descriptors' model_offset / blobs_offset count from here
-  const RefineDesc* desc;    // S
-  const int32_t* stream_of;  // H: the stream of hypothesis h
-  const double* poses;       // H x 12
-  const uint32_t* corr;      // H x 2 * kMaxMarkers
-  pfmpe_refine_out* out;     // S
-  pfmpe_refine_row* rows;    // H
-  double* cov;               // H x 36
-  int32_t H, pad;
-};
-// k_refine_multi over the H hypotheses (skipped when H = 0), then k_refine_fold_multi, one wave per stream, on the
-// leader's stream.
-int refine_multi_launch(pfmpe_ctx* c0, const RefineMultiArgs& ma, int S);
-
+// ---------------------------------------------------------------------- shared preambles of the entry points
+// Defined in pfmpe_engine.hip, used by the side calls' units as well: the byte offset of a table's GridHdr; the frame's
+// blob table for the context's current parameters, built at dst (returns its size); the kept iteration's propagated
+// set regenerated into out (N x 12), or its particles list[i], i < min(*count, limit) (list, count, out on the device),
+// both bracketed as PFMPE_K_AUX; the prior's first `count` particles into d_xfer, on the context's stream.
+size_t grid_off(const pfmpe_ctx* c, int B);
+size_t build_table(const pfmpe_ctx* c, const double* blobs, int B, unsigned char* dst);
+int dispatch_regen(pfmpe_ctx* c, int kept_iter, const void* prior, double* out);
+int dispatch_regen_list(pfmpe_ctx* c, int kept_iter, const void* prior, const int32_t* list, const uint32_t* count,
+                        int limit, double* out);
+int export_prior(pfmpe_ctx* c, int count);
+// The argument and state checks shared by pfmpe_get_pairs / pfmpe_refine_cloud (pfmpe_assoc.hip; texts begin with
+// `who`), then the call's blob table built into d_table (every frame that reads d_table writes it first) and, for the
+// propagated set, the kept set regenerated into d_xfer and named by aa->dense.  *blobs_out / *B_out: the blobs the call
+// means (resolve_blobs).
+int assoc_prepare(pfmpe_ctx* c, const char* who, int which, const pfmpe_assoc_in* in, const double** blobs_out,
+                  int* B_out, size_t* tbytes, GridHdr* gh, AssocArgs* aa);
+// k_assoc_votes in rows mode for the context's state type, marker bucket and pruning option on its stream
+// (pfmpe_assoc.hip): the pair rows (aa.corr, aa.n_corr) of the particles aa.first .. + aa.count of the regenerated kept
+// set (aa.dense) or of the resident prior, against the blob table `table` (device, tbytes, grid header gh) of B blobs,
+// with the context's current model and parameters.  Not bracketed by the timing events.
+int assoc_rows_launch(pfmpe_ctx* c, int B, const unsigned char* table, size_t tbytes, const GridHdr& gh, AssocArgs aa);
 // k_step_tail (pfmpe_refine.hip) for the c->tail_S streams staged in c->h_tail, on c's stream, bracketed as
 // PFMPE_K_AUX: each stream's wave looks for the finished record of frame sequence seq0 + delta.
 int tail_launch(pfmpe_ctx* c, int32_t delta);
@@ -696,11 +636,11 @@ int tail_launch(pfmpe_ctx* c, int32_t delta);
 inline int tail_after(pfmpe_ctx* c) {
   return c->tail_S ? tail_launch(c, (c->seq - c->tail_seq0) & 0x3fffffff) : (int)PFMPE_OK;
 }
-
-// ---------------------------------------------------------------------- shared preambles of the entry points
 // the transfer buffer (N x 12 doubles), written and read inside one blocking call by every user
 inline int ensure_xfer(pfmpe_ctx* c) { return c->d_xfer.ensure(c, (size_t)c->max_particles * 12 * sizeof(double)); }
-// the pair rows of one chunk of pairs_cap(c) particles, then their counts (pfmpe_get_pairs, pfmpe_refine_*)
+// the pair rows of one chunk of pairs_cap(c) particles, kPairsChunk at most (132 B per particle), then their counts
+// (pfmpe_get_pairs, pfmpe_refine_*)
+constexpr int kPairsChunk = 1 << 16;
 constexpr size_t kPairRow = 2 * kMaxMarkers;
 inline int pairs_cap(const pfmpe_ctx* c) { return std::min(c->max_particles, kPairsChunk); }
 inline int ensure_pairs(pfmpe_ctx* c) {

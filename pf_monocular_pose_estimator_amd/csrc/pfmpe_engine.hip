@@ -2,15 +2,15 @@
 //
 // Replaces the PF block of PoseEstimator::estimateBodyPose (pf_mpe_lib/src/pose_estimator.cpp:475-733).
 // The launch sequences live in pfmpe_seq.hpp (Seq) and are instantiated per (state type, RNG) in the
-// pfmpe_k_*.hip translation units; this unit launches the side calls' kernels and builds the blob tables.
+// pfmpe_k_*.hip translation units; this unit holds the step with its tail, the ROI and cloud-statistics calls with
+// their kernels' launches, the read-backs, and builds the blob tables.  The association, refinement, top-K,
+// initialisation and detector calls are in the units of their kernels.
 #include "pf_cloud.hpp"
 #include "pf_gn.hpp"
 #include "pf_likelihood.hpp"
 #include "pf_roi.hpp"
 #include "pf_tail.hpp"
-#include "pf_top.hpp"
 #include "pfmpe_prior.hpp"
-#include "pfmpe_refine_plan.hpp"
 
 using namespace pfmpe_impl;
 
@@ -21,15 +21,8 @@ PFMPE_DECLARE_INSTANCE(double, kRngPhilox, double, extern)
 PFMPE_DECLARE_INSTANCE(float, kRngReference, __half, extern)
 PFMPE_DECLARE_INSTANCE(float, kRngPhilox, __half, extern)
 
-namespace {
-
-int dispatch_step(pfmpe_ctx* c, const pfmpe_frame_in* in, const unsigned char* table, size_t tbytes,
-                  const GridHdr& gh) {
-  return visit_state_rng(c, [&](auto s) {
-    using S = decltype(s);
-    return dispatch_m<typename S::T, S::RNG, typename S::SP>(c, in, table, tbytes, gh);
-  });
-}
+// ---- used by the side calls' units as well (declared in pfmpe_ctx.hpp)
+namespace pfmpe_impl {
 
 int dispatch_regen(pfmpe_ctx* c, int kept_iter, const void* prior, double* out) {
   return visit_state_rng(c, [&](auto s) {
@@ -50,10 +43,6 @@ int dispatch_regen_list(pfmpe_ctx* c, int kept_iter, const void* prior, const in
 size_t grid_off(const pfmpe_ctx* c, int B) {
   return visit_state(c, [&](auto s) { return BlobTable<typename decltype(s)::T>::off_grid(B); });
 }
-// largest blob table of this context's type (base part at kMaxBlobs + the largest grid)
-size_t table_max_bytes(const pfmpe_ctx* c) {
-  return visit_state(c, [&](auto s) { return BlobTable<typename decltype(s)::T>::max_bytes(); });
-}
 // the frame's blob table for the context's current parameters (pruning half-window as build_args computes
 // it); returns its size
 size_t build_table(const pfmpe_ctx* c, const double* blobs, int B, unsigned char* dst) {
@@ -61,6 +50,25 @@ size_t build_table(const pfmpe_ctx* c, const double* blobs, int B, unsigned char
     using T = typename decltype(s)::T;
     return build_blob_table_host<T>(blobs, B, (double)(T)(c->params.tol_pf * (1.0 + 1e-3) + 1e-3), dst);
   });
+}
+
+int export_prior(pfmpe_ctx* c, int count) { return export_prior(c, count, c->stream, c); }
+
+}  // namespace pfmpe_impl
+
+namespace {
+
+int dispatch_step(pfmpe_ctx* c, const pfmpe_frame_in* in, const unsigned char* table, size_t tbytes,
+                  const GridHdr& gh) {
+  return visit_state_rng(c, [&](auto s) {
+    using S = decltype(s);
+    return dispatch_m<typename S::T, S::RNG, typename S::SP>(c, in, table, tbytes, gh);
+  });
+}
+
+// largest blob table of this context's type (base part at kMaxBlobs + the largest grid)
+size_t table_max_bytes(const pfmpe_ctx* c) {
+  return visit_state(c, [&](auto s) { return BlobTable<typename decltype(s)::T>::max_bytes(); });
 }
 
 // pfmpe_step's argument and state checks (also per stream of pfmpe_step_multi)
@@ -1084,679 +1092,6 @@ int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in*
     if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c0, PFMPE_E_STATE, at + "weighted: no step yet");
   }
   return cloud_run(ctxs, S, in, out, "cloud_stats_multi");
-}
-int pfmpe_host_assoc_summary(const uint32_t* votes, int M, int B, pfmpe_assoc_out* out) {
-  if (!votes || !out || M < 1 || M > kMaxMarkers || B < 0) return PFMPE_E_ARG;
-  std::memset(out, 0, sizeof(*out));
-  out->M = M;
-  out->B = B;
-  for (int m = 0; m < M; ++m) {
-    const uint32_t* row = votes + (size_t)m * (B + 1);
-    int64_t sum = 0;
-    uint32_t best = 0, second = 0, arg = 0;
-    for (int b = 0; b <= B; ++b) sum += row[b];
-    for (int b = 1; b <= B; ++b) {  // a strict test keeps the lowest blob index among equal vote counts
-      if (row[b] > best) {
-        second = best;
-        best = row[b];
-        arg = (uint32_t)b;
-      } else if (row[b] > second) {
-        second = row[b];
-      }
-    }
-    if (m == 0) out->n = sum;
-    if (sum != out->n) return PFMPE_E_ARG;
-    out->matched[m] = (uint32_t)(sum - row[0]);
-    out->mode_blob[m] = best ? arg : 0u;
-    out->mode_votes[m] = best;
-    out->second_votes[m] = second;
-  }
-  return PFMPE_OK;
-}
-
-namespace {
-// The argument and state checks shared by pfmpe_assoc_stats / pfmpe_get_pairs, then the call's blob table built
-// into d_table (every frame that reads d_table writes it first) and, for the propagated set, the kept set
-// regenerated into d_xfer (written and read inside one blocking call by every user).  *blobs_out / *B_out: the
-// blobs the call means (resolve_blobs).
-int assoc_prepare(pfmpe_ctx* c, const char* who, int which, const pfmpe_assoc_in* in, const double** blobs_out,
-                  int* B_out, size_t* tbytes, GridHdr* gh, AssocArgs* aa) {
-  const std::string w(who);
-  if (!in || (which != PFMPE_ASSOC_PROPAGATED && which != PFMPE_ASSOC_POSTERIOR))
-    return fail(c, PFMPE_E_ARG, w + ": bad arguments");
-  const double* blobs = nullptr;
-  int B = 0;
-  RET(resolve_blobs(c, w, in, &blobs, &B));
-  if (!c->has_model || !c->has_prior) return fail(c, PFMPE_E_STATE, w + ": set_model and a particle set first");
-  if (which == PFMPE_ASSOC_PROPAGATED && !c->has_last) return fail(c, PFMPE_E_STATE, w + "(propagated): no step yet");
-  RET(set_device(c));
-  *tbytes = build_table(c, blobs, B, c->h_table.get());
-  *gh = *(const GridHdr*)(c->h_table.get() + grid_off(c, B));
-  HIPCHK(c, hipMemcpyAsync(c->d_table.get(), c->h_table.get(), *tbytes, hipMemcpyHostToDevice, c->stream));
-  *aa = AssocArgs{};
-  if (which == PFMPE_ASSOC_PROPAGATED) {
-    RET(ensure_xfer(c));
-    RET(dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()));
-    aa->dense = c->d_xfer.get();
-  }
-  *blobs_out = blobs;
-  *B_out = B;
-  return PFMPE_OK;
-}
-// The record and the table of one entry from its bins as the kernel leaves them (M x B votes, then the M + 1 bins of
-// the pair count), for N particles; votes may be null.  false: the rows do not sum to one n.
-bool assoc_epilogue(const uint32_t* bins, int M, int B, int N, pfmpe_assoc_out* out, uint32_t* votes) {
-  // column 0 is not voted: n minus the row's votes
-  std::vector<uint32_t> tab((size_t)M * (B + 1));
-  for (int m = 0; m < M; ++m) {
-    uint32_t sum = 0;
-    for (int b = 0; b < B; ++b) {
-      tab[(size_t)m * (B + 1) + 1 + b] = bins[(size_t)m * B + b];
-      sum += bins[(size_t)m * B + b];
-    }
-    tab[(size_t)m * (B + 1)] = (uint32_t)N - sum;
-  }
-  pfmpe_assoc_out o;
-  if (pfmpe_host_assoc_summary(tab.data(), M, B, &o) != PFMPE_OK) return false;
-  for (int k = 0; k <= M; ++k) o.npairs_hist[k] = bins[(size_t)M * B + k];
-  o.n_any = (int64_t)N - (int64_t)o.npairs_hist[0];
-  *out = o;
-  if (votes) std::memcpy(votes, tab.data(), tab.size() * sizeof(uint32_t));
-  return true;
-}
-// the largest table build_table can write for B blobs of this context's type (the finest grid B may get, full lists)
-size_t assoc_table_bound(const pfmpe_ctx* c, int B) {
-  return visit_state(c, [&](auto s) {
-    return BlobTable<typename decltype(s)::T>::total_bytes(B, B >= kGridFineMinBlobs ? kGridMaxCells : kGridCoarseCells,
-                                                           kGridMaxEntries);
-  });
-}
-}  // namespace
-
-int pfmpe_assoc_stats(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, pfmpe_assoc_out* out, uint32_t* votes) {
-  if (!c) return PFMPE_E_ARG;
-  if (!out) return fail(c, PFMPE_E_ARG, "assoc_stats: null out");
-  const double* blobs = nullptr;
-  int B = 0;
-  size_t tbytes = 0;
-  GridHdr gh{};
-  AssocArgs aa{};
-  RET(assoc_prepare(c, "assoc_stats", which, in, &blobs, &B, &tbytes, &gh, &aa));
-  // scratch of the call's own: the bins of the largest table
-  RET(c->d_assoc.ensure(c, (size_t)assoc_bins(kMaxMarkers, kMaxBlobs) * sizeof(uint32_t)));
-  const int M = c->M, N = c->N;
-  const int nbins = assoc_bins(M, B);
-  HIPCHK(c, hipMemsetAsync(c->d_assoc.get(), 0, (size_t)nbins * sizeof(uint32_t), c->stream));
-  aa.votes = c->d_assoc.get();
-  aa.first = 0;
-  aa.count = N;
-  RET(assoc_launch(c, B, c->d_table.get(), tbytes, gh, aa));
-  std::vector<uint32_t> bins(nbins);
-  HIPCHK(c, hipMemcpyAsync(bins.data(), c->d_assoc.get(), (size_t)nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  RET(harvest_timing(c));  // (a propagated call's regeneration is bracketed like the particle read-back's)
-  if (!assoc_epilogue(bins.data(), M, B, N, out, votes))
-    return fail(c, PFMPE_E_STATE, "assoc_stats: inconsistent votes table");
-  return PFMPE_OK;
-}
-
-int pfmpe_assoc_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_assoc_multi_in* in, pfmpe_assoc_out* out,
-                            uint32_t* const* votes) {
-  static_assert(sizeof(pfmpe_assoc_multi_in) == 24 && sizeof(pfmpe_assoc_plan) == 24 && sizeof(pfmpe_assoc_plan_total) == 80,
-                "ABI");
-  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
-  pfmpe_ctx* c0 = ctxs[0];
-  if (!in || !out) return fail(c0, PFMPE_E_ARG, "assoc_stats_multi: null in/out");
-  if (S > PFMPE_ASSOC_MAX_STREAMS) return fail(c0, PFMPE_E_CAP, "assoc_stats_multi: S exceeds PFMPE_ASSOC_MAX_STREAMS");
-  // ---- every check, on host data alone
-  AssocMultiEntry e[PFMPE_ASSOC_MAX_STREAMS];
-  const double* blobs[PFMPE_ASSOC_MAX_STREAMS];
-  for (int s = 0; s < S; ++s) {
-    pfmpe_ctx* c = ctxs[s];
-    const std::string at = "assoc_stats_multi: stream " + std::to_string(s) + ": ";
-    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
-    if (c->device != c0->device || c->state_dtype != c0->state_dtype)
-      return fail(c0, PFMPE_E_ARG, at + "device and state type must match ctxs[0]");
-    const int which = in[s].which;
-    if (which != PFMPE_ASSOC_PROPAGATED && which != PFMPE_ASSOC_POSTERIOR) return fail(c0, PFMPE_E_ARG, at + "bad which");
-    int B = 0;
-    RET(resolve_blobs(c, at.substr(0, at.size() - 2), &in[s].blobs, &blobs[s], &B, c0));
-    if (!c->has_model || !c->has_prior) return fail(c0, PFMPE_E_STATE, at + "set_model and a particle set first");
-    if (which == PFMPE_ASSOC_PROPAGATED && !c->has_last) return fail(c0, PFMPE_E_STATE, at + "propagated: no step yet");
-    e[s] = AssocMultiEntry{};
-    e[s].c = c;
-    e[s].which = which;
-    e[s].B = B;
-  }
-  // the distinct contexts in order of first appearance (ctxs[0] first), and which of them have a PROPAGATED entry
-  std::vector<pfmpe_ctx*> distinct;
-  std::vector<char> regen;
-  for (int s = 0; s < S; ++s) {
-    size_t m = 0;
-    while (m < distinct.size() && distinct[m] != ctxs[s]) ++m;
-    if (m == distinct.size()) {
-      distinct.push_back(ctxs[s]);
-      regen.push_back(0);
-    }
-    if (e[s].which == PFMPE_ASSOC_PROPAGATED) regen[m] = 1;
-  }
-  RET(set_device(c0));
-  // ---- the image: every entry's table, built in the leader's pinned block behind the heads and descriptors (host
-  // work: nothing is on the device yet).  The block holds the largest table each entry can get.
-  const size_t tables_off = assoc_multi_tables_off(c0, S);
-  size_t cap = tables_off;
-  for (int s = 0; s < S; ++s) cap += align16(assoc_table_bound(c0, e[s].B));
-  {
-    size_t bins_bound = 0;  // the batch's bins, each entry's start rounded up to 4 words
-    for (int s = 0; s < S; ++s) bins_bound += (((size_t)assoc_bins(e[s].c->M, e[s].B) + 3) & ~(size_t)3) * sizeof(uint32_t);
-    const size_t need = (cap + 255) / 256 * 256 + bins_bound;
-    RET(c0->h_assocm.grow(c0, need, need * 2));
-  }
-  unsigned char* himg = c0->h_assocm.get();
-  int32_t Ns[PFMPE_ASSOC_MAX_STREAMS], Ms[PFMPE_ASSOC_MAX_STREAMS], Bs[PFMPE_ASSOC_MAX_STREAMS], Ws[PFMPE_ASSOC_MAX_STREAMS],
-      Ps[PFMPE_ASSOC_MAX_STREAMS], Ts[PFMPE_ASSOC_MAX_STREAMS];
-  size_t img_bytes = tables_off;
-  for (int s = 0; s < S; ++s) {
-    const pfmpe_ctx* c = e[s].c;
-    e[s].table_off = img_bytes;
-    e[s].tbytes = build_table(c, blobs[s], e[s].B, himg + img_bytes);
-    e[s].gh = *(const GridHdr*)(himg + img_bytes + grid_off(c, e[s].B));
-    img_bytes += align16(e[s].tbytes);
-    Ns[s] = c->N;
-    Ms[s] = c->M;
-    Bs[s] = e[s].B;
-    Ws[s] = e[s].which;
-    Ps[s] = c->prune ? 1 : 0;
-    Ts[s] = (int32_t)e[s].tbytes;
-  }
-  pfmpe_assoc_plan plan[PFMPE_ASSOC_MAX_STREAMS];
-  pfmpe_assoc_plan_total total{};
-  int bad = 0;  // (S, the counts and B were checked above: what is left is a table that exceeds the LDS)
-  if (const int r_ = assoc_plan(Ns, Ms, Bs, Ws, Ps, Ts, S, c0->state_dtype, plan, &total, &bad))
-    return fail(c0, r_, "assoc_stats_multi: stream " + std::to_string(bad) + ": blob table exceeds the LDS");
-  for (int s = 0; s < S; ++s) {
-    e[s].bins_off = plan[s].bins_offset;
-    e[s].launch = plan[s].launch;
-    e[s].first_block = plan[s].first_block;
-    e[s].blocks = plan[s].blocks;
-    e[s].lds_votes = (plan[s].lds_votes && !(e[s].c->diag & kDiagAssocDirect)) ? 1 : 0;
-  }
-  // the device scratch: the image, then the bins (nothing of an earlier batch is pending: the call is blocking)
-  const size_t bins_at = (img_bytes + 255) / 256 * 256;
-  const size_t bins_bytes = (size_t)total.bins_words * sizeof(uint32_t);
-  RET(c0->d_assocm.grow(c0, bins_at + bins_bytes, (bins_at + bins_bytes) * 2));
-  for (size_t m = 0; m < distinct.size(); ++m)
-    if (regen[m]) RET(ensure_xfer(distinct[m]));
-  // each PROPAGATED context's kept propagated set once, as its single call regenerates it: into its own d_xfer, on its
-  // own stream (set_device: after whatever it has pending elsewhere); all its entries read that set
-  for (size_t m = 0; m < distinct.size(); ++m) {
-    pfmpe_ctx* c = distinct[m];
-    if (!regen[m]) continue;
-    if (c != c0) RET(set_device(c));
-    if (const int r_ = dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()))
-      return c == c0 ? r_ : fail(c0, r_, "assoc_stats_multi: " + c->err);
-  }
-  // every member's work so far, that regeneration included, is ordered before the batch; a failure from here on gives
-  // the members their ordering state back (the leader's own was set by set_device)
-  OrderGuard members(distinct.data(), (int)distinct.size());
-  RET(members.order(1, c0->stream, c0));
-  uint32_t* dbins = (uint32_t*)(c0->d_assocm.get() + bins_at);
-  RET(assoc_multi_run(c0, e, S, total.launches, himg, c0->d_assocm.get(), img_bytes, dbins, (size_t)total.bins_words));
-  const uint32_t* hbins = (const uint32_t*)(himg + bins_at);
-  HIPCHK(c0, hipMemcpyAsync((void*)hbins, dbins, bins_bytes, hipMemcpyDeviceToHost, c0->stream));
-  if (hipStreamSynchronize(c0->stream) != hipSuccess)
-    return fail(c0, PFMPE_E_HIP, "assoc_stats_multi: stream synchronise failed");
-  members.commit();  // nothing of the batch is pending: no member needs a fence
-  for (pfmpe_ctx* c : distinct)  // (as every single call ends: the brackets of sampled frames still pending)
-    if (const int r_ = harvest_timing(c)) return c == c0 ? r_ : fail(c0, r_, "assoc_stats_multi: " + c->err);
-  // the tables are checked before any output is written
-  for (int s = 0; s < S; ++s) {
-    pfmpe_assoc_out o;
-    if (!assoc_epilogue(hbins + e[s].bins_off, e[s].c->M, e[s].B, e[s].c->N, &o, nullptr))
-      return fail(c0, PFMPE_E_STATE, "assoc_stats_multi: stream " + std::to_string(s) + ": inconsistent votes table");
-  }
-  for (int s = 0; s < S; ++s)
-    (void)assoc_epilogue(hbins + e[s].bins_off, e[s].c->M, e[s].B, e[s].c->N, &out[s], votes ? votes[s] : nullptr);
-  return PFMPE_OK;
-}
-
-int pfmpe_host_assoc_plan(const int32_t* N, const int32_t* M, const int32_t* B, const int32_t* which, const int32_t* prune,
-                          const int32_t* table_bytes, int S, int state_dtype, pfmpe_assoc_plan* plan,
-                          pfmpe_assoc_plan_total* total) {
-  return assoc_plan(N, M, B, which, prune, table_bytes, S, state_dtype, plan, total, nullptr);
-}
-
-void pfmpe_default_gate_params(pfmpe_gate_params* p) {
-  if (!p) return;
-  p->min_share = 0.5;
-  p->lead = 2.0;
-  p->min_pairs = 4;
-  p->pad = 0;
-}
-
-int pfmpe_host_gate_pairs(const uint32_t* votes, int M, int B, const uint32_t* corr, int n_corr,
-                          const pfmpe_gate_params* params, uint32_t* gated, pfmpe_gate_out* out) {
-  static_assert(sizeof(pfmpe_gate_params) == 24 && sizeof(pfmpe_gate_out) == 32, "ABI");
-  if (!votes || !corr || !gated || !out || M < 1 || M > kMaxMarkers || B < 0 || B > kMaxBlobs || n_corr < 0 ||
-      n_corr > kMaxMarkers)
-    return PFMPE_E_ARG;
-  pfmpe_gate_params prm;
-  pfmpe_default_gate_params(&prm);
-  if (params) prm = *params;
-  for (const double v : {prm.min_share, prm.lead})
-    if (!(v >= 0.0) || !std::isfinite(v)) return PFMPE_E_ARG;
-  if (prm.min_pairs < 0) return PFMPE_E_ARG;
-  for (int k = 0; k < n_corr; ++k)
-    if (corr[2 * k] < 1u || corr[2 * k] > (uint32_t)M || corr[2 * k + 1] < 1u || corr[2 * k + 1] > (uint32_t)B)
-      return PFMPE_E_ARG;
-  pfmpe_assoc_out sum;
-  if (pfmpe_host_assoc_summary(votes, M, B, &sum) != PFMPE_OK) return PFMPE_E_ARG;  // rows that do not all sum to n
-  pfmpe_gate_out go{};
-  uint32_t kept[2 * kMaxMarkers] = {0};
-  go.n_in = n_corr;
-  for (int k = 0; k < n_corr; ++k) {
-    const uint32_t led = corr[2 * k], blob = corr[2 * k + 1];
-    const uint32_t v = votes[(size_t)(led - 1) * (B + 1) + blob];
-    uint8_t r = 0;
-    if (!((double)v >= prm.min_share * (double)sum.n)) r |= 1;
-    if (sum.mode_blob[led - 1] != blob) r |= 2;
-    if (prm.lead * (double)sum.second_votes[led - 1] > (double)sum.mode_votes[led - 1]) r |= 4;
-    go.reason[k] = r;
-    if (r) continue;
-    kept[2 * go.n_gated] = led;
-    kept[2 * go.n_gated + 1] = blob;
-    go.n_gated += 1;
-  }
-  go.fallback = go.n_gated < prm.min_pairs ? 1 : 0;
-  if (go.fallback) {
-    std::memset(kept, 0, sizeof(kept));
-    std::memcpy(kept, corr, (size_t)n_corr * 2 * sizeof(uint32_t));
-  }
-  std::memcpy(gated, kept, sizeof(kept));  // (corr and gated may be the same row)
-  *out = go;
-  return PFMPE_OK;
-}
-
-int pfmpe_get_pairs(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, int64_t first, int32_t count, uint32_t* corr,
-                    int32_t* n_corr) {
-  if (!c) return PFMPE_E_ARG;
-  if (first < 0 || count < 0 || (count > 0 && (!corr || !n_corr)))
-    return fail(c, PFMPE_E_ARG, "get_pairs: bad range or null output");
-  if (c->has_prior && first + (int64_t)count > (int64_t)c->N)
-    return fail(c, PFMPE_E_ARG, "get_pairs: first + count exceeds the particle count");
-  const double* blobs = nullptr;
-  int B = 0;
-  size_t tbytes = 0;
-  GridHdr gh{};
-  AssocArgs aa{};
-  RET(assoc_prepare(c, "get_pairs", which, in, &blobs, &B, &tbytes, &gh, &aa));
-  constexpr size_t kRow = kPairRow;
-  const int cap = pairs_cap(c);
-  RET(ensure_pairs(c));
-  aa.corr = c->d_pairs.get();
-  aa.n_corr = (int32_t*)(c->d_pairs.get() + (size_t)cap * kRow);
-  for (int64_t done = 0; done < count; done += cap) {
-    const int n = (int)std::min<int64_t>(cap, count - done);
-    aa.first = (int32_t)(first + done);
-    aa.count = n;
-    RET(assoc_launch(c, B, c->d_table.get(), tbytes, gh, aa));
-    HIPCHK(c, hipMemcpyAsync(corr + (size_t)done * kRow, aa.corr, (size_t)n * kRow * sizeof(uint32_t),
-                             hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(n_corr + done, aa.n_corr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the chunk buffer is reused
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  RET(harvest_timing(c));
-  return PFMPE_OK;
-}
-
-// ---- the K best distinct hypotheses of the kept propagated set (pf_top.hpp; the kernels are in pfmpe_top.hip)
-void pfmpe_default_top_params(pfmpe_top_params* p) {
-  if (!p) return;
-  p->key = PFMPE_TOP_BY_WEIGHT;
-  p->K = 8;
-  p->min_trans = 0.0;
-  p->min_rot = 0.0;
-}
-
-int pfmpe_top_particles(pfmpe_ctx* c, const pfmpe_top_params* params, const pfmpe_assoc_in* in, pfmpe_top_out* out,
-                        int32_t* index, double* key_value, double* poses, uint32_t* corr, int32_t* n_corr) {
-  if (!c) return PFMPE_E_ARG;
-  if (!params || !out) return fail(c, PFMPE_E_ARG, "top_particles: null params or out");
-  const pfmpe_top_params prm = *params;
-  if (prm.key != PFMPE_TOP_BY_WEIGHT && prm.key != PFMPE_TOP_BY_COUNT) return fail(c, PFMPE_E_ARG, "top_particles: bad key");
-  if (prm.K < 0 || prm.K > PFMPE_TOP_MAX) return fail(c, PFMPE_E_ARG, "top_particles: K out of range");
-  if (!(prm.min_trans >= 0.0) || !std::isfinite(prm.min_trans))
-    return fail(c, PFMPE_E_ARG, "top_particles: min_trans must be finite and >= 0");
-  if (!(prm.min_rot >= 0.0 && prm.min_rot <= M_PI)) return fail(c, PFMPE_E_ARG, "top_particles: min_rot outside [0, pi]");
-  const double* blobs = nullptr;
-  int B = 0;
-  if (in) RET(resolve_blobs(c, "top_particles", in, &blobs, &B));
-  if (!c->has_prior || !c->has_last) return fail(c, PFMPE_E_STATE, "top_particles: no step yet");
-  if (prm.key == PFMPE_TOP_BY_COUNT) {
-    if (!c->record_counts || !c->d_counts.get()) return fail(c, PFMPE_E_STATE, "top_particles: PFMPE_OPT_RECORD_COUNTS off");
-    if (!c->last_accepted) return fail(c, PFMPE_E_STATE, "top_particles: last step did not resample");
-  }
-  if (in && !c->has_model) return fail(c, PFMPE_E_STATE, "top_particles: blobs given without a model");
-  RET(set_device(c));
-  RET(c->d_top.ensure(c, TopBuf::bytes()));
-  RET(c->h_top.ensure(c, TopRows::bytes(PFMPE_TOP_MAX)));
-  const int N = c->N;
-  const int rows = std::min(prm.K, N);  // n_out <= min(K, n_positive): the rows the record is laid out for
-  const TopThresholds th = top_thresholds(prm.min_trans, prm.min_rot);
-  const bool suppress = prm.min_trans != 0.0 || prm.min_rot != 0.0;
-  const bool pairs = in && rows > 0;
-  const bool want_poses = suppress || pairs || (poses && rows > 0);
-  unsigned char* d = c->d_top.get();
-
-  const void* keys = c->d_w[c->last_kept_slot].get();
-  int key_type = c->state_dtype == PFMPE_STATE_F64 ? kTopKeyF64 : kTopKeyF32;
-  if (prm.key == PFMPE_TOP_BY_COUNT) {
-    keys = c->d_counts.get();
-    key_type = kTopKeyU32;
-  }
-  const uint32_t* pool_count = nullptr;
-  RET(top_select_launch(c, d, keys, key_type, N, &pool_count));
-  // the poses of the ranked pool only (all of it for the suppression walk, else the rows wanted), as k_regen makes
-  // them: bracketed as aux like every regeneration
-  if (want_poses)
-    RET(dispatch_regen_list(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), (const int32_t*)(d + TopBuf::kPoolIdx),
-                            pool_count, suppress ? kTopPool : rows, (double*)(d + TopBuf::kPoolPoses)));
-  RET(top_finish_launch(c, d, prm.K, rows, th, want_poses));
-  unsigned char* rec = d + TopBuf::kRecord;
-  if (pairs) {
-    // the rows' pairs as pfmpe_get_pairs derives them: the blob table as assoc_prepare builds it, the pair kernel in
-    // rows mode over the dense list of the kept rows' poses (it bounds its range by first / count alone; count is
-    // `rows`, the rows behind n_out hold a constant pose and are not returned)
-    const size_t tbytes = build_table(c, blobs, B, c->h_table.get());
-    const GridHdr gh = *(const GridHdr*)(c->h_table.get() + grid_off(c, B));
-    HIPCHK(c, hipMemcpyAsync(c->d_table.get(), c->h_table.get(), tbytes, hipMemcpyHostToDevice, c->stream));
-    AssocArgs aa{};
-    aa.dense = (const double*)(rec + TopRows::poses(rows));
-    aa.corr = (uint32_t*)(rec + TopRows::corr(rows));
-    aa.n_corr = (int32_t*)(rec + TopRows::n_corr(rows));
-    aa.first = 0;
-    aa.count = rows;
-    RET(assoc_launch(c, B, c->d_table.get(), tbytes, gh, aa));
-  }
-  // one read-back: the record and the rows (without the pair rows when no blobs were given)
-  unsigned char* h = c->h_top.get();
-  const size_t bytes = pairs ? TopRows::bytes(rows) : TopRows::n_corr(rows);
-  HIPCHK(c, hipMemcpyAsync(h, rec, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  RET(harvest_timing(c));
-  const TopRecord r = *(const TopRecord*)h;
-  if (r.n_out < 0 || r.n_out > rows) return fail(c, PFMPE_E_STATE, "top_particles: inconsistent record");
-  out->n = N;
-  out->n_positive = r.n_positive;
-  out->n_out = r.n_out;
-  out->n_examined = r.n_examined;
-  const size_t n = (size_t)r.n_out;
-  if (index) std::memcpy(index, h + TopRows::index(rows), n * sizeof(int32_t));
-  if (key_value) std::memcpy(key_value, h + TopRows::kKey, n * sizeof(double));
-  if (poses) std::memcpy(poses, h + TopRows::poses(rows), n * 12 * sizeof(double));
-  if (pairs && corr) std::memcpy(corr, h + TopRows::corr(rows), n * kPairRow * sizeof(uint32_t));
-  if (pairs && n_corr) std::memcpy(n_corr, h + TopRows::n_corr(rows), n * sizeof(int32_t));
-  return PFMPE_OK;
-}
-
-// ---- Gauss-Newton refinement (optimisePose, PE:1805-2009): pf_gn.hpp on the host here, k_refine in pfmpe_refine.hip
-void pfmpe_default_refine_params(pfmpe_refine_params* p) {
-  if (!p) return;
-  p->max_iter = 500;
-  p->revert_on_divergence = 1;
-  p->converged = 1e-13;
-}
-
-namespace {
-bool refine_params_ok(const pfmpe_refine_params& p) {
-  return p.max_iter >= 1 && p.max_iter <= 10000 && p.converged >= 0.0;  // (a NaN fails the comparison)
-}
-// the rows' indices: LED 1 .. M beside a blob, never above M; blob 0 .. B
-bool refine_corr_ok(const uint32_t* corr, size_t n_rows, int M, int B) {
-  for (size_t j = 0; j < n_rows; ++j) {
-    const uint32_t led = corr[2 * j], blob = corr[2 * j + 1];
-    if (led > (uint32_t)M || blob > (uint32_t)B || (blob != 0u && led == 0u)) return false;
-  }
-  return true;
-}
-bool refine_poses_finite(const double* poses, size_t n) {
-  for (size_t q = 0; q < 12 * n; ++q)
-    if (!std::isfinite(poses[q])) return false;
-  return true;
-}
-
-// the scratch, the model and the call's blobs in fp64 (enqueued on the stream; `stage` must outlive the copy)
-int refine_stage(pfmpe_ctx* c, const double* blobs, int B, int cap, std::vector<double>& stage) {
-  RET(c->d_refine.ensure(c, RefineBuf::bytes(c->max_blobs, cap)));
-  const size_t words = (RefineBuf::kBlobs - RefineBuf::kMarkers) / sizeof(double) + 2 * (size_t)B;
-  stage.assign(words, 0.0);
-  std::memcpy(stage.data(), c->markers, sizeof(c->markers));
-  std::memcpy(stage.data() + (RefineBuf::kK - RefineBuf::kMarkers) / sizeof(double), c->K, sizeof(c->K));
-  if (B > 0) std::memcpy(stage.data() + (RefineBuf::kBlobs - RefineBuf::kMarkers) / sizeof(double), blobs, 2 * (size_t)B * sizeof(double));
-  HIPCHK(c, hipMemcpyAsync(c->d_refine.get() + RefineBuf::kMarkers, stage.data(), words * sizeof(double), hipMemcpyHostToDevice,
-                           c->stream));
-  return PFMPE_OK;
-}
-// a chunk's rows and covariances, hypotheses lo .. hi - 1 of the chunk, to the caller's arrays at index `at`
-int refine_fetch(pfmpe_ctx* c, int cap, int lo, int hi, pfmpe_refine_row* rows, double* cov, int64_t at) {
-  if (hi <= lo) return PFMPE_OK;
-  const unsigned char* d = c->d_refine.get();
-  if (rows)
-    HIPCHK(c, hipMemcpyAsync(rows + at, d + RefineBuf::rows(c->max_blobs) + (size_t)lo * sizeof(pfmpe_refine_row),
-                             (size_t)(hi - lo) * sizeof(pfmpe_refine_row), hipMemcpyDeviceToHost, c->stream));
-  if (cov)
-    HIPCHK(c, hipMemcpyAsync(cov + 36 * at, d + RefineBuf::cov(c->max_blobs, cap) + (size_t)lo * 36 * sizeof(double),
-                             (size_t)(hi - lo) * 36 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  return PFMPE_OK;
-}
-int refine_finish(pfmpe_ctx* c, int64_t n, pfmpe_refine_out* out) {
-  HIPCHK(c, hipMemcpyAsync(out, c->d_refine.get() + RefineBuf::kOut, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  RET(harvest_timing(c));  // (a propagated call's regeneration is bracketed like the particle read-back's)
-  out->n = n;
-  return PFMPE_OK;
-}
-}  // namespace
-
-int pfmpe_refine_poses(pfmpe_ctx* c, const pfmpe_assoc_in* in, const pfmpe_refine_params* params, const double* poses,
-                       const uint32_t* corr, int32_t K, pfmpe_refine_out* out, pfmpe_refine_row* rows, double* cov) {
-  if (!c) return PFMPE_E_ARG;
-  pfmpe_refine_params prm;
-  pfmpe_default_refine_params(&prm);
-  if (params) prm = *params;
-  if (!out || !in || K < 0 || (K > 0 && (!poses || !corr))) return fail(c, PFMPE_E_ARG, "refine_poses: bad arguments");
-  if (!refine_params_ok(prm)) return fail(c, PFMPE_E_ARG, "refine_poses: bad parameters");
-  const double* blobs = nullptr;
-  int B = 0;
-  RET(resolve_blobs(c, "refine_poses", in, &blobs, &B));
-  if (K > c->max_particles) return fail(c, PFMPE_E_CAP, "refine_poses: K exceeds max_particles");
-  if (!c->has_model) return fail(c, PFMPE_E_STATE, "refine_poses: set_model first");
-  if (K > 0 && !refine_corr_ok(corr, (size_t)K * kMaxMarkers, c->M, B))
-    return fail(c, PFMPE_E_ARG, "refine_poses: LED or blob index out of range");
-  if (K > 0 && !refine_poses_finite(poses, (size_t)K)) return fail(c, PFMPE_E_ARG, "refine_poses: non-finite start pose");
-  RET(set_device(c));
-  RET(ensure_xfer(c));
-  constexpr size_t kRow = kPairRow;
-  const int cap = pairs_cap(c);
-  RET(ensure_pairs(c));
-  std::vector<double> stage;
-  RET(refine_stage(c, blobs, B, cap, stage));
-  // d_xfer is written and read inside one blocking call by every user
-  if (K > 0) HIPCHK(c, hipMemcpyAsync(c->d_xfer.get(), poses, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  int64_t done = 0;
-  do {  // (K = 0: one empty chunk writes the empty summary)
-    const int n = (int)std::min<int64_t>(cap, (int64_t)K - done);
-    if (n > 0)
-      HIPCHK(c, hipMemcpyAsync(c->d_pairs.get(), corr + (size_t)done * kRow, (size_t)n * kRow * sizeof(uint32_t),
-                               hipMemcpyHostToDevice, c->stream));
-    RET(refine_launch(c, prm, c->d_xfer.get() + 12 * done, c->d_pairs.get(), done, n, cap, done == 0));
-    RET(refine_fetch(c, cap, 0, n, rows, cov, done));
-    done += n;
-  } while (done < K);
-  return refine_finish(c, K, out);
-}
-
-int pfmpe_refine_cloud(pfmpe_ctx* c, int which, const pfmpe_assoc_in* in, const pfmpe_refine_params* params,
-                       int64_t first, int32_t count, pfmpe_refine_out* out, pfmpe_refine_row* rows, double* cov) {
-  if (!c) return PFMPE_E_ARG;
-  pfmpe_refine_params prm;
-  pfmpe_default_refine_params(&prm);
-  if (params) prm = *params;
-  if (!out || first < 0 || count < 0) return fail(c, PFMPE_E_ARG, "refine_cloud: null out or bad range");
-  if (c->has_prior && first + (int64_t)count > (int64_t)c->N)
-    return fail(c, PFMPE_E_ARG, "refine_cloud: first + count exceeds the particle count");
-  if (!refine_params_ok(prm)) return fail(c, PFMPE_E_ARG, "refine_cloud: bad parameters");
-  const double* blobs = nullptr;
-  int B = 0;
-  size_t tbytes = 0;
-  GridHdr gh{};
-  AssocArgs aa{};
-  RET(assoc_prepare(c, "refine_cloud", which, in, &blobs, &B, &tbytes, &gh, &aa));
-  const int N = c->N;
-  // the start poses as get_particles delivers them: the propagated set is in d_xfer already (assoc_prepare)
-  if (which == PFMPE_ASSOC_POSTERIOR) {
-    RET(ensure_xfer(c));
-    RET(export_prior(c, N));
-  }
-  constexpr size_t kRow = kPairRow;
-  const int cap = pairs_cap(c);
-  RET(ensure_pairs(c));
-  std::vector<double> stage;
-  RET(refine_stage(c, blobs, B, cap, stage));
-  aa.corr = c->d_pairs.get();
-  aa.n_corr = (int32_t*)(c->d_pairs.get() + (size_t)cap * kRow);
-  for (int64_t done = 0; done < N; done += cap) {
-    const int n = (int)std::min<int64_t>(cap, (int64_t)N - done);
-    aa.first = (int32_t)done;
-    aa.count = n;
-    RET(assoc_launch(c, B, c->d_table.get(), tbytes, gh, aa));
-    RET(refine_launch(c, prm, c->d_xfer.get() + 12 * done, c->d_pairs.get(), done, n, cap, done == 0));
-    const int64_t lo = std::max<int64_t>(first, done), hi = std::min<int64_t>(first + count, done + n);
-    RET(refine_fetch(c, cap, (int)(lo - done), (int)(hi - done), rows, cov, lo - first));
-  }
-  return refine_finish(c, N, out);
-}
-
-// pfmpe_refine_poses of S streams as one batch on ctxs[0]'s stream: the per-stream checks of the single call, the
-// upload of pfmpe_refine_plan.hpp built in the leader's pinned block, one copy up, two launches, one copy down, one
-// synchronise, and the results scattered to the caller's arrays.
-int pfmpe_refine_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_refine_in* in, const pfmpe_refine_params* params,
-                       pfmpe_refine_out* out, pfmpe_refine_row* const* rows, double* const* cov) {
-  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
-  pfmpe_ctx* c0 = ctxs[0];
-  if (!in || !out) return fail(c0, PFMPE_E_ARG, "refine_multi: null in/out");
-  if (S > PFMPE_REFINE_MAX_STREAMS) return fail(c0, PFMPE_E_CAP, "refine_multi: S exceeds PFMPE_REFINE_MAX_STREAMS");
-  struct Stream {
-    const double* blobs;
-    int B;
-    pfmpe_refine_params prm;
-  };
-  std::vector<Stream> st(S);
-  int32_t Ks[PFMPE_REFINE_MAX_STREAMS], Bs[PFMPE_REFINE_MAX_STREAMS];
-  int64_t H = 0;
-  for (int s = 0; s < S; ++s) {
-    const pfmpe_ctx* c = ctxs[s];
-    const pfmpe_refine_in& q = in[s];
-    const std::string at = "refine_multi: stream " + std::to_string(s) + ": ";
-    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
-    if (c->device != c0->device) return fail(c0, PFMPE_E_ARG, at + "device must match ctxs[0]");
-    pfmpe_default_refine_params(&st[s].prm);
-    if (params) st[s].prm = params[s];
-    if (q.K < 0 || (q.K > 0 && (!q.poses || !q.corr))) return fail(c0, PFMPE_E_ARG, at + "bad arguments");
-    if (!refine_params_ok(st[s].prm)) return fail(c0, PFMPE_E_ARG, at + "bad parameters");
-    RET(resolve_blobs(c, at + "blobs", &q.blobs, &st[s].blobs, &st[s].B, c0));
-    if (q.K > c->max_particles) return fail(c0, PFMPE_E_CAP, at + "K exceeds max_particles");
-    if (!c->has_model) return fail(c0, PFMPE_E_STATE, at + "set_model first");
-    if (q.K > 0 && !refine_corr_ok(q.corr, (size_t)q.K * kMaxMarkers, c->M, st[s].B))
-      return fail(c0, PFMPE_E_ARG, at + "LED or blob index out of range");
-    if (q.K > 0 && !refine_poses_finite(q.poses, (size_t)q.K)) return fail(c0, PFMPE_E_ARG, at + "non-finite start pose");
-    Ks[s] = q.K;
-    Bs[s] = st[s].B;
-    H += q.K;
-    if (H > PFMPE_REFINE_MULTI_MAX_HYPOTHESES)
-      return fail(c0, PFMPE_E_CAP, at + "the batch exceeds PFMPE_REFINE_MULTI_MAX_HYPOTHESES hypotheses");
-  }
-  static_assert(PFMPE_REFINE_MULTI_MAX_HYPOTHESES <= kPairsChunk, "one launch without a grid stride");
-  pfmpe_refine_plan plan[PFMPE_REFINE_MAX_STREAMS];
-  pfmpe_refine_plan_total tot;
-  pfmpe_plan::refine_plan(Ks, Bs, S, plan, &tot);
-  RET(set_device(c0));
-  // the device block: the upload, then summaries, rows and covariances; the pinned block mirrors it
-  const size_t up = (size_t)tot.upload_bytes, down = (size_t)tot.download_bytes, all = up + down;
-  RET(c0->d_refm.grow(c0, all, all + all / 2));
-  RET(c0->h_refm.grow(c0, all, all + all / 2));
-  unsigned char* h = c0->h_refm.get();
-  unsigned char* d = c0->d_refm.get();
-  std::memset(h, 0, up);  // the gaps between regions and unused marker slots: the same bytes for the same plan
-  RefineDesc* ds = (RefineDesc*)(h + tot.desc_offset);
-  int32_t* stream_of = (int32_t*)(h + tot.stream_of_offset);
-  for (int s = 0; s < S; ++s) {
-    const pfmpe_ctx* c = ctxs[s];
-    const size_t K = (size_t)Ks[s], first = (size_t)plan[s].first;
-    ds[s].model_offset = plan[s].model_offset;
-    ds[s].blobs_offset = plan[s].blobs_offset;
-    ds[s].first = plan[s].first;
-    ds[s].count = Ks[s];
-    ds[s].max_iter = st[s].prm.max_iter;
-    ds[s].revert = st[s].prm.revert_on_divergence ? 1 : 0;
-    ds[s].converged = st[s].prm.converged;
-    for (size_t i = 0; i < K; ++i) stream_of[first + i] = s;
-    if (K > 0) {
-      std::memcpy(h + tot.poses_offset + first * 12 * sizeof(double), in[s].poses, K * 12 * sizeof(double));
-      std::memcpy(h + tot.corr_offset + first * kPairRow * sizeof(uint32_t), in[s].corr, K * kPairRow * sizeof(uint32_t));
-    }
-    std::memcpy(h + plan[s].model_offset, c->markers, sizeof(c->markers));
-    std::memcpy(h + plan[s].model_offset + sizeof(c->markers), c->K, sizeof(c->K));
-    if (st[s].B > 0) std::memcpy(h + plan[s].blobs_offset, st[s].blobs, 2 * (size_t)st[s].B * sizeof(double));
-  }
-  RefineMultiArgs ma{};
-  ma.up = d;
-  ma.desc = (const RefineDesc*)(d + tot.desc_offset);
-  ma.stream_of = (const int32_t*)(d + tot.stream_of_offset);
-  ma.poses = (const double*)(d + tot.poses_offset);
-  ma.corr = (const uint32_t*)(d + tot.corr_offset);
-  const size_t o_rows = up + (size_t)S * sizeof(pfmpe_refine_out), o_cov = o_rows + (size_t)H * sizeof(pfmpe_refine_row);
-  ma.out = (pfmpe_refine_out*)(d + up);
-  ma.rows = (pfmpe_refine_row*)(d + o_rows);
-  ma.cov = (double*)(d + o_cov);
-  ma.H = (int32_t)H;
-  // what comes back: the summaries, then the rows and the covariances as far as somebody wants them
-  bool want_rows = false, want_cov = false;
-  for (int s = 0; s < S; ++s) {
-    want_rows = want_rows || (rows && rows[s] && Ks[s] > 0);
-    want_cov = want_cov || (cov && cov[s] && Ks[s] > 0);
-  }
-  const size_t back = want_cov ? down : want_rows ? o_cov - up : o_rows - up;
-  HIPCHK(c0, hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, c0->stream));
-  RET(refine_multi_launch(c0, ma, S));
-  HIPCHK(c0, hipMemcpyAsync(h + up, d + up, back, hipMemcpyDeviceToHost, c0->stream));
-  HIPCHK(c0, hipStreamSynchronize(c0->stream));
-  std::memcpy(out, h + up, (size_t)S * sizeof(pfmpe_refine_out));
-  for (int s = 0; s < S; ++s) {
-    const size_t K = (size_t)Ks[s], first = (size_t)plan[s].first;
-    if (K == 0) continue;
-    if (rows && rows[s]) std::memcpy(rows[s], h + o_rows + first * sizeof(pfmpe_refine_row), K * sizeof(pfmpe_refine_row));
-    if (cov && cov[s]) std::memcpy(cov[s], h + o_cov + first * 36 * sizeof(double), K * 36 * sizeof(double));
-  }
-  return PFMPE_OK;
-}
-
-int pfmpe_host_optimise_pose(const double* markers_xyz, int M, const double* K, const double* blobs, int B,
-                             const uint32_t* corr, int n_rows, const pfmpe_refine_params* params, const double* pose12,
-                             pfmpe_refine_row* row, double* cov36) {
-  pfmpe_refine_params prm;
-  pfmpe_default_refine_params(&prm);
-  if (params) prm = *params;
-  if (!markers_xyz || !K || !pose12 || !row || M < 1 || B < 0 || n_rows < 0 || (B > 0 && !blobs) || (n_rows > 0 && !corr))
-    return PFMPE_E_ARG;
-  if (!refine_params_ok(prm) || !refine_corr_ok(corr, (size_t)n_rows, M, B) || !refine_poses_finite(pose12, 1))
-    return PFMPE_E_ARG;
-  double cov[36];
-  gn_optimise(markers_xyz, K, blobs, corr, n_rows, prm.max_iter, prm.revert_on_divergence ? 1 : 0, prm.converged, pose12,
-              *row, cov);
-  if (cov36) std::memcpy(cov36, cov, sizeof(cov));
-  return PFMPE_OK;
 }
 
 // ---- the step with its refinement (pf_tail.hpp; k_step_tail in pfmpe_refine.hip)

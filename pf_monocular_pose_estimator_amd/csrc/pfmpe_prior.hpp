@@ -82,6 +82,5 @@ inline int export_prior(pfmpe_ctx* c, int count, hipStream_t on, pfmpe_ctx* err)
   HIPCHK(err, hipGetLastError());
   return PFMPE_OK;
 }
-inline int export_prior(pfmpe_ctx* c, int count) { return export_prior(c, count, c->stream, c); }
 
 }  // namespace pfmpe_impl

@@ -1,7 +1,7 @@
 #pragma once
 // pfmpe_refine_plan.hpp — the packed upload buffer of pfmpe_refine_multi, host C++ without device code: shared by the
-// host-only entry point (pfmpe_refine_plan.cpp: pfmpe_host_refine_plan) and the device call (pfmpe_engine.hip), which
-// stages exactly this plan, and by the kernels (pfmpe_refine.hip), which read the descriptor defined here.
+// host-only entry point (pfmpe_refine_plan.cpp: pfmpe_host_refine_plan) and the device call (pfmpe_refine.hip), which
+// stages exactly this plan and whose kernels read the descriptor defined here.
 #include <cstdint>
 
 #include "../../include/pfmpe.h"

@@ -1,4 +1,5 @@
-// pfmpe_top.hip — the kernels of pfmpe_top_particles and their launches, and pfmpe_host_top_suppress.
+// pfmpe_top.hip — pfmpe_top_particles (pf_top.hpp): its kernels, their launches and the entry point, and
+// pfmpe_host_top_suppress.
 //
 // Selection: an exact radix select over the keys' bit patterns (pf_top.hpp TopKey), most significant digit first, 11
 // bits a pass.  Every kernel is one launch over the same grid of contiguous strips; nothing waits on another block.
@@ -419,8 +420,12 @@ int top_select_t(pfmpe_ctx* c, unsigned char* d, const KT* keys, int N) {
   HIPCHK(c, hipGetLastError());
   return PFMPE_OK;
 }
-}  // namespace
 
+enum { kTopKeyF32 = 0, kTopKeyF64 = 1, kTopKeyU32 = 2 };
+// The selection on the context's stream: the scratch cleared, then the radix select over the N keys (`key_type` says
+// what they are), the compaction and the sort.  Leaves the result state (state[kTopMaxPasses]), the ranked
+// pool's particle indices (kPoolIdx) and keys as doubles (kPoolKey).  *pool_count: the device address of the pool's
+// size.
 int top_select_launch(pfmpe_ctx* c, unsigned char* d_top, const void* keys, int key_type, int N,
                       const uint32_t** pool_count) {
   HIPCHK(c, hipMemsetAsync(d_top, 0, TopBuf::kClear, c->stream));
@@ -432,6 +437,10 @@ int top_select_launch(pfmpe_ctx* c, unsigned char* d_top, const void* keys, int 
   }
 }
 
+// The rest, behind the regeneration of the pool's poses into kPoolPoses (skipped when neither suppression nor a pose
+// row is wanted: poses = false): the near-matrix (suppression only), then one block that walks it and writes the
+// record and the rows of the kept candidates for `rows` rows; pose rows n_out .. rows - 1 get a harmless constant
+// (the pair kernel runs over `rows` rows: n_out is not known to the host yet).
 int top_finish_launch(pfmpe_ctx* c, unsigned char* d_top, int K, int rows, const TopThresholds& th, bool poses) {
   const bool suppress = th.min_trans != 0.0 || th.min_rot != 0.0;
   const TopState* state = (const TopState*)(d_top + TopBuf::kState);
@@ -458,8 +467,101 @@ int top_finish_launch(pfmpe_ctx* c, unsigned char* d_top, int K, int rows, const
   HIPCHK(c, hipGetLastError());
   return PFMPE_OK;
 }
+}  // namespace
 
 }  // namespace pfmpe_impl
+
+// ======================================================================================= C-ABI
+using namespace pfmpe_impl;
+
+void pfmpe_default_top_params(pfmpe_top_params* p) {
+  if (!p) return;
+  p->key = PFMPE_TOP_BY_WEIGHT;
+  p->K = 8;
+  p->min_trans = 0.0;
+  p->min_rot = 0.0;
+}
+
+int pfmpe_top_particles(pfmpe_ctx* c, const pfmpe_top_params* params, const pfmpe_assoc_in* in, pfmpe_top_out* out,
+                        int32_t* index, double* key_value, double* poses, uint32_t* corr, int32_t* n_corr) {
+  if (!c) return PFMPE_E_ARG;
+  if (!params || !out) return fail(c, PFMPE_E_ARG, "top_particles: null params or out");
+  const pfmpe_top_params prm = *params;
+  if (prm.key != PFMPE_TOP_BY_WEIGHT && prm.key != PFMPE_TOP_BY_COUNT) return fail(c, PFMPE_E_ARG, "top_particles: bad key");
+  if (prm.K < 0 || prm.K > PFMPE_TOP_MAX) return fail(c, PFMPE_E_ARG, "top_particles: K out of range");
+  if (!(prm.min_trans >= 0.0) || !std::isfinite(prm.min_trans))
+    return fail(c, PFMPE_E_ARG, "top_particles: min_trans must be finite and >= 0");
+  if (!(prm.min_rot >= 0.0 && prm.min_rot <= M_PI)) return fail(c, PFMPE_E_ARG, "top_particles: min_rot outside [0, pi]");
+  const double* blobs = nullptr;
+  int B = 0;
+  if (in) RET(resolve_blobs(c, "top_particles", in, &blobs, &B));
+  if (!c->has_prior || !c->has_last) return fail(c, PFMPE_E_STATE, "top_particles: no step yet");
+  if (prm.key == PFMPE_TOP_BY_COUNT) {
+    if (!c->record_counts || !c->d_counts.get()) return fail(c, PFMPE_E_STATE, "top_particles: PFMPE_OPT_RECORD_COUNTS off");
+    if (!c->last_accepted) return fail(c, PFMPE_E_STATE, "top_particles: last step did not resample");
+  }
+  if (in && !c->has_model) return fail(c, PFMPE_E_STATE, "top_particles: blobs given without a model");
+  RET(set_device(c));
+  RET(c->d_top.ensure(c, TopBuf::bytes()));
+  RET(c->h_top.ensure(c, TopRows::bytes(PFMPE_TOP_MAX)));
+  const int N = c->N;
+  const int rows = std::min(prm.K, N);  // n_out <= min(K, n_positive): the rows the record is laid out for
+  const TopThresholds th = top_thresholds(prm.min_trans, prm.min_rot);
+  const bool suppress = prm.min_trans != 0.0 || prm.min_rot != 0.0;
+  const bool pairs = in && rows > 0;
+  const bool want_poses = suppress || pairs || (poses && rows > 0);
+  unsigned char* d = c->d_top.get();
+
+  const void* keys = c->d_w[c->last_kept_slot].get();
+  int key_type = c->state_dtype == PFMPE_STATE_F64 ? kTopKeyF64 : kTopKeyF32;
+  if (prm.key == PFMPE_TOP_BY_COUNT) {
+    keys = c->d_counts.get();
+    key_type = kTopKeyU32;
+  }
+  const uint32_t* pool_count = nullptr;
+  RET(top_select_launch(c, d, keys, key_type, N, &pool_count));
+  // the poses of the ranked pool only (all of it for the suppression walk, else the rows wanted), as k_regen makes
+  // them: bracketed as aux like every regeneration
+  if (want_poses)
+    RET(dispatch_regen_list(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), (const int32_t*)(d + TopBuf::kPoolIdx),
+                            pool_count, suppress ? kTopPool : rows, (double*)(d + TopBuf::kPoolPoses)));
+  RET(top_finish_launch(c, d, prm.K, rows, th, want_poses));
+  unsigned char* rec = d + TopBuf::kRecord;
+  if (pairs) {
+    // the rows' pairs as pfmpe_get_pairs derives them: the blob table as assoc_prepare builds it, the pair kernel in
+    // rows mode over the dense list of the kept rows' poses (it bounds its range by first / count alone; count is `rows`, the rows behind
+    // n_out hold a constant pose and are not returned)
+    const size_t tbytes = build_table(c, blobs, B, c->h_table.get());
+    const GridHdr gh = *(const GridHdr*)(c->h_table.get() + grid_off(c, B));
+    HIPCHK(c, hipMemcpyAsync(c->d_table.get(), c->h_table.get(), tbytes, hipMemcpyHostToDevice, c->stream));
+    AssocArgs aa{};
+    aa.dense = (const double*)(rec + TopRows::poses(rows));
+    aa.corr = (uint32_t*)(rec + TopRows::corr(rows));
+    aa.n_corr = (int32_t*)(rec + TopRows::n_corr(rows));
+    aa.first = 0;
+    aa.count = rows;
+    RET(assoc_rows_launch(c, B, c->d_table.get(), tbytes, gh, aa));
+  }
+  // one read-back: the record and the rows (without the pair rows when no blobs were given)
+  unsigned char* h = c->h_top.get();
+  const size_t bytes = pairs ? TopRows::bytes(rows) : TopRows::n_corr(rows);
+  HIPCHK(c, hipMemcpyAsync(h, rec, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  RET(harvest_timing(c));
+  const TopRecord r = *(const TopRecord*)h;
+  if (r.n_out < 0 || r.n_out > rows) return fail(c, PFMPE_E_STATE, "top_particles: inconsistent record");
+  out->n = N;
+  out->n_positive = r.n_positive;
+  out->n_out = r.n_out;
+  out->n_examined = r.n_examined;
+  const size_t n = (size_t)r.n_out;
+  if (index) std::memcpy(index, h + TopRows::index(rows), n * sizeof(int32_t));
+  if (key_value) std::memcpy(key_value, h + TopRows::kKey, n * sizeof(double));
+  if (poses) std::memcpy(poses, h + TopRows::poses(rows), n * 12 * sizeof(double));
+  if (pairs && corr) std::memcpy(corr, h + TopRows::corr(rows), n * kPairRow * sizeof(uint32_t));
+  if (pairs && n_corr) std::memcpy(n_corr, h + TopRows::n_corr(rows), n * sizeof(int32_t));
+  return PFMPE_OK;
+}
 
 int pfmpe_host_top_suppress(const double* poses, int32_t P, int32_t K, double min_trans, double min_rot, int32_t* keep,
                             int32_t* n_out, int32_t* n_examined) {

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time pfmpe_assoc_stats after one step at the C2 and C3 sizes, with pfmpe_cloud_stats(POSTERIOR) on the same
-context beside it as the yardstick (the other whole-set reduction of the resident prior).
+context beside it as the yardstick (the other whole-set reduction of the resident prior), and pfmpe_get_pairs over the
+whole set (the rows kernel with its read-back).
 
 Every call is blocking, so each is timed on the host around the call: 5 warm-up calls, then the median of 20.  Run
 it on an otherwise idle device.  Prints one row per size and one JSON line.
@@ -58,15 +59,19 @@ def main():
             t_post = median_ms(lambda: eng.assoc_stats(pf.ASSOC_POSTERIOR, blobs=fr.blobs), args.warmup, args.reps)
             t_prop = median_ms(lambda: eng.assoc_stats(pf.ASSOC_PROPAGATED, blobs=fr.blobs), args.warmup, args.reps)
             t_cloud = median_ms(lambda: eng.cloud_stats(pf.CLOUD_POSTERIOR, ref), args.warmup, args.reps)
+            t_pairs = median_ms(lambda: eng.get_pairs(pf.ASSOC_POSTERIOR, blobs=fr.blobs), args.warmup, args.reps)
+            t_pairs_prop = median_ms(lambda: eng.get_pairs(pf.ASSOC_PROPAGATED, blobs=fr.blobs), args.warmup, args.reps)
             a = eng.assoc_stats(pf.ASSOC_POSTERIOR, blobs=fr.blobs)
         finally:
             eng.close()
         rows.append({"config": name, "N": cfg.N, "M": cfg.M, "B": cfg.B, "diag": args.diag,
                      "resampled": int(out.resampled), "assoc_posterior_ms": t_post, "assoc_propagated_ms": t_prop,
-                     "cloud_posterior_ms": t_cloud, "n_any": int(a["n_any"]),
+                     "cloud_posterior_ms": t_cloud, "get_pairs_posterior_ms": t_pairs,
+                     "get_pairs_propagated_ms": t_pairs_prop, "n_any": int(a["n_any"]),
                      "mode_share": [round(float(v) / cfg.N, 4) for v in a["mode_votes"]]})
         print(f"{name}: N={cfg.N} M={cfg.M} B={cfg.B}  assoc_stats(POSTERIOR) {t_post:.3f} ms  "
-              f"assoc_stats(PROPAGATED) {t_prop:.3f} ms  cloud_stats(POSTERIOR) {t_cloud:.3f} ms", flush=True)
+              f"assoc_stats(PROPAGATED) {t_prop:.3f} ms  cloud_stats(POSTERIOR) {t_cloud:.3f} ms  "
+              f"get_pairs(POSTERIOR) {t_pairs:.3f} ms  get_pairs(PROPAGATED) {t_pairs_prop:.3f} ms", flush=True)
     print(json.dumps({"assoc_stats_time": rows}))
     return 0
 

@@ -405,3 +405,130 @@ def test_errors():
         assert eng.get_pairs(pf.ASSOC_POSTERIOR, blobs=blobs)[1].shape == (1000,)
     finally:
         eng.close()
+
+
+# ---- 9. the single call's own codes and texts
+def test_single_call_error_texts():
+    """Every code and text of pfmpe_assoc_stats that an argument or a state can reach, in the order of its checks.  (A
+    blob table that exceeds the LDS and an inconsistent votes table cannot be provoked through the API: the largest
+    table max_blobs admits fits, and the bins are the kernel's own.)"""
+    st = _stream(5, 50, 1000)
+    blobs = st.frames[0].blobs
+    eng = pf.Engine(device=0, max_particles=1000, max_blobs=64, state_dtype=pf.STATE_F32)
+    lib, up, dp = eng.lib, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
+    out = _capi.AssocOut()
+    keep = np.ascontiguousarray(blobs, dtype=np.float64)
+
+    def call(which=pf.ASSOC_POSTERIOR, B=50, ptr=True, bank_frame=-1, null_in=False, null_out=False):
+        ai = _capi.AssocIn()
+        ai.blobs = keep.ctypes.data_as(dp) if ptr else dp()
+        ai.B = B
+        ai.bank_frame = bank_frame
+        rc = lib.pfmpe_assoc_stats(eng.ctx, which, None if null_in else ctypes.byref(ai),
+                                   None if null_out else ctypes.byref(out), up())
+        return rc, eng.last_error()
+
+    try:
+        # the argument checks come before the state checks: a context without a model reports them
+        assert call(null_out=True) == (pf.E_ARG, "assoc_stats: null out")
+        assert call(null_in=True) == (pf.E_ARG, "assoc_stats: bad arguments")
+        assert call(which=2) == (pf.E_ARG, "assoc_stats: bad arguments")
+        assert call(which=-1) == (pf.E_ARG, "assoc_stats: bad arguments")
+        assert call(B=-1) == (pf.E_ARG, "assoc_stats: B < 0")
+        assert call(bank_frame=0) == (pf.E_ARG, "assoc_stats: bank_frame out of range")
+        assert call(B=4, ptr=False) == (pf.E_ARG, "assoc_stats: null blobs")
+        assert call(B=65) == (pf.E_CAP, "assoc_stats: B exceeds max_blobs")
+        assert call() == (pf.E_STATE, "assoc_stats: set_model and a particle set first")
+        eng.set_model(st.markers, st.K)
+        assert call() == (pf.E_STATE, "assoc_stats: set_model and a particle set first")
+        eng.set_prior(st.prior(fast=True))
+        assert call(which=pf.ASSOC_PROPAGATED) == (pf.E_STATE, "assoc_stats(propagated): no step yet")
+        eng.stage_blob_bank([blobs])
+        assert call(bank_frame=1) == (pf.E_ARG, "assoc_stats: bank_frame out of range")
+        assert call()[0] == pf.OK and call(bank_frame=0)[0] == pf.OK and out.B == 50
+    finally:
+        eng.close()
+
+
+# ---- 10. the single call and the batch on one context's scratch
+def _same_stats(a, b, what):
+    assert a.keys() == b.keys(), what
+    for k in a:
+        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), (what, k)
+
+
+def test_single_call_shares_scratch_with_batches():
+    """A batch of three B = 50 entries, a single call with B = 1, a single call with B = 50 on a context that has only
+    ever run B = 1, a batch again: every record and table equals that of a context that ran nothing else."""
+    made = [_stepped(5, 50, 1000, pf.STATE_F32) for _ in range(4)]
+    a, c, fresh50, fresh1 = [m[0] for m in made]
+    blobs = made[0][3]
+    try:
+        ref50 = {w: fresh50.assoc_stats(w, blobs=blobs) for w in WHICH}
+        ref1 = {w: fresh1.assoc_stats(w, blobs=blobs[:1]) for w in WHICH}
+        assert all(ref50[w]["n_any"] > 0 for w in WHICH)
+        whichs = [pf.ASSOC_PROPAGATED, pf.ASSOC_POSTERIOR, pf.ASSOC_PROPAGATED]
+        for s, got in enumerate(pf.Engine.assoc_stats_multi([a] * 3, whichs, [blobs] * 3)):
+            _same_stats(got, ref50[whichs[s]], ("first batch", s))
+        for w in WHICH:
+            _same_stats(a.assoc_stats(w, blobs=blobs[:1]), ref1[w], ("single B=1 after a batch", w))
+        for w in WHICH:
+            _same_stats(c.assoc_stats(w, blobs=blobs[:1]), ref1[w], ("single B=1", w))
+        for w in WHICH:
+            _same_stats(c.assoc_stats(w, blobs=blobs), ref50[w], ("single B=50 after B=1", w))
+        for s, got in enumerate(pf.Engine.assoc_stats_multi([a, c, a], whichs, [blobs] * 3)):
+            _same_stats(got, ref50[whichs[s]], ("second batch", s))
+    finally:
+        for e in (a, c, fresh50, fresh1):
+            e.close()
+
+
+# ---- 11. what the single call adds to the kernel statistics
+# read once on the build whose single call had a path of its own: launches per kernel name added by one call.  Neither
+# adds any: the association launches are not bracketed, the step's own brackets are harvested by the statistics read
+# before the call, and a PROPAGATED call's regeneration opens its aux bracket only inside a sampled frame.
+SINGLE_CALL_ADDS = {pf.ASSOC_POSTERIOR: {}, pf.ASSOC_PROPAGATED: {}}
+
+
+def test_single_call_kernel_stats():
+    """With every frame sampled (OPT_TIMING 1): the launches a POSTERIOR and a PROPAGATED single call add to
+    pfmpe_get_kernel_stats (the kernels not named in SINGLE_CALL_ADDS: none)."""
+    st = _stream(5, 50, 1000)
+    eng = make_engine(1000, st.markers, st.K, pf.STATE_F32, pf.RNG_PHILOX)
+    try:
+        eng.set_option(pf.OPT_TIMING, 1)
+        eng.set_prior(st.prior(fast=True))
+        fr = st.frames[0]
+        eng.step(_frame(eng, fr))
+        for which in (pf.ASSOC_POSTERIOR, pf.ASSOC_PROPAGATED):
+            before = eng.kernel_stats()
+            eng.assoc_stats(which, blobs=fr.blobs)
+            after = eng.kernel_stats()
+            added = {k: after[k][0] - before[k][0] for k in after if after[k][0] != before[k][0]}
+            print("which", which, "adds", added)
+            assert added == SINGLE_CALL_ADDS[which]
+    finally:
+        eng.close()
+
+
+# ---- 12. the single call against a batch entry without blobs
+@pytest.mark.parametrize("N", [1, 257])
+def test_single_equals_batch_entry_without_blobs(N):
+    eng, st, mk, blobs, _ = _stepped(5, 50, N, pf.STATE_F32)
+    none = np.zeros((0, 2))
+    try:
+        for which in WHICH:
+            want = _raw_stats(eng, which, none)
+            ai, keep = eng._assoc_in(none, -1)
+            ins = (_capi.AssocMultiIn * 1)()
+            ins[0].blobs = ai
+            ins[0].which = which
+            outs = (_capi.AssocOut * 1)()
+            votes = np.zeros(eng.M, dtype=np.uint32)
+            vps = (ctypes.POINTER(ctypes.c_uint32) * 1)(votes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+            ctxs = (ctypes.c_void_p * 1)(eng.ctx.value)
+            assert eng.lib.pfmpe_assoc_stats_multi(ctxs, 1, ins, outs, vps) == pf.OK
+            assert bytes(outs[0]) + votes.tobytes() == want
+            assert outs[0].n == N and outs[0].n_any == 0 and np.all(votes == N)
+    finally:
+        eng.close()
