@@ -1026,7 +1026,7 @@ enum { PFMPE_K_PROPAGATE = 0, /* k_propagate_weigh (+ last-block iteration reduc
        PFMPE_K_RESAMPLE = 1,  /* k_resample / k_resample_owners: resampling           */
        PFMPE_K_AUX = 2,       /* hand-off kernels (k_group*, k_top*), regeneration   */
        PFMPE_K_FRAME = 3,     /* k_frame: the whole frame in one launch              */
-       PFMPE_K_ROI = 4,       /* k_roi_stage + k_roi_multi* (pfmpe_predict_roi[_multi]) */
+       PFMPE_K_ROI = 4,       /* k_batch_stage + k_roi_multi* (pfmpe_predict_roi[_multi]) */
        PFMPE_K_FINAL = 5,     /* k_resample_final (non-deferred frames): the record   */
        PFMPE_K_P3P_HIST = 6,  /* k_p3p_hist: initialisation histogram                */
        PFMPE_K_P3P_CHECK = 7, /* k_p3p_check: checkCorrespondences of all candidates */

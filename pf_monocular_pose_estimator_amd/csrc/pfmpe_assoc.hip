@@ -3,8 +3,8 @@
 // pfmpe_assoc_stats is a batch of one), each per state type x kept set / resident prior x marker bucket x pruning
 // option; the batch's plan, the host summary and gate, and the entry points.  A TU of its own so the instances build
 // beside the others.
+#include "pf_batch.hpp"
 #include "pf_likelihood.hpp"
-#include "pf_roi.hpp"  // roi_stream_of_block (the batch)
 #include "pfmpe_args.hpp"
 
 namespace pfmpe {
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void k_assoc_votes(const FrameArgsT<T> fa, 
 // ---- the votes of S entries in one batch (pfmpe_assoc_stats_multi; S = 1: pfmpe_assoc_stats).  One flat grid per
 // kernel instance the batch needs (set kind x marker bucket x pruning option): a launch's head names its entries and
 // the prefix of their blocks (entry g of the launch owns blocks first[g] .. first[g + 1], a block per 256 of its N
-// particles up to kAssocMaxBlocks), and a block finds its entry by one wave-wide comparison (roi_stream_of_block: the
+// particles up to kAssocMaxBlocks), and a block finds its entry by one wave-wide comparison (batch_stream_of_block: the
 // index is block-uniform, so the head and the descriptor are read with scalar loads).  The descriptor holds what
 // k_assoc_votes gets as arguments: the frame arguments, the entry's table in the batch's device image, its slice of
 // the batch's bins, its particles and whether its bins fit in LDS behind its table.  The block's LDS is laid out for
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void k_assoc_votes(const FrameArgsT<T> fa, 
 // own slice, so an entry's table does not depend on its neighbours or on the grid.  No waits on other blocks.
 constexpr int kAssocMaxStreams = 64;
 constexpr int kAssocMaxLaunches = 16;  // 2 set kinds x 4 marker buckets x 2 pruning options
-static_assert(kAssocMaxStreams <= kRoiMaxStreams, "AssocHead::first is read by roi_stream_of_block");
+static_assert(kAssocMaxStreams <= kBatchMaxStreams, "AssocHead::first is read by batch_stream_of_block");
 struct AssocHead {  // one launch of the batch
   int32_t S, pad;
   int32_t first[kAssocMaxStreams + 1];  // first block of the launch's entry g; first[S] = all its blocks
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(kBlock) void k_assoc_votes_multi(const AssocHead* _
                                                              const AssocDesc<T>* __restrict__ descs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ LdsConst<T> sc;
-  const int g = roi_stream_of_block(hd->first, hd->S, blockIdx.x);
+  const int g = batch_stream_of_block(hd->first, hd->S, blockIdx.x);
   const int b0 = __builtin_amdgcn_readfirstlane(hd->first[g]);
   const int b1 = __builtin_amdgcn_readfirstlane(hd->first[g + 1]);
   const AssocDesc<T>& d = descs[__builtin_amdgcn_readfirstlane(hd->entry[g])];
@@ -427,18 +427,8 @@ int assoc_run(pfmpe_ctx* const* ctxs, int S, AssocEntry* e, pfmpe_assoc_out* out
               const std::string& who, bool single) {
   pfmpe_ctx* c0 = ctxs[0];
   auto at = [&](int s) { return single ? who + ": " : who + ": stream " + std::to_string(s) + ": "; };
-  // the distinct contexts in order of first appearance (ctxs[0] first), and which of them have a PROPAGATED entry
-  std::vector<pfmpe_ctx*> distinct;
-  std::vector<char> regen;
-  for (int s = 0; s < S; ++s) {
-    size_t m = 0;
-    while (m < distinct.size() && distinct[m] != ctxs[s]) ++m;
-    if (m == distinct.size()) {
-      distinct.push_back(ctxs[s]);
-      regen.push_back(0);
-    }
-    if (e[s].which == PFMPE_ASSOC_PROPAGATED) regen[m] = 1;
-  }
+  BatchMembers members(who.c_str(), S);  // flagged: a context with a PROPAGATED entry (all its entries read one regenerated set)
+  for (int s = 0; s < S; ++s) members.add(ctxs[s], e[s].which == PFMPE_ASSOC_PROPAGATED);
   RET(set_device(c0));
   // ---- the image: every entry's table, built in the leader's pinned block behind the heads and descriptors (host
   // work: nothing is on the device yet).  The block holds the largest table each entry can get.
@@ -481,8 +471,6 @@ int assoc_run(pfmpe_ctx* const* ctxs, int S, AssocEntry* e, pfmpe_assoc_out* out
   const size_t bins_at = (img_bytes + 255) / 256 * 256;
   const size_t bins_bytes = (size_t)total.bins_words * sizeof(uint32_t);
   RET(c0->d_assocm.grow(c0, bins_at + bins_bytes, (bins_at + bins_bytes) * 2));
-  for (size_t m = 0; m < distinct.size(); ++m)
-    if (regen[m]) RET(ensure_xfer(distinct[m]));
   // one upload (heads, descriptors, tables) and one memset of all bins, ahead of the leader's kernels: a copy behind
   // the regeneration launch would wait for it across engines, 11 us per PROPAGATED call at C2
   uint32_t* dbins = (uint32_t*)(c0->d_assocm.get() + bins_at);
@@ -492,23 +480,11 @@ int assoc_run(pfmpe_ctx* const* ctxs, int S, AssocEntry* e, pfmpe_assoc_out* out
   });
   HIPCHK(c0, hipMemcpyAsync(c0->d_assocm.get(), himg, img_bytes, hipMemcpyHostToDevice, c0->stream));
   HIPCHK(c0, hipMemsetAsync(dbins, 0, bins_bytes, c0->stream));
-  // each PROPAGATED context's kept propagated set once: into its own d_xfer, on its own stream (set_device: after
-  // whatever it has pending elsewhere), bracketed as aux like every regeneration; all its entries read that set
-  for (size_t m = 0; m < distinct.size(); ++m) {
-    pfmpe_ctx* c = distinct[m];
-    if (!regen[m]) continue;
-    int r_ = c != c0 ? set_device(c) : (int)PFMPE_OK;
-    const bool launched = r_ == PFMPE_OK;
-    if (launched) r_ = dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get());
-    if (r_) {
-      (void)hipStreamSynchronize(c0->stream);  // the upload reads the pinned image, which the next call rewrites
-      return (c == c0 || !launched) ? r_ : fail(c0, r_, who + ": " + c->err);
-    }
+  if (const int r_ = members.regen()) {
+    (void)hipStreamSynchronize(c0->stream);  // the upload reads the pinned image, which the next call rewrites
+    return r_;
   }
-  // every member's work so far, that regeneration included, is ordered before the batch; a failure from here on gives
-  // the members their ordering state back (the leader's own was set by set_device)
-  OrderGuard members(distinct.data(), (int)distinct.size());
-  RET(members.order(1, c0->stream, c0));
+  RET(members.order());
   visit_state(c0, [&](auto s) {
     assoc_votes_launch<typename decltype(s)::T, typename decltype(s)::SP>(ctxs, e, S, total.launches, himg,
                                                                           c0->d_assocm.get(), lds);
@@ -516,10 +492,7 @@ int assoc_run(pfmpe_ctx* const* ctxs, int S, AssocEntry* e, pfmpe_assoc_out* out
   HIPCHK(c0, hipGetLastError());
   const uint32_t* hbins = (const uint32_t*)(himg + bins_at);
   HIPCHK(c0, hipMemcpyAsync((void*)hbins, dbins, bins_bytes, hipMemcpyDeviceToHost, c0->stream));
-  if (hipStreamSynchronize(c0->stream) != hipSuccess) return fail(c0, PFMPE_E_HIP, who + ": stream synchronise failed");
-  members.commit();  // nothing of the batch is pending: no member needs a fence
-  for (pfmpe_ctx* c : distinct)  // (as every single call ends: the brackets of sampled frames still pending)
-    if (const int r_ = harvest_timing(c)) return c == c0 ? r_ : fail(c0, r_, who + ": " + c->err);
+  RET(members.finish());
   // the tables are checked before any output is written
   for (int s = 0; s < S; ++s) {
     pfmpe_assoc_out o;

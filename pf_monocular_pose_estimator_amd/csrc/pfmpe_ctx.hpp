@@ -1,7 +1,7 @@
 #pragma once
 // pfmpe_ctx.hpp — the context and what every translation unit of the library does with it: owned buffers, errors,
-// stream ordering, the timed launch wrappers, the frame record and the shared preambles of the entry points.  No
-// kernel: the step's launch sequences are in pfmpe_seq.hpp, each side call's kernels in the header of its subject.
+// stream ordering, the timed launch wrappers and scope, the frame record, the entries' shared preambles, a blocking
+// batch's members.  No kernel: the step's sequences are in pfmpe_seq.hpp, a side call's kernels with its subject.
 //
 // Replaces the PF block of PoseEstimator::estimateBodyPose (pf_mpe_lib/src/pose_estimator.cpp:475-733)
 // behind include/pfmpe.h.  Device layout (DESIGN.md "HBM layout"): particle state as 12 SoA planes
@@ -24,6 +24,7 @@
 #include <string>
 #include <map>
 #include <memory>
+#include <optional>
 #include <type_traits>
 #include <vector>
 
@@ -509,6 +510,19 @@ inline void klaunch(pfmpe_ctx* c, void (*kernel)(KArgs...), dim3 grid, dim3 bloc
   }
 }
 
+// The timing scope of a host-synchronous entry (detector, ROI, initialisation): fn with the brackets of c (a batch's
+// leader) on.  timing_now is cleared on every exit; a failure drops the brackets this call opened and left unharvested
+// (one may lack its end event, which the next harvest would trip over), the pending ones of earlier frames stay.
+template <typename F>
+int timed(pfmpe_ctx* c, F&& fn) {
+  const size_t ev_mark = c->ev_used;
+  c->timing_now = c->timing > 0;
+  const int rc = fn();
+  c->timing_now = false;
+  if (rc != PFMPE_OK && c->ev_used > ev_mark) c->ev_used = ev_mark;
+  return rc;
+}
+
 // Brackets are harvested lazily: a timed PF frame leaves its event pairs pending (no stream synchronize on the
 // frame path, which had added a host round trip to every sampled frame: at --steps 20 one frame in two), and
 // they are read here, when the pool holds kHarvestPairs of them, at pfmpe_get_kernel_stats, or after the
@@ -719,6 +733,61 @@ class OrderGuard {
   pfmpe_ctx* const* cs_;
   std::vector<std::pair<hipStream_t, std::shared_ptr<BatchFence>>> saved_;
   bool committed_ = false;
+};
+
+// The members of a blocking batch (ROI, cloud statistics, association, the streams detector): the distinct contexts in
+// order of first appearance, the leader first, each with a flag "its kept propagated set is read", and the steps such
+// a runner takes with them.  A member's failure is reported on the leader as "<who>: <the member's text>".
+class BatchMembers {
+ public:
+  BatchMembers(const char* who, int n) : who_(who) {  // n: at most so many members (no growth on a per-frame call)
+    cs_.reserve(n);
+    flag_.reserve(n);
+  }
+  void add(pfmpe_ctx* c, bool flag = false) {  // before order(); a context joins once, its flag sticks
+    const size_t m = std::find(cs_.begin(), cs_.end(), c) - cs_.begin();
+    if (m == cs_.size()) {
+      cs_.push_back(c);
+      flag_.push_back(0);
+    }
+    if (flag) flag_[m] = 1;
+  }
+  // every flagged member's kept propagated set once, as its single call regenerates it: into its own d_xfer (all of
+  // them allocated first), on its own stream (set_device: after whatever it has pending elsewhere), bracketed as aux
+  int regen() {
+    for (size_t m = 0; m < cs_.size(); ++m)
+      if (flag_[m]) RET(ensure_xfer(cs_[m]));
+    for (size_t m = 0; m < cs_.size(); ++m) {
+      pfmpe_ctx* c = cs_[m];
+      if (!flag_[m]) continue;
+      if (c != cs_[0]) RET(set_device(c));
+      if (const int r_ = dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()))
+        return report(c, r_);
+    }
+    return PFMPE_OK;
+  }
+  // every member's work so far, a regeneration included, before the batch on the leader's stream (through OrderGuard)
+  int order() {
+    guard_.emplace(cs_.data(), (int)cs_.size());
+    return guard_->order(1, cs_[0]->stream, cs_[0]);
+  }
+  void commit() { guard_->commit(); }  // after order(), as finish(): nothing is pending, no member needs a fence
+  // the end of the call: one synchronise, so the commit, then every member's pending brackets (sampled frames' too)
+  int finish() {
+    if (hipStreamSynchronize(cs_[0]->stream) != hipSuccess)
+      return fail(cs_[0], PFMPE_E_HIP, std::string(who_) + ": stream synchronise failed");
+    commit();
+    for (pfmpe_ctx* c : cs_)
+      if (const int r_ = harvest_timing(c)) return report(c, r_);
+    return PFMPE_OK;
+  }
+
+ private:
+  int report(pfmpe_ctx* c, int rc) { return c == cs_[0] ? rc : fail(cs_[0], rc, std::string(who_) + ": " + c->err); }
+  const char* who_;
+  std::vector<pfmpe_ctx*> cs_;
+  std::vector<char> flag_;
+  std::optional<OrderGuard> guard_;
 };
 
 // Blocks per batch accepted by pfmpe_step_multi (PFMPE_E_CAP above): the size the GPU tests cover

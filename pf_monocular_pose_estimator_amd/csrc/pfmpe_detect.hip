@@ -25,6 +25,7 @@
 // pfmpe_find_leds_streams runs that sequence over the images of several cameras: a descriptor carries its own K and
 // the address of its ROI's top-left pixel, in its context's staged image or in the crops the batch uploads
 // (pfmpe_detect_plan.hpp: only the ROIs' pixels of a host image cross the host link; k_detm_pull).
+#include "pf_batch.hpp"
 #include "pfmpe_ctx.hpp"
 #include "pfmpe_detect_plan.hpp"
 
@@ -441,10 +442,10 @@ __global__ __launch_bounds__(kEmitBlock) void k_det_emit(const int* __restrict__
 // indexing, so labels and roots are the numbers the single call computes and the output order is its order).  The
 // grids are flat: ROI r owns the blocks first[r] .. first[r + 1) of a stage (its 16 x 16 tiles, its 32 x 32 tiles,
 // its 256-pixel ranges), so a small ROI next to a large one launches its own tile count only.  A block finds its
-// ROI by one wave-wide comparison against the prefix (R <= 64 = the wave size: lane r holds first[r]), which
-// replaces a block -> ROI map and its upload.
+// ROI by one wave-wide comparison against the prefix (batch_stream_of_block, pf_batch.hpp), which replaces a
+// block -> ROI map and its upload.
 constexpr int kDetMaxRois = PFMPE_DETECT_MAX_ROIS;
-static_assert(kDetMaxRois <= 64, "det_roi_of_block compares one prefix entry per lane of a wave");
+static_assert(kDetMaxRois <= kBatchMaxStreams, "DetBatch::first* are read by batch_stream_of_block");
 struct DetBatch {  // head of the batch's device image, the descriptors follow
   int R, pad[3];
   int first16[kDetMaxRois], first32[kDetMaxRois], firstpix[kDetMaxRois];  // first block of ROI r per stage
@@ -465,21 +466,8 @@ struct DetDesc {
 constexpr int kDetWorkCount = kDetMaxRois;
 constexpr size_t kDetCounterBytes = (kDetMaxRois + 1) * sizeof(int);
 
-__device__ __forceinline__ int det_roi_of_block(const int* __restrict__ first, const int R, const int b) {
-  const int lane = threadIdx.x & 63;
-  const bool le = lane < R && first[lane] <= b;  // first[0] = 0: at least one
-  return __builtin_amdgcn_readfirstlane(__popcll(__ballot(le)) - 1);
-}
-
-// The batch's first launch: the head and the descriptors from the host's pinned image into device memory (the
-// stages' blocks then read them from L2, not over the host link), and the counters to zero.  In place of an async
-// copy and a memset: measured at R = 1, those two commands cost the call 20 us of wall time over the single call.
-constexpr int kStageBlock = 1024;
-__global__ __launch_bounds__(kStageBlock) void k_detm_stage(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst,
-                                                            const int nwords, int* __restrict__ counters) {
-  for (int i = threadIdx.x; i < nwords; i += kStageBlock) dst[i] = src[i];
-  if (threadIdx.x <= kDetWorkCount) counters[threadIdx.x] = 0;
-}
+constexpr int kStageBlock = 1024;  // the batch's first launch (k_batch_stage: head, descriptors, counters to zero)
+static_assert(kDetWorkCount + 1 <= kStageBlock, "k_batch_stage zeroes one counter per thread");
 
 // The streams batch's crops (pfmpe_find_leds_streams) from the leader's host-mapped pinned buffer into the scratch:
 // n 16-byte words, one load per lane, consecutive lanes consecutive words, blocks grid-striding (the grid is sized
@@ -494,7 +482,7 @@ __global__ __launch_bounds__(kPullBlock) void k_detm_pull(const uint4* __restric
 
 __global__ __launch_bounds__(kDetTile* kDetTile) void k_detm_mask(const DetBatch* __restrict__ hd,
                                                                    const DetDesc* __restrict__ descs) {
-  const int roi = det_roi_of_block(hd->first16, hd->R, blockIdx.x);
+  const int roi = batch_stream_of_block(hd->first16, hd->R, blockIdx.x);
   const DetDesc& d = descs[roi];
   const int t = blockIdx.x - hd->first16[roi];
   const int ty = t / d.tiles16_x, tx = t - ty * d.tiles16_x;
@@ -503,7 +491,7 @@ __global__ __launch_bounds__(kDetTile* kDetTile) void k_detm_mask(const DetBatch
 
 __global__ __launch_bounds__(kLabelBlock) void k_detm_label(const DetBatch* __restrict__ hd,
                                                             const DetDesc* __restrict__ descs) {
-  const int roi = det_roi_of_block(hd->first32, hd->R, blockIdx.x);
+  const int roi = batch_stream_of_block(hd->first32, hd->R, blockIdx.x);
   const DetDesc& d = descs[roi];
   const int t = blockIdx.x - hd->first32[roi];
   const int ty = t / d.tiles32_x, tx = t - ty * d.tiles32_x;
@@ -513,7 +501,7 @@ __global__ __launch_bounds__(kLabelBlock) void k_detm_label(const DetBatch* __re
 constexpr int kPixBlock = 256;  // an ROI's pixels are rounded up to whole blocks: a block belongs to one ROI
 __global__ __launch_bounds__(kPixBlock) void k_detm_merge(const DetBatch* __restrict__ hd,
                                                           const DetDesc* __restrict__ descs) {
-  const int roi = det_roi_of_block(hd->firstpix, hd->R, blockIdx.x);
+  const int roi = batch_stream_of_block(hd->firstpix, hd->R, blockIdx.x);
   const DetDesc& d = descs[roi];
   det_merge_pixel(d.a, d.nbr, d.label, (int64_t)(blockIdx.x - hd->firstpix[roi]) * kPixBlock + threadIdx.x);
 }
@@ -522,7 +510,7 @@ __global__ __launch_bounds__(kPixBlock) void k_detm_merge(const DetBatch* __rest
 __global__ __launch_bounds__(kPixBlock) void k_detm_roots(const DetBatch* __restrict__ hd,
                                                           const DetDesc* __restrict__ descs, int* __restrict__ counters,
                                                           uint32_t* __restrict__ work) {
-  const int roi = det_roi_of_block(hd->firstpix, hd->R, blockIdx.x);
+  const int roi = batch_stream_of_block(hd->firstpix, hd->R, blockIdx.x);
   const DetDesc& d = descs[roi];
   const int64_t i = (int64_t)(blockIdx.x - hd->firstpix[roi]) * kPixBlock + threadIdx.x;
   if (i >= (int64_t)d.a.W * d.a.H || !d.mask[i]) return;
@@ -667,6 +655,18 @@ int detm_buffers(pfmpe_ctx* c, int R, DetDesc* descs, size_t crop_bytes, size_t*
   return PFMPE_OK;
 }
 
+// one ROI's output record h (pinned, written by the emit kernel) -> the caller's arrays (max_out rows) and out
+void det_take(const DetOutHost& h, double* blobs, float* distorted, int max_out, pfmpe_detect_out* out) {
+  const int nw = std::min(std::min(h.n, max_out), kMaxBlobs);
+  if (nw > 0) {
+    std::memcpy(blobs, h.und, 2 * (size_t)nw * sizeof(double));
+    if (distorted) std::memcpy(distorted, h.dist, 2 * (size_t)nw * sizeof(float));
+  }
+  out->n = h.n;
+  out->n_components = h.n_components;
+  out->overflow = h.overflow;
+}
+
 // A batch on its leader c (pfmpe_find_leds_multi, pfmpe_find_leds_streams), after every check: the pinned image of the
 // batch head and the descriptors, the scratch, the launch sequence, one synchronise, the results.  fill(r, d) sets
 // entry r's d.a and, for an entry that reads an image where it is, d.pix / d.pix_pitch.  An entry with
@@ -708,55 +708,46 @@ int detm_run(pfmpe_ctx* c, int R, Fill&& fill, const pfmpe_detect_crop* crops, i
   const DetBatch* dhd = (const DetBatch*)(c->d_detm.get() + kDetmHead);
   const DetDesc* ddescs = (const DetDesc*)(c->d_detm.get() + kDetmDesc);
   uint32_t* work = (uint32_t*)(c->d_detm.get() + o_work);
-  static_assert(sizeof(DetDesc) % sizeof(uint64_t) == 0, "k_detm_stage copies 8-byte words");
+  static_assert(sizeof(DetDesc) % sizeof(uint64_t) == 0, "k_batch_stage copies 8-byte words");
   const int stage_words = (int)((al256(sizeof(DetBatch)) + (size_t)R * sizeof(DetDesc)) / sizeof(uint64_t));
   const uint64_t* stage_src = (const uint64_t*)c->h_detm.dev();
   DetOutHost* hout = (DetOutHost*)c->h_detm_out.get();
   DetOutHost* dout = (DetOutHost*)c->h_detm_out.dev();
   const int64_t pull_n = upload_bytes / (int64_t)sizeof(uint4);  // upload_bytes is a multiple of 256
   const unsigned pull_grid = (unsigned)std::min<int64_t>((pull_n + kPullBlock - 1) / kPullBlock, kPullMaxGrid);
-  hipError_t copy_err = hipSuccess;
-  c->timing_now = c->timing > 0;
-  const int rl = launch(c, PFMPE_K_DETECT, [&] {
-    hipLaunchKernelGGL(k_detm_stage, dim3(1), dim3(kStageBlock), 0, c->stream, stage_src,
-                       (uint64_t*)(c->d_detm.get() + kDetmHead), stage_words, counters);
-    if (pull_n > 0) {
-      if (c->diag & kDiagDetCopy)
-        copy_err = hipMemcpyAsync(c->d_detm.get() + o_crop, c->h_detm_pix.get(), (size_t)upload_bytes,
-                                  hipMemcpyHostToDevice, c->stream);
-      else
-        hipLaunchKernelGGL(k_detm_pull, dim3(pull_grid), dim3(kPullBlock), 0, c->stream,
-                           (const uint4*)c->h_detm_pix.dev(), (uint4*)(c->d_detm.get() + o_crop), pull_n);
-    }
-    hipLaunchKernelGGL(k_detm_mask, dim3(n16), dim3(kDetTile * kDetTile), 0, c->stream, dhd, ddescs);
-    hipLaunchKernelGGL(k_detm_label, dim3(n32), dim3(kLabelBlock), 0, c->stream, dhd, ddescs);
-    hipLaunchKernelGGL(k_detm_merge, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs);
-    hipLaunchKernelGGL(k_detm_roots, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs, counters, work);
-    hipLaunchKernelGGL(k_detm_trace, dim3(512), dim3(64), 0, c->stream, ddescs, (const int*)counters,
-                       (const uint32_t*)work);
-    hipLaunchKernelGGL(k_detm_emit, dim3(R), dim3(kEmitBlock), 0, c->stream, ddescs, (const int*)counters, dout);
-  });
-  // whatever was enqueued is drained before returning, so a failure leaves nothing of the batch pending
-  const hipError_t se = hipStreamSynchronize(c->stream);
-  int rc = rl;
-  if (rc == PFMPE_OK && copy_err != hipSuccess)
-    rc = fail(c, PFMPE_E_HIP, std::string("crop upload: ") + hipGetErrorString(copy_err));
-  if (rc == PFMPE_OK && se != hipSuccess)
-    rc = fail(c, PFMPE_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
-  if (rc == PFMPE_OK && c->timing_now) rc = harvest_timing(c);
-  c->timing_now = false;
-  RET(rc);
-  for (int r = 0; r < R; ++r) {
-    const DetOutHost& h = hout[r];
-    const int nw = std::min(std::min(h.n, max_out), kMaxBlobs);
-    if (nw > 0) {
-      std::memcpy(blobs + (size_t)r * 2 * max_out, h.und, 2 * (size_t)nw * sizeof(double));
-      if (distorted) std::memcpy(distorted + (size_t)r * 2 * max_out, h.dist, 2 * (size_t)nw * sizeof(float));
-    }
-    out[r].n = h.n;
-    out[r].n_components = h.n_components;
-    out[r].overflow = h.overflow;
-  }
+  RET(timed(c, [&] {
+    hipError_t copy_err = hipSuccess;
+    int rc = launch(c, PFMPE_K_DETECT, [&] {
+      hipLaunchKernelGGL((k_batch_stage<kStageBlock>), dim3(1), dim3(kStageBlock), 0, c->stream, stage_src,
+                         (uint64_t*)(c->d_detm.get() + kDetmHead), stage_words, counters, kDetWorkCount + 1);
+      if (pull_n > 0) {
+        if (c->diag & kDiagDetCopy)
+          copy_err = hipMemcpyAsync(c->d_detm.get() + o_crop, c->h_detm_pix.get(), (size_t)upload_bytes,
+                                    hipMemcpyHostToDevice, c->stream);
+        else
+          hipLaunchKernelGGL(k_detm_pull, dim3(pull_grid), dim3(kPullBlock), 0, c->stream,
+                             (const uint4*)c->h_detm_pix.dev(), (uint4*)(c->d_detm.get() + o_crop), pull_n);
+      }
+      hipLaunchKernelGGL(k_detm_mask, dim3(n16), dim3(kDetTile * kDetTile), 0, c->stream, dhd, ddescs);
+      hipLaunchKernelGGL(k_detm_label, dim3(n32), dim3(kLabelBlock), 0, c->stream, dhd, ddescs);
+      hipLaunchKernelGGL(k_detm_merge, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs);
+      hipLaunchKernelGGL(k_detm_roots, dim3(npb), dim3(kPixBlock), 0, c->stream, dhd, ddescs, counters, work);
+      hipLaunchKernelGGL(k_detm_trace, dim3(512), dim3(64), 0, c->stream, ddescs, (const int*)counters,
+                         (const uint32_t*)work);
+      hipLaunchKernelGGL(k_detm_emit, dim3(R), dim3(kEmitBlock), 0, c->stream, ddescs, (const int*)counters, dout);
+    });
+    // whatever was enqueued is drained before returning, so a failure leaves nothing of the batch pending
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    if (rc == PFMPE_OK && copy_err != hipSuccess)
+      rc = fail(c, PFMPE_E_HIP, std::string("crop upload: ") + hipGetErrorString(copy_err));
+    if (rc == PFMPE_OK && se != hipSuccess)
+      rc = fail(c, PFMPE_E_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
+    if (rc == PFMPE_OK && c->timing_now) rc = harvest_timing(c);
+    return rc;
+  }));
+  for (int r = 0; r < R; ++r)
+    det_take(hout[r], blobs + (size_t)r * 2 * max_out, distorted ? distorted + (size_t)r * 2 * max_out : nullptr, max_out,
+             &out[r]);
   return PFMPE_OK;
 }
 
@@ -826,33 +817,24 @@ int pfmpe_find_leds(pfmpe_ctx* c, const uint8_t* image, int width, int height, i
   RET(det_buffers(c, npix, b));
   HIPCHK(c, hipMemsetAsync(b.count, 0, sizeof(int), c->stream));
   const unsigned g1 = (unsigned)((npix + 255) / 256);
-  c->timing_now = c->timing > 0;
   RET(c->h_det.ensure(c, sizeof(DetOutHost)));
   DetOutHost* hout = (DetOutHost*)c->h_det.get();
   DetOutHost* dout = (DetOutHost*)c->h_det.dev();
-  RET(launch(c, PFMPE_K_DETECT, [&] {
-    hipLaunchKernelGGL(k_det_mask, dim3((W + kDetTile - 1) / kDetTile, (H + kDetTile - 1) / kDetTile),
-                       dim3(kDetTile * kDetTile), 0, c->stream, a, c->d_img.get(), b.mask);
-    hipLaunchKernelGGL(k_det_label, dim3((W + kLT - 1) / kLT, (H + kLT - 1) / kLT), dim3(kLabelBlock), 0, c->stream, a, b.mask,
-                       b.nbr, b.label);
-    hipLaunchKernelGGL(k_det_merge, dim3(g1), dim3(256), 0, c->stream, a, b.nbr, b.label);
-    hipLaunchKernelGGL(k_det_roots, dim3(g1), dim3(256), 0, c->stream, a, b.mask, b.label, b.count, b.roots);
-    hipLaunchKernelGGL(k_det_trace, dim3(512), dim3(64), 0, c->stream, a, b.nbr, b.count, b.roots, b.rec);
-    hipLaunchKernelGGL(k_det_emit, dim3(1), dim3(kEmitBlock), 0, c->stream, b.count, b.rec, dout);
+  RET(timed(c, [&] {
+    RET(launch(c, PFMPE_K_DETECT, [&] {
+      hipLaunchKernelGGL(k_det_mask, dim3((W + kDetTile - 1) / kDetTile, (H + kDetTile - 1) / kDetTile),
+                         dim3(kDetTile * kDetTile), 0, c->stream, a, c->d_img.get(), b.mask);
+      hipLaunchKernelGGL(k_det_label, dim3((W + kLT - 1) / kLT, (H + kLT - 1) / kLT), dim3(kLabelBlock), 0, c->stream, a,
+                         b.mask, b.nbr, b.label);
+      hipLaunchKernelGGL(k_det_merge, dim3(g1), dim3(256), 0, c->stream, a, b.nbr, b.label);
+      hipLaunchKernelGGL(k_det_roots, dim3(g1), dim3(256), 0, c->stream, a, b.mask, b.label, b.count, b.roots);
+      hipLaunchKernelGGL(k_det_trace, dim3(512), dim3(64), 0, c->stream, a, b.nbr, b.count, b.roots, b.rec);
+      hipLaunchKernelGGL(k_det_emit, dim3(1), dim3(kEmitBlock), 0, c->stream, b.count, b.rec, dout);
+    }));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return c->timing_now ? harvest_timing(c) : (int)PFMPE_OK;
   }));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->timing_now) RET(harvest_timing(c));
-  c->timing_now = false;
-  const int m = hout->n;
-  const int nc = hout->n_components;
-  const int nw = std::min(std::min(m, max_out), kMaxBlobs);
-  if (nw > 0) {
-    std::memcpy(blobs, hout->und, 2 * (size_t)nw * sizeof(double));
-    if (distorted) std::memcpy(distorted, hout->dist, 2 * (size_t)nw * sizeof(float));
-  }
-  out->n = m;
-  out->n_components = nc;
-  out->overflow = hout->overflow;
+  det_take(*hout, blobs, distorted, max_out, out);
   return PFMPE_OK;
 }
 
@@ -893,7 +875,7 @@ int pfmpe_find_leds_streams(const pfmpe_detect_image* images, int I, const int32
   if (!out || max_out < 0 || (max_out > 0 && !blobs)) return fail(c0, PFMPE_E_ARG, who + "bad arguments");
   std::string why;
   if (const int rc = pfmpe_plan::check(images, I, image_of, prm, R, det_check, &why)) return fail(c0, rc, who + why);
-  std::vector<pfmpe_ctx*> ctxs{c0};  // the batch's contexts, each once, the leader first
+  BatchMembers members("find_leds_streams", I);  // the batch's contexts, each once, the leader first
   for (int i = 0; i < I; ++i) {
     const pfmpe_detect_image& im = images[i];
     pfmpe_ctx* c = im.ctx;
@@ -903,17 +885,15 @@ int pfmpe_find_leds_streams(const pfmpe_detect_image* images, int I, const int32
     if (!c->has_model) return fail(c0, PFMPE_E_STATE, at + "set_model first (K)");
     if (!im.image && (!c->d_img || c->img_w != im.width || c->img_h != im.height || c->img_pitch != im.pitch))
       return fail(c0, PFMPE_E_STATE, at + "no staged image of this size (pfmpe_stage_image)");
-    if (std::find(ctxs.begin(), ctxs.end(), c) == ctxs.end()) ctxs.push_back(c);
+    members.add(c);
   }
   pfmpe_detect_crop crops[PFMPE_DETECT_MAX_ROIS];
   int64_t upload_bytes = 0;
   if (const int rc = pfmpe_plan::build(images, image_of, prm, R, crops, &upload_bytes))
     return fail(c0, rc, who + "the ROIs' pixels exceed the upload limit");
   RET(set_device(c0));
-  // every member's work so far (the staging of its image, on its own stream) is ordered before the batch; a failure
-  // from here on gives the members their ordering state back (the leader's own was set by set_device)
-  OrderGuard members(ctxs.data(), (int)ctxs.size());
-  RET(members.order(1, c0->stream, c0));
+  // every member's staging before the batch; the call's end is detm_run's (shared with find_leds_multi), then commit()
+  RET(members.order());
   RET(detm_run(
       c0, R,
       [&](int r, DetDesc& d) {

@@ -2,13 +2,11 @@
 //
 // Replaces the PF block of PoseEstimator::estimateBodyPose (pf_mpe_lib/src/pose_estimator.cpp:475-733).
 // The launch sequences live in pfmpe_seq.hpp (Seq) and are instantiated per (state type, RNG) in the
-// pfmpe_k_*.hip translation units; this unit holds the step with its tail, the ROI and cloud-statistics calls with
-// their kernels' launches, the read-backs, and builds the blob tables.  The association, refinement, top-K,
-// initialisation and detector calls are in the units of their kernels.
-#include "pf_cloud.hpp"
+// pfmpe_k_*.hip translation units; this unit holds the context's life, the step with its tail, the read-backs, the
+// statistics of the timing brackets, and builds the blob tables.  Every side call (ROI, cloud statistics,
+// association, refinement, top-K, initialisation, detector) is in the unit of its kernels.
 #include "pf_gn.hpp"
 #include "pf_likelihood.hpp"
-#include "pf_roi.hpp"
 #include "pf_tail.hpp"
 #include "pfmpe_prior.hpp"
 
@@ -518,199 +516,6 @@ int pfmpe_step_batch(pfmpe_ctx* c, const pfmpe_frame_in* in, int n, pfmpe_frame_
   return PFMPE_OK;
 }
 
-namespace {
-// project2d (PE:1017-1034) in double on the host: (K34 * T) * [X;1], then / z
-void host_project(const double* K, const double* T12, const double* X, double* uv) {
-  double Q[12];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 4; ++j) {
-      double s = K[i * 3 + 0] * T12[0 * 4 + j];
-      s = s + K[i * 3 + 1] * T12[1 * 4 + j];
-      s = s + K[i * 3 + 2] * T12[2 * 4 + j];
-      Q[i * 4 + j] = s;
-    }
-  double p[3];
-  for (int i = 0; i < 3; ++i) {
-    double s = Q[i * 4 + 0] * X[0];
-    s = s + Q[i * 4 + 1] * X[1];
-    s = s + Q[i * 4 + 2] * X[2];
-    p[i] = s + Q[i * 4 + 3];
-  }
-  uv[0] = p[0] / p[2];
-  uv[1] = p[1] / p[2];
-}
-// LEDDetector::distortPoints (led_detector.cpp:371-414) on cv::Point2f inputs, result back to float
-void host_distort(const double* K, const double* D, float xin, float yin, float* xo, float* yo) {
-  const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-  const double k1 = D[0], k2 = D[1], p1 = D[2], p2 = D[3], k3 = D[4];
-  const double x = ((double)xin - cx) / fx;
-  const double y = ((double)yin - cy) / fy;
-  const double r2 = x * x + y * y;
-  double xc = x * (1. + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2);
-  double yc = y * (1. + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2);
-  xc = xc + (2. * p1 * x * y + p2 * (r2 + 2. * x * x));
-  yc = yc + (p1 * (r2 + 2. * y * y) + 2. * p2 * x * y);
-  *xo = (float)(xc * fx + cx);
-  *yo = (float)(yc * fy + cy);
-}
-// The host end of every ROI entry point: bb = the particles' box {x_min, x_max, y_min, y_max} -> out.
-void roi_epilogue(const double* K, const double* markers, int M, const pfmpe_roi_in* in, double* bb,
-                  pfmpe_roi_out* out) {
-  // + the markers at predicted_pose_ (PE:1049-1052)
-  for (int m = 0; m < M; ++m) {
-    double uv[2];
-    host_project(K, in->predicted_pose, markers + 3 * m, uv);
-    if (uv[0] < bb[0]) bb[0] = uv[0];
-    if (uv[0] > bb[1]) bb[1] = uv[0];
-    if (uv[1] < bb[2]) bb[2] = uv[1];
-    if (uv[1] > bb[3]) bb[3] = uv[1];
-  }
-  std::memcpy(out->bbox, bb, 4 * sizeof(double));
-  // determineROI (led_detector.cpp:317-368): corners as cv::Point2f, distorted, border, clamp, cv::Rect
-  float x0f, y0f, x1f, y1f;
-  host_distort(K, in->D, (float)bb[0], (float)bb[2], &x0f, &y0f);
-  host_distort(K, in->D, (float)bb[1], (float)bb[3], &x1f, &y1f);
-  const double W = in->image_w, H = in->image_h, b = in->border;
-  const double x0 = std::max(0.0, std::min(W, (double)x0f - b));
-  const double x1 = std::max(0.0, std::min(W, (double)x1f + b));
-  const double y0 = std::max(0.0, std::min(H, (double)y0f - b));
-  const double y1 = std::max(0.0, std::min(H, (double)y1f + b));
-  if (x1 - x0 < 1 || y1 - y0 < 1) {
-    out->x = 0;
-    out->y = 0;
-    out->width = in->image_w;
-    out->height = in->image_h;
-  } else {
-    out->x = (int32_t)x0;
-    out->y = (int32_t)y0;
-    out->width = (int32_t)(x1 - x0);
-    out->height = (int32_t)(y1 - y0);
-  }
-}
-// the kernel arguments of context c's current prior for one ROI request
-RoiArgs roi_args(const pfmpe_ctx* c, const pfmpe_roi_in* in) {
-  RoiArgs ra{};
-  std::memcpy(ra.cam, in->cam_move_inv, sizeof(ra.cam));
-  std::memcpy(ra.predm, in->prediction, sizeof(ra.predm));
-  std::memcpy(ra.K, c->K, sizeof(ra.K));
-  std::memcpy(ra.markers, c->markers, sizeof(ra.markers));
-  std::memcpy(ra.anchor, c->anchor[c->prior_idx], sizeof(ra.anchor));
-  ra.N = c->N;
-  ra.M = c->M;
-  ra.ld = c->ld;
-  ra.owner = prior_owner_ptr(c);
-  return ra;
-}
-// what one stream of an ROI call must satisfy: its context c and its request; the text begins with `at`, on `err`
-int roi_check_stream(pfmpe_ctx* err, const pfmpe_ctx* c, const pfmpe_roi_in* in, const std::string& at) {
-  if (!c->has_model || !c->has_prior) return fail(err, PFMPE_E_STATE, at + "set_model and set_prior first");
-  if (in->image_w < 1 || in->image_h < 1) return fail(err, PFMPE_E_ARG, at + "bad image size");
-  return PFMPE_OK;
-}
-// The ROIs of S checked streams, 1 <= S <= kRoiMaxStreams, on ctxs[0]'s stream: pfmpe_predict_roi_multi and, as a
-// batch of one, pfmpe_predict_roi.  The errors it can raise itself begin with `who`.
-int roi_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* in, pfmpe_roi_out* out, const std::string& who) {
-  pfmpe_ctx* c0 = ctxs[0];
-  int64_t total = 0;
-  for (int s = 0; s < S; ++s) total += (ctxs[s]->N + kBlock - 1) / kBlock;
-  if (total > INT32_MAX) return fail(c0, PFMPE_E_CAP, who + ": too many blocks in one batch");
-  RET(set_device(c0));
-  // the scratch before any member's ordering state changes: pinned image (head, descriptors, result boxes) once,
-  // device image + partials grown on demand (nothing of an earlier batch is pending: the call is blocking)
-  constexpr size_t kDescOff = (sizeof(RoiBatch) + 255) / 256 * 256;
-  constexpr size_t kBoxOff = kDescOff + kRoiMaxStreams * sizeof(RoiDesc);
-  RET(c0->h_roim.ensure(c0, kBoxOff + kRoiMaxStreams * 4 * sizeof(double)));
-  const size_t need = kBoxOff + (size_t)total * 4 * sizeof(double);
-  RET(c0->d_roim.grow(c0, need, kBoxOff + (need - kBoxOff) * 2));
-  unsigned char* hd_img = c0->h_roim.dev();
-  // every member's work so far is ordered before the batch; a failure from here on gives the members their
-  // ordering state back (the leader's own was set by set_device)
-  OrderGuard members(ctxs, S);
-  RET(members.order(1, c0->stream, c0));
-  RoiBatch* hd = (RoiBatch*)c0->h_roim.get();
-  RoiDesc* descs = (RoiDesc*)(c0->h_roim.get() + kDescOff);
-  std::memset(hd, 0, sizeof(*hd));
-  hd->S = S;
-  int32_t nb = 0;
-  for (int s = 0; s < S; ++s) {
-    const pfmpe_ctx* c = ctxs[s];
-    RoiDesc& d = descs[s];
-    d.a = roi_args(c, &in[s]);
-    d.prior = c->d_state[c->prior_idx].get();
-    hd->first[s] = nb;
-    nb += (c->N + kBlock - 1) / kBlock;
-  }
-  hd->first[S] = nb;
-  const int stage_words = (int)((kDescOff + (size_t)S * sizeof(RoiDesc)) / sizeof(uint64_t));
-  const RoiBatch* dhd = (const RoiBatch*)c0->d_roim.get();
-  const RoiDesc* ddescs = (const RoiDesc*)(c0->d_roim.get() + kDescOff);
-  double* part = (double*)(c0->d_roim.get() + kBoxOff);
-  const double* hbox = (const double*)(c0->h_roim.get() + kBoxOff);
-  double* dbox = (double*)(hd_img + kBoxOff);
-  c0->timing_now = c0->timing > 0;
-  int rc = launch(c0, PFMPE_K_ROI, [&] {
-    hipLaunchKernelGGL((k_roi_stage<uint64_t>), dim3(1), dim3(kBlock), 0, c0->stream, (const uint64_t*)hd_img,
-                       (uint64_t*)c0->d_roim.get(), stage_words);
-    visit_state(c0, [&](auto s) {
-      hipLaunchKernelGGL((k_roi_multi<typename decltype(s)::T, typename decltype(s)::SP>), dim3(nb), dim3(kBlock), 0,
-                         c0->stream, dhd, ddescs, part);
-    });
-    hipLaunchKernelGGL((k_roi_multi_final<double>), dim3(S), dim3(kBlock), 0, c0->stream, dhd, (const double*)part,
-                       dbox);
-  });
-  c0->timing_now = false;
-  if (rc == PFMPE_OK && hipStreamSynchronize(c0->stream) != hipSuccess)
-    rc = fail(c0, PFMPE_E_HIP, who + ": stream synchronise failed");
-  if (rc == PFMPE_OK) rc = harvest_timing(c0);
-  RET(rc);
-  members.commit();  // nothing of the batch is pending: no member needs a fence
-  for (int s = 0; s < S; ++s) {
-    double bb[4];
-    std::memcpy(bb, hbox + 4 * (size_t)s, sizeof(bb));
-    roi_epilogue(ctxs[s]->K, ctxs[s]->markers, ctxs[s]->M, &in[s], bb, &out[s]);
-  }
-  return PFMPE_OK;
-}
-}  // namespace
-
-int pfmpe_predict_roi(pfmpe_ctx* c, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
-  if (!c) return PFMPE_E_ARG;
-  if (!in || !out) return fail(c, PFMPE_E_ARG, "predict_roi: null in/out");
-  RET(roi_check_stream(c, c, in, "predict_roi: "));
-  return roi_run(&c, 1, in, out, "predict_roi");
-}
-
-int pfmpe_predict_roi_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_roi_in* in, pfmpe_roi_out* out) {
-  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
-  pfmpe_ctx* c0 = ctxs[0];
-  if (!in || !out) return fail(c0, PFMPE_E_ARG, "predict_roi_multi: null in/out");
-  if (S > PFMPE_ROI_MAX_STREAMS)
-    return fail(c0, PFMPE_E_CAP, "predict_roi_multi: S exceeds PFMPE_ROI_MAX_STREAMS");
-  RET(check_members(
-      ctxs, S, "predict_roi_multi", "device and state type", [](const pfmpe_ctx*) { return true; },
-      [&](int s, const std::string& at) { return roi_check_stream(c0, ctxs[s], &in[s], at); }));
-  return roi_run(ctxs, S, in, out, "predict_roi_multi");
-}
-
-int pfmpe_host_predict_roi(const double* markers_xyz, int M, const double* K, const double* poses, int64_t N,
-                           const pfmpe_roi_in* in, pfmpe_roi_out* out) {
-  if (!markers_xyz || !K || !in || !out || M < 1 || M > PFMPE_MAX_MARKERS || N < 0 || (N > 0 && !poses) ||
-      in->image_w < 1 || in->image_h < 1)
-    return PFMPE_E_ARG;
-  RoiArgs ra{};
-  std::memcpy(ra.cam, in->cam_move_inv, sizeof(ra.cam));
-  std::memcpy(ra.predm, in->prediction, sizeof(ra.predm));
-  std::memcpy(ra.K, K, sizeof(ra.K));
-  std::memcpy(ra.markers, markers_xyz, (size_t)M * 3 * sizeof(double));
-  ra.N = 1;  // each pose row is a one-particle set: 12 planes of one element
-  ra.M = M;
-  ra.ld = 1;
-  double bb[4] = {INFINITY, 0.0, INFINITY, 0.0};
-  for (int64_t n = 0; n < N; ++n) roi_particle_box<double, double>(ra, poses + 12 * n, 0, bb[0], bb[1], bb[2], bb[3]);
-  roi_epilogue(ra.K, ra.markers, M, in, bb, out);
-  return PFMPE_OK;
-}
-
 int pfmpe_get_particles(pfmpe_ctx* c, int which, double* out) {
   if (!c) return PFMPE_E_ARG;
   if (!out || (which != 0 && which != 1)) return fail(c, PFMPE_E_ARG, "get_particles: bad arguments");
@@ -757,341 +562,6 @@ int pfmpe_get_counts(pfmpe_ctx* c, uint32_t* out) {
   HIPCHK(c, hipMemcpyAsync(out, c->d_counts.get(), (size_t)c->N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PFMPE_OK;
-}
-
-namespace {
-// exponentialMap (PE:2194-2226): twist [upsilon; omega] -> pose
-void host_exp_map(const double* xi, double* pose) {
-  const double* u = xi;
-  const double* w = xi + 3;
-  const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), th2 = th * th;
-  const double O[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-  double O2[9], R[9], V[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) O2[i * 3 + j] = O[i * 3] * O[j] + O[i * 3 + 1] * O[3 + j] + O[i * 3 + 2] * O[6 + j];
-  for (int i = 0; i < 9; ++i) {
-    const double I = (i % 4 == 0) ? 1.0 : 0.0;
-    R[i] = I;
-    V[i] = I;
-    if (th != 0) {
-      const double s = std::sin(th), c = std::cos(th);
-      R[i] = I + O[i] / th * s + O2[i] / th2 * (1 - c);
-      V[i] = I + (1 - c) / th2 * O[i] + (th - s) / (th2 * th) * O2[i];
-    }
-  }
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) pose[i * 4 + j] = R[i * 3 + j];
-    pose[i * 4 + 3] = V[i * 3] * u[0] + V[i * 3 + 1] * u[1] + V[i * 3 + 2] * u[2];
-  }
-}
-// the kernel arguments of one statistics request on context c: its kept propagated set regenerated into d_xfer with
-// the kept iteration's raw weights (WEIGHTED), or its current prior (POSTERIOR)
-CloudArgs cloud_args(const pfmpe_ctx* c, int which, const double* ref) {
-  CloudArgs ca{};
-  std::memcpy(ca.ref, ref, sizeof(ca.ref));
-  ca.N = c->N;
-  if (which == PFMPE_CLOUD_WEIGHTED) {
-    ca.dense = c->d_xfer.get();
-    ca.w = c->d_w[c->last_kept_slot].get();
-  } else {
-    std::memcpy(ca.anchor, c->anchor[c->prior_idx], sizeof(ca.anchor));
-    ca.ld = c->ld;
-    ca.owner = prior_owner_ptr(c);
-  }
-  return ca;
-}
-// the kCloudWords reduced words r of a set of N particles about ref -> pfmpe_cloud_out (pfmpe_cloud_stats and every
-// entry of pfmpe_cloud_stats_multi)
-void cloud_epilogue(const double* r, int N, const double* ref, pfmpe_cloud_out* out) {
-  std::memset(out, 0, sizeof(*out));
-  out->n = N;
-  out->wsum = r[0];
-  if (!(r[0] > 0.0)) {  // all weights zero (the re-initialisation branch): no mean to speak of
-    out->degenerate = 1;
-    std::memcpy(out->mean_pose, ref, sizeof(out->mean_pose));
-    return;
-  }
-  const double W = r[0];
-  out->ess = W * W / r[1];
-  for (int q = 0; q < 6; ++q) out->mean_twist[q] = r[2 + q] / W;
-  int k = 8;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j, ++k) {
-      const double v = r[k] / W - out->mean_twist[i] * out->mean_twist[j];
-      out->cov[i * 6 + j] = v;
-      out->cov[j * 6 + i] = v;
-    }
-  out->max_trans = std::sqrt(r[kCloudSums]);
-  out->max_rot = std::sqrt(r[kCloudSums + 1]);
-  // mean_pose = exp(mu) * ref: one step toward the intrinsic mean
-  double E[12];
-  host_exp_map(out->mean_twist, E);
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j)
-      out->mean_pose[i * 4 + j] = E[i * 4] * ref[j] + E[i * 4 + 1] * ref[4 + j] + E[i * 4 + 2] * ref[8 + j];
-    out->mean_pose[i * 4 + 3] = E[i * 4] * ref[3] + E[i * 4 + 1] * ref[7] + E[i * 4 + 2] * ref[11] + E[i * 4 + 3];
-  }
-}
-}  // namespace
-
-int pfmpe_host_cloud_plan(const int32_t* N, int S, pfmpe_cloud_plan* plan, int32_t* total_blocks) {
-  if (!N || !plan || !total_blocks || S < 1) return PFMPE_E_ARG;
-  if (S > PFMPE_CLOUD_MAX_STREAMS) return PFMPE_E_CAP;
-  for (int s = 0; s < S; ++s)
-    if (N[s] < 1) return PFMPE_E_ARG;
-  int32_t nb = 0;  // at most 64 x 1024
-  for (int s = 0; s < S; ++s) {
-    plan[s].first_block = nb;
-    // (cloud_blocks rounds N up in int: any N, not a context's only, comes through here)
-    plan[s].blocks = N[s] >= kCloudMaxBlocks * kBlock ? kCloudMaxBlocks : cloud_blocks(N[s]);
-    nb += plan[s].blocks;
-  }
-  *total_blocks = nb;
-  return PFMPE_OK;
-}
-
-namespace {
-// pfmpe_cloud_modes' batch: its S = K + 1 entries are one set of one context, entry s < K about seed s and restricted
-// to mode s, entry K about seed 0 and restricted to the particles without a mode.
-struct CloudModesRun {
-  ModeSeeds seeds;
-  uint8_t* mode_of;  // the caller's N bytes, or null
-};
-constexpr size_t kModesCountBytes = 256;  // the K + 1 member counts in front of pfmpe_ctx::d_modes' bytes
-static_assert((kModesMax + 1) * sizeof(uint32_t) <= kModesCountBytes && PFMPE_MODES_MAX == kModesMax &&
-                  PFMPE_MODE_NONE == kModeNone && kModesMax + 1 <= kCloudMaxStreams,
-              "the modes of a call are one batch");
-// The statistics of S checked entries, 1 <= S <= kCloudMaxStreams, on ctxs[0]'s stream: pfmpe_cloud_stats_multi, as a
-// batch of one pfmpe_cloud_stats and, with `modes`, pfmpe_cloud_modes (the assignment runs between the regeneration
-// and the reduction, and every entry reduces its mode's members: the same launches otherwise).  The errors it can
-// raise itself begin with `who`.
-int cloud_run(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out, const std::string& who,
-              const CloudModesRun* modes = nullptr) {
-  pfmpe_ctx* c0 = ctxs[0];
-  // the distinct contexts in order of first appearance (ctxs[0] first), and which of them have a WEIGHTED entry
-  std::vector<pfmpe_ctx*> distinct;
-  std::vector<char> weighted;
-  int32_t Ns[PFMPE_CLOUD_MAX_STREAMS];
-  for (int s = 0; s < S; ++s) {
-    pfmpe_ctx* c = ctxs[s];
-    size_t m = 0;
-    while (m < distinct.size() && distinct[m] != c) ++m;
-    if (m == distinct.size()) {
-      distinct.push_back(c);
-      weighted.push_back(0);
-    }
-    if (in[s].which == PFMPE_CLOUD_WEIGHTED) weighted[m] = 1;
-    Ns[s] = c->N;
-  }
-  pfmpe_cloud_plan plan[PFMPE_CLOUD_MAX_STREAMS];
-  int32_t total = 0;
-  if (pfmpe_host_cloud_plan(Ns, S, plan, &total) != PFMPE_OK)
-    return fail(c0, PFMPE_E_STATE, who + ": a context without particles");
-  RET(set_device(c0));
-  // the scratch before any member's ordering state changes: pinned image (head, descriptors, result rows) once,
-  // device image + partial rows grown on demand (nothing of an earlier batch is pending: the call is blocking)
-  constexpr size_t kDescOff = (sizeof(CloudBatch) + 255) / 256 * 256;
-  constexpr size_t kRowOff = (kDescOff + kCloudMaxStreams * sizeof(CloudDesc) + 255) / 256 * 256;
-  constexpr size_t kRowBytes = kCloudWords * sizeof(double);
-  RET(c0->h_cloudm.ensure(c0, kRowOff + kCloudMaxStreams * kRowBytes));
-  const size_t need = kRowOff + (size_t)total * kRowBytes;
-  RET(c0->d_cloudm.grow(c0, need, kRowOff + (need - kRowOff) * 2));
-  if (modes) {
-    RET(c0->h_modes.ensure(c0, kModesCountBytes));
-    const size_t bytes = kModesCountBytes + (((size_t)c0->N + 3) & ~(size_t)3);
-    RET(c0->d_modes.grow(c0, bytes, bytes));
-  }
-  for (size_t m = 0; m < distinct.size(); ++m)
-    if (weighted[m]) RET(ensure_xfer(distinct[m]));
-  // each WEIGHTED context's kept propagated set once, as its single call regenerates it: into its own d_xfer, on its
-  // own stream (set_device: after whatever it has pending elsewhere); all its entries read that set
-  for (size_t m = 0; m < distinct.size(); ++m) {
-    pfmpe_ctx* c = distinct[m];
-    if (!weighted[m]) continue;
-    if (c != c0) RET(set_device(c));
-    if (const int r_ = dispatch_regen(c, c->last_kept_iter, c->d_state[c->last_prior_idx].get(), c->d_xfer.get()))
-      return c == c0 ? r_ : fail(c0, r_, who + ": " + c->err);
-  }
-  // every member's work so far, that regeneration included, is ordered before the batch (a context that appears
-  // twice once); a failure from here on gives the members their ordering state back (the leader's own was set by
-  // set_device)
-  OrderGuard members(distinct.data(), (int)distinct.size());
-  RET(members.order(1, c0->stream, c0));
-  unsigned char* hd_img = c0->h_cloudm.dev();
-  CloudBatch* hd = (CloudBatch*)c0->h_cloudm.get();
-  CloudDesc* descs = (CloudDesc*)(c0->h_cloudm.get() + kDescOff);
-  std::memset(hd, 0, sizeof(*hd));
-  hd->S = S;
-  for (int s = 0; s < S; ++s) {
-    const pfmpe_ctx* c = ctxs[s];
-    CloudDesc& d = descs[s];
-    d.a = cloud_args(c, in[s].which, in[s].ref_pose);
-    d.dense = in[s].which == PFMPE_CLOUD_WEIGHTED;
-    d.st = d.dense ? nullptr : c->d_state[c->prior_idx].get();
-    d.mode_of = modes ? c0->d_modes.get() + kModesCountBytes : nullptr;
-    d.mode = s < S - 1 ? s : kModeNone;  // (read by a filtered entry only)
-    hd->first[s] = plan[s].first_block;
-  }
-  hd->first[S] = total;
-  const int stage_words = (int)((kDescOff + (size_t)S * sizeof(CloudDesc)) / sizeof(uint64_t));
-  const CloudBatch* dhd = (const CloudBatch*)c0->d_cloudm.get();
-  const CloudDesc* ddescs = (const CloudDesc*)(c0->d_cloudm.get() + kDescOff);
-  double* part = (double*)(c0->d_cloudm.get() + kRowOff);
-  const double* hrow = (const double*)(c0->h_cloudm.get() + kRowOff);
-  hipLaunchKernelGGL((k_roi_stage<uint64_t>), dim3(1), dim3(kBlock), 0, c0->stream, (const uint64_t*)hd_img,
-                     (uint64_t*)c0->d_cloudm.get(), stage_words);
-  uint32_t* d_count = (uint32_t*)c0->d_modes.get();
-  if (modes) {  // every entry reads the same set: entry 0's descriptor names it
-    HIPCHK(c0, hipMemsetAsync(d_count, 0, kModesCountBytes, c0->stream));
-    visit_state(c0, [&](auto s) {
-      hipLaunchKernelGGL((k_cloud_assign<typename decltype(s)::T, typename decltype(s)::SP>), dim3(cloud_blocks(c0->N)),
-                         dim3(kBlock), 0, c0->stream, descs[0], modes->seeds, c0->d_modes.get() + kModesCountBytes,
-                         d_count);
-    });
-  }
-  visit_state(c0, [&](auto s) {
-    using T = typename decltype(s)::T;
-    using SP = typename decltype(s)::SP;
-    if (modes)
-      hipLaunchKernelGGL((k_cloud_multi<T, SP, true>), dim3(total), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
-    else
-      hipLaunchKernelGGL((k_cloud_multi<T, SP, false>), dim3(total), dim3(kBlock), 0, c0->stream, dhd, ddescs, part);
-  });
-  hipLaunchKernelGGL(k_cloud_multi_final, dim3(S), dim3(kCloudSegs * kCloudWords), 0, c0->stream, dhd,
-                     (const double*)part, (double*)(hd_img + kRowOff));
-  HIPCHK(c0, hipGetLastError());
-  if (modes) {
-    HIPCHK(c0, hipMemcpyAsync(c0->h_modes.get(), d_count, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, c0->stream));
-    if (modes->mode_of)
-      HIPCHK(c0, hipMemcpyAsync(modes->mode_of, c0->d_modes.get() + kModesCountBytes, (size_t)c0->N,
-                                hipMemcpyDeviceToHost, c0->stream));
-  }
-  if (hipStreamSynchronize(c0->stream) != hipSuccess)
-    return fail(c0, PFMPE_E_HIP, who + ": stream synchronise failed");
-  members.commit();  // nothing of the batch is pending: no member needs a fence
-  for (pfmpe_ctx* c : distinct)  // (as every single call ends: the brackets of sampled frames still pending)
-    if (const int r_ = harvest_timing(c)) return c == c0 ? r_ : fail(c0, r_, who + ": " + c->err);
-  for (int s = 0; s < S; ++s) {
-    double r[kCloudWords];
-    std::memcpy(r, hrow + (size_t)kCloudWords * s, sizeof(r));
-    const int64_t n = modes ? (int64_t)((const uint32_t*)c0->h_modes.get())[s] : (int64_t)ctxs[s]->N;
-    cloud_epilogue(r, n, in[s].ref_pose, &out[s]);
-  }
-  return PFMPE_OK;
-}
-// the checks pfmpe_cloud_modes and pfmpe_host_cloud_assign share: K, the seeds, the parameters
-const char* modes_args_bad(const double* seeds, int K, const pfmpe_modes_params& p) {
-  if (K < 1 || K > PFMPE_MODES_MAX) return "K outside 1..PFMPE_MODES_MAX";
-  for (int q = 0; q < 12 * K; ++q)
-    if (!std::isfinite(seeds[q])) return "non-finite seed";
-  for (const double v : {p.trans_scale, p.rot_scale, p.max_dist})
-    if (!(v >= 0.0) || !std::isfinite(v)) return "a scale or max_dist is negative or not finite";
-  if (p.trans_scale == 0.0 && p.rot_scale == 0.0) return "both scales are 0";
-  return nullptr;
-}
-ModeSeeds mode_seeds(const double* seeds, int K, const pfmpe_modes_params& p) {
-  ModeSeeds ms{};
-  std::memcpy(ms.seed, seeds, (size_t)K * 12 * sizeof(double));
-  ms.it2 = mode_inv2(p.trans_scale);
-  ms.ir2 = mode_inv2(p.rot_scale);
-  ms.max_dist = p.max_dist;
-  ms.K = K;
-  return ms;
-}
-}  // namespace
-
-void pfmpe_default_modes_params(pfmpe_modes_params* p) {
-  if (!p) return;
-  p->trans_scale = 0.01;
-  p->rot_scale = 0.05;
-  p->max_dist = 0.0;
-}
-
-int pfmpe_cloud_modes(pfmpe_ctx* c, int which, const double* seeds, int K, const pfmpe_modes_params* params,
-                      pfmpe_mode_out* out, uint8_t* mode_of) {
-  static_assert(sizeof(pfmpe_modes_params) == 24 && sizeof(pfmpe_mode_out) == 488, "ABI");
-  if (!c) return PFMPE_E_ARG;
-  if (!seeds || !out || (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR))
-    return fail(c, PFMPE_E_ARG, "cloud_modes: bad arguments");
-  pfmpe_modes_params prm;
-  pfmpe_default_modes_params(&prm);
-  if (params) prm = *params;
-  if (const char* bad = modes_args_bad(seeds, K, prm)) return fail(c, PFMPE_E_ARG, std::string("cloud_modes: ") + bad);
-  if (!c->has_prior) return fail(c, PFMPE_E_STATE, "cloud_modes: no particle set");
-  if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_modes(weighted): no step yet");
-  CloudModesRun run{mode_seeds(seeds, K, prm), mode_of};
-  pfmpe_ctx* ctxs[kModesMax + 1];
-  pfmpe_cloud_in in[kModesMax + 1];
-  pfmpe_cloud_out stats[kModesMax + 1];
-  for (int s = 0; s <= K; ++s) {
-    ctxs[s] = c;
-    in[s] = pfmpe_cloud_in{};
-    std::memcpy(in[s].ref_pose, seeds + 12 * (s < K ? s : 0), sizeof(in[s].ref_pose));
-    in[s].which = which;
-  }
-  RET(cloud_run(ctxs, K + 1, in, stats, "cloud_modes", &run));
-  double total = 0.0;
-  for (int s = 0; s <= K; ++s) total = total + stats[s].wsum;
-  for (int s = 0; s <= K; ++s) {
-    out[s].stats = stats[s];
-    out[s].share = total > 0.0 ? stats[s].wsum / total : 0.0;
-  }
-  return PFMPE_OK;
-}
-
-int pfmpe_host_cloud_assign(const double* poses, int64_t N, const double* seeds, int K, const pfmpe_modes_params* params,
-                            uint8_t* mode_of, int64_t* counts) {
-  if (!seeds || N < 0 || (N > 0 && (!poses || !mode_of))) return PFMPE_E_ARG;
-  pfmpe_modes_params prm;
-  pfmpe_default_modes_params(&prm);
-  if (params) prm = *params;
-  if (modes_args_bad(seeds, K, prm)) return PFMPE_E_ARG;
-  const ModeSeeds ms = mode_seeds(seeds, K, prm);
-  int64_t cnt[kModesMax + 1] = {0};
-  for (int64_t n = 0; n < N; ++n) {
-    const int mode = mode_assign(poses + 12 * n, ms);
-    mode_of[n] = (uint8_t)mode;
-    cnt[mode == kModeNone ? K : mode] += 1;
-  }
-  if (counts) std::memcpy(counts, cnt, (size_t)(K + 1) * sizeof(int64_t));
-  return PFMPE_OK;
-}
-
-int pfmpe_cloud_stats(pfmpe_ctx* c, int which, const double* ref, pfmpe_cloud_out* out) {
-  if (!c) return PFMPE_E_ARG;
-  if (!ref || !out || (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR))
-    return fail(c, PFMPE_E_ARG, "cloud_stats: bad arguments");
-  for (int q = 0; q < 12; ++q)
-    if (!std::isfinite(ref[q])) return fail(c, PFMPE_E_ARG, "cloud_stats: non-finite reference pose");
-  if (!c->has_prior) return fail(c, PFMPE_E_STATE, "cloud_stats: no particle set");
-  if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c, PFMPE_E_STATE, "cloud_stats(weighted): no step yet");
-  pfmpe_cloud_in e{};
-  std::memcpy(e.ref_pose, ref, sizeof(e.ref_pose));
-  e.which = which;
-  return cloud_run(&c, 1, &e, out, "cloud_stats");
-}
-
-int pfmpe_cloud_stats_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_cloud_in* in, pfmpe_cloud_out* out) {
-  static_assert(PFMPE_CLOUD_MAX_STREAMS == kCloudMaxStreams, "stream capacity mismatch");
-  if (!ctxs || S < 1 || !ctxs[0]) return PFMPE_E_ARG;
-  pfmpe_ctx* c0 = ctxs[0];
-  if (!in || !out) return fail(c0, PFMPE_E_ARG, "cloud_stats_multi: null in/out");
-  if (S > PFMPE_CLOUD_MAX_STREAMS)
-    return fail(c0, PFMPE_E_CAP, "cloud_stats_multi: S exceeds PFMPE_CLOUD_MAX_STREAMS");
-  for (int s = 0; s < S; ++s) {
-    const pfmpe_ctx* c = ctxs[s];
-    const std::string at = "cloud_stats_multi: stream " + std::to_string(s) + ": ";
-    if (!c) return fail(c0, PFMPE_E_ARG, at + "null context");
-    if (c->device != c0->device || c->state_dtype != c0->state_dtype)
-      return fail(c0, PFMPE_E_ARG, at + "device and state type must match ctxs[0]");
-    const int which = in[s].which;
-    if (which != PFMPE_CLOUD_WEIGHTED && which != PFMPE_CLOUD_POSTERIOR) return fail(c0, PFMPE_E_ARG, at + "bad which");
-    for (int q = 0; q < 12; ++q)
-      if (!std::isfinite(in[s].ref_pose[q])) return fail(c0, PFMPE_E_ARG, at + "non-finite reference pose");
-    if (!c->has_prior) return fail(c0, PFMPE_E_STATE, at + "no particle set");
-    if (which == PFMPE_CLOUD_WEIGHTED && !c->has_last) return fail(c0, PFMPE_E_STATE, at + "weighted: no step yet");
-  }
-  return cloud_run(ctxs, S, in, out, "cloud_stats_multi");
 }
 
 // ---- the step with its refinement (pf_tail.hpp; k_step_tail in pfmpe_refine.hip)
@@ -1419,11 +889,6 @@ void pfmpe_host_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t ou
   out[1] = o.y;
   out[2] = o.z;
   out[3] = o.w;
-}
-
-// the twist the cloud-statistics kernel forms for one particle
-void pfmpe_host_pose_twist(const double* pose12, const double* ref_pose12, double* twist6) {
-  pose_twist(pose12, ref_pose12, twist6);
 }
 
 }  // extern "C"

@@ -1020,33 +1020,35 @@ int multi_run(pfmpe_ctx* const* ctxs, std::vector<MultiStream>& st, pfmpe_init_o
   RET(set_device(c0));
   // every member's work so far is ordered before the batch; a failure from here on gives the members their
   // ordering state back (the leader's own was set by set_device)
-  OrderGuard members(ctxs, S);
+  OrderGuard members(ctxs, S);  // (not BatchMembers: a synchronise per stage, no single end for its finish())
   RET(members.order(1, c0->stream, c0));
-  RET(multi_histograms(c0, st, false));
-  for (int s = 0; s < S; ++s)
-    if (hist_out && hist_out[s] && !st[s].hist.empty())
-      std::memcpy(hist_out[s], st[s].hist.data(), st[s].hist.size() * sizeof(uint32_t));
-  for (int s = 0; s < S; ++s) {
-    MultiStream& m = st[s];
-    if (m.hist.empty()) continue;  // B < M: flag 10
-    uint64_t tot = 0;
-    for (uint32_t h : m.hist) tot += h;
-    m.o.hist_total = tot;
-    if (tot == 0) {
-      m.o.flag_fail = 12;
-      continue;
-    }
-    RET(candidates(c0, m.at, m.B, m.c->M, m.hist.data(), m.p.max_candidates, m.cands));
-    m.o.n_candidates = (int)m.cands.size();
-    m.flag = m.cands.empty() ? 11 : -1;
-    for (size_t i = 0; i < m.cands.size(); ++i)
-      if ((int)m.cands[i].size() == 2 * m.c->M) m.full.push_back((int)i);
-  }
   const uint8_t* status = nullptr;
   const double* invs = nullptr;
-  RET(multi_check(c0, st, &status, &invs));
-  if (c0->timing_now) RET(harvest_timing(c0));
-  c0->timing_now = false;
+  // stages 1 to 3 are the timed ones: the seeding's exports and imports are not bracketed
+  RET(timed(c0, [&] {
+    RET(multi_histograms(c0, st, false));
+    for (int s = 0; s < S; ++s)
+      if (hist_out && hist_out[s] && !st[s].hist.empty())
+        std::memcpy(hist_out[s], st[s].hist.data(), st[s].hist.size() * sizeof(uint32_t));
+    for (int s = 0; s < S; ++s) {
+      MultiStream& m = st[s];
+      if (m.hist.empty()) continue;  // B < M: flag 10
+      uint64_t tot = 0;
+      for (uint32_t h : m.hist) tot += h;
+      m.o.hist_total = tot;
+      if (tot == 0) {
+        m.o.flag_fail = 12;
+        continue;
+      }
+      RET(candidates(c0, m.at, m.B, m.c->M, m.hist.data(), m.p.max_candidates, m.cands));
+      m.o.n_candidates = (int)m.cands.size();
+      m.flag = m.cands.empty() ? 11 : -1;
+      for (size_t i = 0; i < m.cands.size(); ++i)
+        if ((int)m.cands[i].size() == 2 * m.c->M) m.full.push_back((int)i);
+    }
+    RET(multi_check(c0, st, &status, &invs));
+    return c0->timing_now ? harvest_timing(c0) : (int)PFMPE_OK;
+  }));
   bool any_found = false;
   for (int s = 0; s < S; ++s) {
     MultiStream& m = st[s];
@@ -1082,18 +1084,6 @@ int validate_stream(pfmpe_ctx* rep, const std::string& at, pfmpe_ctx* c, const d
   m.o.first_match = -1;
   if (B < c->M) m.o.flag_fail = 10;
   return PFMPE_OK;
-}
-
-// fn with the timing brackets of c (the leader) on; a failure drops the brackets this call left unharvested, the
-// pending ones of earlier frames stay
-template <typename F>
-int timed(pfmpe_ctx* c, F&& fn) {
-  const size_t ev_mark = c->ev_used;
-  c->timing_now = c->timing > 0;
-  const int rc = fn();
-  c->timing_now = false;
-  if (rc != PFMPE_OK && c->ev_used > ev_mark) c->ev_used = ev_mark;
-  return rc;
 }
 
 }  // namespace
@@ -1137,7 +1127,7 @@ int pfmpe_initialise(pfmpe_ctx* c, const double* blobs, int B, const pfmpe_init_
     *out = st[0].o;
     return PFMPE_OK;
   }
-  return timed(c, [&] { return multi_run(&c, st, out, &hist_out, true); });
+  return multi_run(&c, st, out, &hist_out, true);
 }
 
 int pfmpe_initialise_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_init_in* in, const pfmpe_init_params* prm,
@@ -1162,7 +1152,7 @@ int pfmpe_initialise_multi(pfmpe_ctx* const* ctxs, int S, const pfmpe_init_in* i
     for (int s = 0; s < S; ++s) out[s] = st[s].o;
     return PFMPE_OK;
   }
-  return timed(c0, [&] { return multi_run(ctxs, st, out, hist_out, false); });
+  return multi_run(ctxs, st, out, hist_out, false);
 }
 
 }  // extern "C"

@@ -30,6 +30,13 @@ __global__ void k_export(const SP* __restrict__ st, double* __restrict__ poses, 
   for (int q = 0; q < 12; ++q)
     poses[12 * (int64_t)n + q] = (double)StateIO<T, SP>::load(st[plane_index<SP>(q, r, ld)], anchor.v[q]);
 }
+// the weights widened into the transfer buffer (pfmpe_get_weights)
+template <typename T>
+__global__ void k_weights_export(const T* __restrict__ w, double* __restrict__ out, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  out[n] = (double)w[n];
+}
 
 }  // namespace pfmpe
 

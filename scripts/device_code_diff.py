@@ -5,7 +5,8 @@ usage: device_code_diff.py OLD_DIR NEW_DIR   (each holds <unit>.s from `hipcc <M
 
 Per unit: the kernel symbols of both sides, and for every common symbol its code (from its label to its end label)
 and its kernel descriptor (.amdhsa_kernel block).  Local label numbers and trailing comments follow the order of
-emission and are not compared.  Prints one line per unit and the symbols present on one side only; exit status 1 if a
+emission and are not compared.  A kernel that changed unit is looked up by its symbol in the parent's other units and
+reported as moved.  Prints one line per unit and the symbols present on one side only; exit status 1 if a
 common symbol differs, a symbol's code was not found, or the new side has a symbol the old one lacks.
 """
 import os
@@ -51,13 +52,20 @@ def kernels(path):
 def main():
     old, new = sys.argv[1], sys.argv[2]
     bad = False
-    for f in sorted(os.listdir(new)):
-        if not f.endswith(".s"):
-            continue
-        a, b = kernels(os.path.join(old, f)), kernels(os.path.join(new, f))
+    units = lambda d: sorted(f for f in os.listdir(d) if f.endswith(".s"))
+    olds = {f: kernels(os.path.join(old, f)) for f in units(old)}
+    news = {f: kernels(os.path.join(new, f)) for f in units(new)}
+    for f in units(new):
+        a, b = dict(olds.get(f, {})), news[f]
+        # a kernel that changed unit is compared with the parent's code where the parent had it
+        moved = {k: g for k in set(b) - set(a) for g in olds if g != f and k in olds[g]}
+        for k, g in sorted(moved.items()):
+            a[k] = olds[g][k]
+            print("    %s: %s was in %s at the parent" % (f.replace(".s", ".hip"), k, g.replace(".s", ".hip")))
         common = sorted(set(a) & set(b))
         diff = [k for k in common if a[k] != b[k] or not b[k][0]]
-        gone, added = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+        elsewhere = {k for k in set(a) - set(b) if any(k in news[g] for g in news if g != f)}
+        gone, added = sorted(set(a) - set(b) - elsewhere), sorted(set(b) - set(a))
         print("%s: %d kernels at the parent, %d at this tree; common symbols identical: %s" %
               (f.replace(".s", ".hip"), len(a), len(b), "NO" if diff else "yes"))
         for k in gone:

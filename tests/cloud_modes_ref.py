@@ -1,6 +1,6 @@
 """numpy restatement of the assignment pfmpe_cloud_modes defines (include/pfmpe.h), and the multi-modal cloud its tests
 share.  numpy rounds every product and sum on its own, and the expressions below keep the operand order of
-mode_dist / mode_assign (csrc/pf_cloud.hpp), so on inputs where no decision sits on a rounding the two agree exactly.
+mode_dist / mode_assign (csrc/pfmpe_cloud.hip), so on inputs where no decision sits on a rounding the two agree exactly.
 `assert_margin` is that condition on the inputs; it is evaluated with the numpy numbers alone."""
 import functools
 

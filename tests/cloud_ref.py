@@ -1,6 +1,6 @@
 """numpy restatement of the cloud statistics defined in include/pfmpe.h (pfmpe_cloud_stats), vectorised over N.
 
-The elementwise expressions keep the order of operations of the engine's pose_twist (csrc/pf_cloud.hpp), so that
+The elementwise expressions keep the order of operations of the engine's pose_twist (csrc/pfmpe_cloud.hip), so that
 the cancellations in D_R - D_R^T and t_i - D_R t_r round the same way on both sides and the two differ only by libm
 rounding (sin, atan2) and by the order of the sums over particles."""
 import numpy as np
