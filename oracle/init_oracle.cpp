@@ -699,6 +699,9 @@ void orc_inverse44(const double* sol12, double* inv16) {
   inverse44(s, inv16);
 }
 
+// project2d of one point X through a 4 x 4 transform T (row-major, 16 doubles)
+void orc_project44(const double* K, const double* T16, const double* X, double* uv) { project44(K, T16, X, uv); }
+
 int orc_init_histogram(int M, const double* markers, const double* K, int B, const double* blobs, double tol,
                        uint32_t* hist) {
   if (B < 3 || B > 1024 || M < 3 || M > 16) return -1;

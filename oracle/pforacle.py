@@ -137,6 +137,8 @@ def load() -> C.CDLL:
     lib.orc_p3p.argtypes = [dp, dp, dp]
     lib.orc_inverse44.restype = None
     lib.orc_inverse44.argtypes = [dp, dp]
+    lib.orc_project44.restype = None
+    lib.orc_project44.argtypes = [dp, dp, dp, dp]
     lib.orc_init_histogram.restype = C.c_int
     lib.orc_init_histogram.argtypes = [C.c_int, dp, dp, C.c_int, dp, C.c_double, u32p]
     lib.orc_init_histogram_bounds.restype = C.c_int
@@ -369,6 +371,13 @@ def inverse44(sol12):
     out = np.zeros(16)
     load().orc_inverse44(_p(_d(sol12).reshape(12)), _p(out))
     return out.reshape(4, 4)
+
+
+def project44(K, T44, X):
+    """project2d of one point through a 4 x 4 transform -> (u, v)."""
+    uv = np.zeros(2)
+    load().orc_project44(_p(_d(K).reshape(9)), _p(_d(T44).reshape(16)), _p(_d(X).reshape(3)), _p(uv))
+    return uv
 
 
 def init_histogram(markers, K, blobs, tol=5.0):
