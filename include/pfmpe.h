@@ -600,6 +600,67 @@ int pfmpe_cloud_modes(pfmpe_ctx* ctx, int which, const double* seeds /* K x 12 *
 int pfmpe_host_cloud_assign(const double* poses, int64_t N, const double* seeds, int K,
                             const pfmpe_modes_params* params, uint8_t* mode_of, int64_t* counts /* K + 1, may be NULL */);
 
+/* A new prior of n_new particles from the members of the current one, on the device: change the particle count of a
+ * context (a wide cloud for acquisition, a small one for steady tracking: a frame of up to 131k particles is one
+ * launch), keep one hypothesis and drop the others, or hand one hypothesis to a second context.  A lossless gather of
+ * stored state: no pose crosses the host link and none is converted.
+ *
+ * Source set: src's current prior, the N rows pfmpe_get_particles(src, 1) returns (the posterior, unit weights).
+ * Members: with K = 0 every particle; with K > 0 the particles n with mode_of[n] == mode, mode_of being what
+ * pfmpe_cloud_modes(src, PFMPE_CLOUD_POSTERIOR, seeds, K, &modes, ., mode_of) writes (the same function assigns them).
+ * Rank: let m be the member count and j_0 < j_1 < ... < j_(m-1) the members in ascending particle index.  New particle
+ * k, 0 <= k < n_new, is a copy of source particle j_r with r = ((2k + 1) * m) / (2 * n_new) in unsigned 64-bit integers
+ * (no overflow: 2k + 1 < 2^32, m < 2^31).  This is systematic resampling of unit weights with offset 1/2 and no random
+ * draw: r is non-decreasing in k, every member is used floor or ceil of n_new / m times when n_new >= m, the ranks are
+ * distinct and floor or ceil of m / n_new apart when n_new < m, and n_new == m is the identity on the members.  The
+ * prior is sorted by owner (stratified resampling writes ascending owners), so equal-spaced picks of it are a systematic
+ * resample of the same distribution: the posterior stays a posterior.
+ * Copy: the 12 state elements of the source row as stored (fp64, fp32, or the fp16 deltas; a deferred prior is read
+ * through its owner indices), and for fp16 state dst takes the anchor of src's set.  Hence for every state type, bit
+ * for bit, pfmpe_get_particles(dst, 1)[k] after the call == pfmpe_get_particles(src, 1)[source[k]] before it, with
+ * source from pfmpe_host_resample_source for the same mode_of; a repeated call gives the same bytes.
+ *
+ * Contexts: dst == src resamples in place; dst != src fills another context (a fork) and leaves src untouched.  Both
+ * must be on one device and of one state type; max_particles, model and parameters may differ, and dst needs neither a
+ * model nor a prior of its own.  The new prior goes to the state buffer dst's prior does not occupy, in particle order,
+ * and becomes the prior only once the device work has been waited for: a failure leaves dst as it was.  Afterwards dst
+ * is as after pfmpe_set_prior: N = n_new, no kept set of an earlier step (PROPAGATED / WEIGHTED calls and
+ * pfmpe_get_counts return PFMPE_E_STATE until the next step), hand-off state zeroed.  The set is a posterior, not a
+ * fresh initialisation: the caller keeps passing its own it_since_init.
+ * No members (n_members == 0) is an outcome, not an error: PFMPE_OK, out->n_new = 0 and dst unchanged, its kept set
+ * included.
+ * Blocking; runs on dst's stream, after whatever src has pending on another stream.  Not timed by PFMPE_OPT_TIMING.
+ * The scratch (a byte and 4/256 B per source particle, with a filter only) is dst's, grown on demand.  DESIGN.md §4.18.
+ * Errors, all checked before anything is launched (out untouched, no context changed; the text, in dst's last error,
+ * begins "resample_prior: "): PFMPE_E_ARG for a NULL dst (no text), src, params or out, n_new < 1, a device or
+ * state-type mismatch, K outside 0..PFMPE_MODES_MAX, and with K > 0 NULL or non-finite seeds, the scale and max_dist
+ * errors of pfmpe_cloud_modes, a mode that is neither 0..K-1 nor PFMPE_MODE_NONE; PFMPE_E_CAP for n_new above dst's
+ * max_particles; PFMPE_E_STATE for a src without a particle set. */
+typedef struct {
+  int32_t n_new;             /* particles of the new prior, 1 .. dst's max_particles                          */
+  int32_t K;                 /* 0: every particle is a member; 1..PFMPE_MODES_MAX: seeds, as pfmpe_cloud_modes */
+  const double* seeds;       /* K x 12; may be NULL when K == 0                                                */
+  int32_t mode;              /* K > 0: the mode kept, 0..K-1 or PFMPE_MODE_NONE; ignored when K == 0           */
+  int32_t pad;
+  pfmpe_modes_params modes;  /* K > 0: scales and gate, pfmpe_cloud_modes' rules; ignored when K == 0          */
+} pfmpe_resample_params;     /* 48 bytes */
+typedef struct {
+  int64_t n_src;      /* particles of src's prior                                            */
+  int64_t n_members;  /* of them, members                                                    */
+  int64_t n_new;      /* particles of dst's new prior; 0 when n_members == 0 (dst unchanged) */
+} pfmpe_resample_out;        /* 24 bytes */
+int pfmpe_resample_prior(pfmpe_ctx* dst, pfmpe_ctx* src, const pfmpe_resample_params* params,
+                         pfmpe_resample_out* out);
+/* host-only (no GPU, no context): the source particle of every new slot by the rule above, for the members
+ * mode_of[n] == mode of N particles (mode_of NULL: every particle is a member).  *n_members = m; with m == 0 no source
+ * entry is written.  PFMPE_E_ARG for a NULL source with n_new > 0, a NULL n_members, N < 0, n_new < 0, N or n_new above
+ * 2^31 - 1, a mode outside 0..255 when mode_of is given; the outputs are untouched then. */
+int pfmpe_host_resample_source(const uint8_t* mode_of /* N bytes; NULL: all members */, int64_t N, int32_t mode,
+                               int64_t n_new, int32_t* source /* n_new */, int64_t* n_members);
+/* host-only: the rank r of the one slot k by the function the device runs.  PFMPE_E_ARG for a NULL rank, m < 1,
+ * n_new < 1, k outside 0..n_new-1, m or n_new above 2^31 - 1; *rank is untouched then. */
+int pfmpe_host_resample_rank(int64_t k, int64_t m, int64_t n_new, int64_t* rank);
+
 /* ------------------------------------------------------------- LED-blob association of the particle cloud */
 /* The reference keeps the correspondences of every particle (correspondencesVec, PE:2385-2445, read at PE:688); a
  * step reports the winner's only (pfmpe_frame_out.corr).  These calls derive every particle's pairs on the device

@@ -27,6 +27,7 @@ from ._capi import (  # noqa: F401
     CLOUD_MAX_STREAMS, CloudIn, CloudPlan, host_cloud_plan,
     TOP_MAX, TOP_POOL, TOP_BY_WEIGHT, TOP_BY_COUNT, TopParams, TopOut, default_top_params, host_top_suppress,
     MODES_MAX, MODE_NONE, ModesParams, ModeOut, default_modes_params, host_cloud_assign,
+    ResampleParams, ResampleOut, host_resample_source, host_resample_rank,
     ASSOC_MAX_STREAMS, ASSOC_MAX_LAUNCHES, AssocMultiIn, AssocPlan, AssocPlanTotal, host_assoc_plan,
     GateParams, GateOut, default_gate_params, host_gate_pairs,
 )

@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "pfmpe_cloud_stats_multi", "pfmpe_host_cloud_plan",
     "pfmpe_default_top_params", "pfmpe_top_particles", "pfmpe_host_top_suppress",
     "pfmpe_default_modes_params", "pfmpe_cloud_modes", "pfmpe_host_cloud_assign",
+    "pfmpe_resample_prior", "pfmpe_host_resample_source", "pfmpe_host_resample_rank",
     "pfmpe_assoc_stats_multi", "pfmpe_host_assoc_plan", "pfmpe_default_gate_params", "pfmpe_host_gate_pairs",
 )
 MODES_MAX = 16
@@ -234,6 +235,21 @@ class ModeOut(C.Structure):
 
 # the sizes include/pfmpe.h states (pfmpe_engine.hip asserts them on its side)
 assert C.sizeof(ModesParams) == 24 and C.sizeof(CloudOut) == 480 and C.sizeof(ModeOut) == 488
+
+
+class ResampleParams(C.Structure):
+    _fields_ = [("n_new", C.c_int32), ("K", C.c_int32), ("seeds", C.POINTER(C.c_double)), ("mode", C.c_int32),
+                ("pad", C.c_int32), ("modes", ModesParams)]
+
+
+class ResampleOut(C.Structure):
+    _fields_ = [("n_src", C.c_int64), ("n_members", C.c_int64), ("n_new", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {"n_src": self.n_src, "n_members": self.n_members, "n_new": self.n_new}
+
+
+assert C.sizeof(ResampleParams) == 48 and C.sizeof(ResampleOut) == 24
 
 
 class AssocIn(C.Structure):
@@ -412,6 +428,10 @@ def load() -> C.CDLL:
         "pfmpe_cloud_modes": (I, [P, I, dp, I, C.POINTER(ModesParams), C.POINTER(ModeOut), C.POINTER(C.c_uint8)]),
         "pfmpe_host_cloud_assign": (I, [dp, I64, dp, I, C.POINTER(ModesParams), C.POINTER(C.c_uint8),
                                         C.POINTER(I64)]),
+        "pfmpe_resample_prior": (I, [P, P, C.POINTER(ResampleParams), C.POINTER(ResampleOut)]),
+        "pfmpe_host_resample_source": (I, [C.POINTER(C.c_uint8), I64, C.c_int32, I64, C.POINTER(C.c_int32),
+                                           C.POINTER(I64)]),
+        "pfmpe_host_resample_rank": (I, [I64, I64, I64, C.POINTER(I64)]),
         "pfmpe_default_refine_params": (None, [C.POINTER(RefineParams)]),
         "pfmpe_refine_poses": (I, [P, C.POINTER(AssocIn), C.POINTER(RefineParams), dp, C.POINTER(C.c_uint32), C.c_int32,
                                    C.POINTER(RefineOut), P, dp]),
@@ -961,6 +981,26 @@ class Engine:
             mode_of.ctypes.data_as(C.POINTER(C.c_uint8)) if want_mode_of else None))
         return [o.as_dict() for o in out], mode_of
 
+    def resample_prior(self, n_new: int, src=None, seeds=None, mode: int = 0, trans_scale=None, rot_scale=None,
+                       max_dist: float = 0.0) -> dict:
+        """A new prior of n_new particles for this engine from the members of src's prior (src None: this engine's own,
+        in place), gathered on the device (pfmpe_resample_prior).  seeds None: every particle is a member; else the
+        members are the particles cloud_modes(CLOUD_POSTERIOR, seeds, ...) gives `mode` (0 .. K-1, or MODE_NONE), with
+        the same scales and gate (defaults: pfmpe_default_modes_params).  Returns {"n_src", "n_members", "n_new"};
+        n_new is 0, and this engine unchanged, when the mode has no member."""
+        src = self if src is None else src
+        prm = ResampleParams()
+        prm.n_new = int(n_new)
+        if seeds is not None:
+            sd, prm.modes = _modes_args(seeds, None, trans_scale, rot_scale, max_dist)
+            prm.K, prm.seeds, prm.mode = sd.shape[0], _dptr(sd), int(mode)
+        out = ResampleOut()
+        self._chk(self.lib.pfmpe_resample_prior(self.ctx, src.ctx, C.byref(prm), C.byref(out)))
+        if out.n_new > 0:
+            self.N = int(out.n_new)
+            self._last_out = None
+        return out.as_dict()
+
     @staticmethod
     def _assoc_in(blobs, bank_frame):
         ai = AssocIn()
@@ -1463,6 +1503,30 @@ def host_cloud_assign(poses, seeds, params=None, trans_scale=None, rot_scale=Non
     if rc != OK:
         raise PFError(rc, "host_cloud_assign: bad arguments")
     return mode_of[: p.shape[0]], counts
+
+
+def host_resample_source(mode_of, mode: int, n_new: int, N=None) -> tuple:
+    """The source particle of every slot of a new prior of n_new particles (pfmpe_host_resample_source), by the rule
+    pfmpe_resample_prior runs: (source (int32, n_new entries; none when there is no member), n_members).  mode_of: every
+    particle's mode (uint8), the members being those equal to `mode`; None with N: all N particles are members."""
+    mo = None if mode_of is None else np.ascontiguousarray(mode_of, dtype=np.uint8)
+    n = int(N) if mo is None else mo.shape[0]
+    source = np.empty(max(int(n_new), 1), dtype=np.int32)
+    m = C.c_int64(-1)
+    rc = load().pfmpe_host_resample_source(None if mo is None else mo.ctypes.data_as(C.POINTER(C.c_uint8)), n, int(mode),
+                                           int(n_new), source.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(m))
+    if rc != OK:
+        raise PFError(rc, "host_resample_source: bad arguments")
+    return source[: int(n_new) if m.value > 0 else 0].copy(), m.value
+
+
+def host_resample_rank(k: int, m: int, n_new: int) -> int:
+    """The rank of the member slot k of n_new copies, of m members (pfmpe_host_resample_rank)."""
+    r = C.c_int64(-1)
+    rc = load().pfmpe_host_resample_rank(int(k), int(m), int(n_new), C.byref(r))
+    if rc != OK:
+        raise PFError(rc, "host_resample_rank: bad arguments")
+    return r.value
 
 
 def make_detect_images(images):

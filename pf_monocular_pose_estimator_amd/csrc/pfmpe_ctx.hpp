@@ -217,6 +217,10 @@ struct pfmpe_ctx : CtxQueue {
   // up to 4 (grown on demand, never shrunk); and the pinned block the counts are read back into
   Buf<unsigned char> d_modes;
   Buf<unsigned char, Mem::Pinned> h_modes;
+  // pfmpe_resample_prior with a mode filter (owned by dst, which also lends d_modes / h_modes): the member total, then
+  // the member prefixes of the source's 256-particle blocks (RsLayout, pfmpe_resample_prior.hip); grown on demand,
+  // never shrunk
+  Buf<unsigned char> d_resample;
   // pfmpe_assoc_stats_multi (owned by the batch's first context; pfmpe_assoc_stats is a batch of one): the device copy of the batch's image (launch heads,
   // descriptors, every entry's blob table) followed by the bins of all entries, and the pinned block the image is
   // built in and the bins are read back into (same layout); grown on demand, never shrunk
